@@ -3,8 +3,13 @@
 Benchmark of the sGDML hot path on MI355X (BASELINE.json metric: kernel-matrix build+solve
 wall-clock [s] and predict forces/s at N_train=1000, aspirin-sized = 21 atoms).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N=1: plain python)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     (N=1: plain python)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W untimed and K timed steps, and prints the headline line.  Everything else the line can carry
+(residual check, per-kernel rooflines, prediction by batch size, symmetry search, the configs[] entries, the CPU baseline;
+N > 1: the configs[2] legs beside the analytic value) is measured only with --full.  --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy (N = 1 analytic: alphas, E, F of the query batch), from inputs fixed by the arguments.
 
 `value` measures the SAME workload for every --gpus N (--workload, default analytic), so that a driver's N = 1, 2, 4, 8 runs
 form a curve; `metric` / `config.workload` come from line_skeleton() and are identical across N:
@@ -40,6 +45,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 FP64_MFMA_PEAK_TF = 78.6  # MI355X fp64 matrix peak (256 CU x 4 SIMD x 2.4 GHz x 32 flop/clk)
+DUMP_CAP_BYTES = 64 * 10**6  # --dump-outputs writes at most this much in all
 
 
 def line_skeleton(workload, n_atoms, n_train, world, cg_iters=None, cg_inducing=None):
@@ -526,26 +532,35 @@ def main():
     ap.add_argument('--n-query', type=int, default=1000)
     ap.add_argument('--sig', type=float, default=20.0)
     ap.add_argument('--lam', type=float, default=1e-10)
-    ap.add_argument('--no-cpu', action='store_true', help='skip the CPU-baseline leg')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline (residual, rooflines, prediction by batch, '
+                         'symmetry search, configs[], CPU baseline; N>1: the configs[2] legs)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float64; N=1 analytic workload)')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: skip the CPU-baseline leg')
     ap.add_argument('--cpu-sample', type=int, default=500, help='training points of the CPU sample that runs beside the configs[] section')
     ap.add_argument('--cpu-full', action='store_true', help='time the CPU port at the benchmark size in this run (4-5 minutes of host time, overlapped with the GPU work)')
-    ap.add_argument('--no-configs', action='store_true', help='N=1: skip the configs[0] sweep and the configs[2] point')
-    ap.add_argument('--no-profile', action='store_true', help='do not bracket kernels with HIP events')
+    ap.add_argument('--no-configs', action='store_true', help='--full, N=1: skip the configs[0] sweep and the configs[2] point')
+    ap.add_argument('--no-profile', action='store_true', help='--full: do not bracket kernels with HIP events')
     ap.add_argument('--separate-solve', action='store_true',
                     help='A/B: forward substitution as a separate triangular solve instead of inside the factorisation')
     ap.add_argument('--cg-n-train', type=int, default=5000)
     ap.add_argument('--cg-inducing', type=int, default=200)
     ap.add_argument('--cg-iters', type=int, default=50, help='PCG iterations per step of the configs[2] workload')
-    ap.add_argument('--no-to-tol', action='store_true', help='N>1: skip the sharded run to solver_tol')
+    ap.add_argument('--no-to-tol', action='store_true', help='--full, N>1: skip the sharded run to solver_tol')
     ap.add_argument('--dist-chol-timeout', type=float, default=900.0, help='N>1: seconds the distributed-Cholesky measurement may take')
     ap.add_argument('--to-tol-timeout', type=float, default=600.0, help='N>1: seconds the sharded run to solver_tol may take')
     ap.add_argument('--dist-chol', action='store_true', help='N>1: also time the configs[1] system through the distributed Cholesky')
     ap.add_argument('--workload', default='auto', choices=('auto', 'analytic', 'cg'),
                     help="what `value` measures, the SAME for every --gpus N: analytic (default) = configs[1] build+solve (N>1: "
                          "through the distributed Cholesky); cg = the configs[2] sharded Nystroem-PCG step")
-    ap.add_argument('--no-cg-extras', action='store_true', help='N>1 analytic: skip the configs[2] step / time-to-tol blocks')
+    ap.add_argument('--no-cg-extras', action='store_true', help='--full, N>1 analytic: skip the configs[2] step / time-to-tol blocks')
     ap.add_argument('--comm', default='auto', help="N>1: 'rccl', 'host' (collectives staged through the host channel), or auto (rccl if every rank has a GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.dump_outputs and (args.gpus != 1 or args.workload == 'cg'):
+        ap.error('--dump-outputs: only the one-GPU analytic workload')
 
     # ---- `--gpus N` with N > 1 and no launcher around us: become the launcher (one rank per GPU over RCCL)
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -664,7 +679,7 @@ def run_multi(args, rank, world, workload):
         return [max(e[i] for e in every) for i in range(len(values))]
 
     N, M, k = args.n_atoms, args.cg_n_train, args.cg_inducing
-    with_cg = workload == 'cg' or not args.no_cg_extras
+    with_cg = workload == 'cg' or (args.full and not args.no_cg_extras)
     with_chol = world > 1 and (workload == 'analytic' or args.dist_chol)
 
     # ---- configs[1] (n = 63 000) through the distributed Cholesky over the communicator: the `value` of the default N > 1
@@ -785,7 +800,7 @@ def run_multi(args, rank, world, workload):
     # (leverage-sampled inducing points, the reference's restart policy): what a SCALE record means as a SOLVE
     to_tol = None
     hung = chol_hung
-    if with_cg and not args.no_to_tol:
+    if with_cg and args.full and not args.no_to_tol:
         # in a worker thread under a time limit: this leg builds a second communicator and runs several hundred sharded
         # iterations; should a collective ever hang on some node, the line above must still be printed (the main
         # thread gives up waiting, reports it, and the process leaves through os._exit)
@@ -811,13 +826,13 @@ def run_multi(args, rank, world, workload):
             to_tol['time_to_tol_s'] = to_tol['train_wall_s'] = tw
 
     one_gpu = None
-    if rank == 0 and not hung and world > 1 and res is not None:  # the 1-GPU point of the configs[2] curve, same run, rank 0's GPU
+    if args.full and rank == 0 and not hung and world > 1 and res is not None:  # the 1-GPU point of the configs[2] curve, same run, rank 0's GPU
         c1 = _lib.Context(local_rank % max(1, n_dev))
         wl1 = make_cg_workload(c1, N, M, k, args.sig, args.lam)
         one_gpu = time_cg(c1, wl1, args.cg_iters, 1, 1, c1.sync)
         c1.close()
     cpu = None
-    if rank == 0 and not hung and not args.no_cpu:
+    if args.full and rank == 0 and not hung and not args.no_cpu:
         try:
             cpu = cpu_baseline(N, args.sig, args.lam, args.n_train)
         except Exception as e:
@@ -1011,7 +1026,8 @@ def run_analytic(args):
         first_call['process_start_to_first_solution_s'] = time.perf_counter() - t_first
     for _ in range(n_warm):
         step(False)
-    if not args.no_profile:
+    profiled = args.full and not args.no_profile
+    if profiled:
         ctx.profile(True)
     ctx.sync()
     t0 = time.perf_counter()
@@ -1019,19 +1035,67 @@ def run_analytic(args):
         alphas = step(True)
     ctx.sync()
     t1 = time.perf_counter()
-    wall_ms = (t1 - t0) * 1e3 / max(1, args.steps)
+    wall_ms = (t1 - t0) * 1e3 / args.steps
     build_solve_ms = float(np.mean(phases['assemble']) + np.mean(phases['factor']) + np.mean(phases['solve']))
     pred_ms = float(np.mean(phases['predict']))
+
+    if args.dump_outputs:  # what a caller of the timed path receives from its last step
+        E_out, F_out = np.empty(B), np.empty((B, N3))
+        ctx._check(lib.gdml_memcpy_d2h(ctx._h, E_out.ctypes.data_as(C.c_void_p), dE, E_out.nbytes))
+        ctx._check(lib.gdml_memcpy_d2h(ctx._h, F_out.ctypes.data_as(C.c_void_p), dF, F_out.nbytes))
+        dump = {'alphas': np.asarray(alphas, dtype=np.float64), 'E': E_out, 'F': F_out}
+        total = sum(a.nbytes for a in dump.values())
+        if total > DUMP_CAP_BYTES:  # larger than the default sizes: the same seeded sample of rows in every run
+            for name, a in dump.items():
+                keep = max(1, len(a) * DUMP_CAP_BYTES // total)
+                dump[name] = a[np.sort(np.random.RandomState(0).choice(len(a), keep, replace=False))]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
+
+    chol_tf = (n**3 / 3.0) / (np.mean(phases['factor']) * 1e-3) / 1e12
+    sk = line_skeleton('analytic', N, M, 1)
+    out = {
+        'metric': sk['metric'],
+        'value': build_solve_ms / 1e3,
+        'unit': 's',
+        'n_gpus': 1,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'ms_per_step': wall_ms,
+        'higher_is_better': False,
+        'scaling': 'strong',
+        'vs_baseline': None,
+        'dtype': 'f64',
+        'data': 'synthetic',
+        'config': {'workload': sk['workload'], 'n_atoms': N, 'n_train': M, 'n_perms': 1, 'sig': sig, 'lam': args.lam,
+                   'matrix_n': n, 'query_batch': B, 'parallelism': sk['parallelism']},
+        'phases_ms': {k: float(np.mean(v)) for k, v in phases.items()},
+        'cholesky_info': info_last[0],
+        'cholesky_TFLOPs_whole_factorization': chol_tf,
+        'predict': {'geoms_per_s': B / (pred_ms * 1e-3), 'forces_per_s': B * N3 / (pred_ms * 1e-3),
+                    'batch': B, 'ms': pred_ms},
+        'roofline': None,
+    }
+    out['first_call_in_process'] = dict(first_call, note='context creation, descriptors + upload, then the first step (warm-up, untimed): '
+                                        'first_build_solve_s are its device phases (first_step_s - that = hipMalloc of the matrix, code-object '
+                                        'loading, model upload); `value` is the steady state')
+    # the point this line contributes to a `--gpus 1, 2, 4, 8` curve (same keys in the N > 1 line)
+    out['scale_point'] = {'workload': sk['workload'], 'seconds': out['value'], 'n_gpus': 1, 'roofline_frac': None}
+    if not args.full:
+        ctx.close()
+        return out
 
     # sanity of the result that was timed: residual of the solve through the matrix-free operator
     Kv = ctx.kernel_matvec(args.lam, False, -alphas)
     resid = float(np.linalg.norm(-Kv - y) / np.linalg.norm(y))  # (-K + lam I) x = -(Kx - lam x)
     if not resid < 1e-10:  # a fast wrong answer is not a result (the analytic contract)
         raise SystemExit('bench: residual of the timed solve is %.3e (> 1e-10): refusing to report' % resid)
+    out['solve_rel_residual'] = resid
     roof = None
     extra = {}
     traffic = load_pmc_traffic()
-    if not args.no_profile:
+    if profiled:
         # dominant kernel: gemm_nt_sub_diag_kernel, the trailing-update launches of the blocked Cholesky (each also carries
         # the workgroup that factors the next diagonal block); the plain gemm_nt_sub_kernel launches (first / last panels,
         # K = 64 steps of the tail) are reported next to it
@@ -1067,38 +1131,9 @@ def run_analytic(args):
         if p_ms > 0:
             extra['predict_kernel'] = {'kernel': 'predict_kernel', 'avg_launch_ms': p_ms / max(1, p_n),
                                        'algorithmic_TFLOPs': p_fl / (p_ms * 1e-3) / 1e12}
-    chol_tf = (n**3 / 3.0) / (np.mean(phases['factor']) * 1e-3) / 1e12
-    sk = line_skeleton('analytic', N, M, 1)
-    out = {
-        'metric': sk['metric'],
-        'value': build_solve_ms / 1e3,
-        'unit': 's',
-        'n_gpus': 1,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'ms_per_step': wall_ms,
-        'higher_is_better': False,
-        'scaling': 'strong',
-        'vs_baseline': None,
-        'dtype': 'f64',
-        'data': 'synthetic',
-        'config': {'workload': sk['workload'], 'n_atoms': N, 'n_train': M, 'n_perms': 1, 'sig': sig, 'lam': args.lam,
-                   'matrix_n': n, 'query_batch': B, 'parallelism': sk['parallelism']},
-        'phases_ms': {k: float(np.mean(v)) for k, v in phases.items()},
-        'cholesky_info': info_last[0],
-        'solve_rel_residual': resid,
-        'cholesky_TFLOPs_whole_factorization': chol_tf,
-        'predict': {'geoms_per_s': B / (pred_ms * 1e-3), 'forces_per_s': B * N3 / (pred_ms * 1e-3),
-                    'batch': B, 'ms': pred_ms},
-        'roofline': roof,
-    }
+    out['roofline'] = roof
     out.update(extra)
-    out['first_call_in_process'] = dict(first_call, note='context creation, descriptors + upload, then the first step (warm-up, untimed): '
-                                        'first_build_solve_s are its device phases (first_step_s - that = hipMalloc of the matrix, code-object '
-                                        'loading, model upload); `value` is the steady state')
-    # the point this line contributes to a `--gpus 1, 2, 4, 8` curve (same keys in the N > 1 line)
-    out['scale_point'] = {'workload': sk['workload'], 'seconds': out['value'], 'n_gpus': 1,
-                          'roofline_frac': None if roof is None else roof['frac']}
+    out['scale_point']['roofline_frac'] = None if roof is None else roof['frac']
     cpu_handle = None
     try:  # the metric names "predict forces/sec": the resident model at four batch sizes, with both rooflines
         ctx.profile(False)

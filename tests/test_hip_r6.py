@@ -123,12 +123,13 @@ def test_bench_lines_for_one_and_two_ranks_carry_the_same_metric(tmp_path):
     """`python bench.py` and `python bench.py --gpus 2 --comm host` (two ranks sharing the GPU, host-staged collectives, the
     module's own launcher) at a reduced size: ONE JSON line each, identical `metric` and `config.workload`, `scale_point`
     under the same keys, the two-rank value produced by the distributed Cholesky with a residual at the contract; the
-    `--workload cg` lines of both rank counts agree with each other as well."""
+    `--workload cg` lines of both rank counts agree with each other as well.  With --full: the residuals and the configs[2]
+    legs are measured only there."""
     import json
     import subprocess
 
     env = dict(os.environ, OMP_NUM_THREADS='2')
-    common = ['--steps', '1', '--warmup', '1', '--no-cpu', '--n-train', '96', '--cg-n-train', '160', '--cg-inducing', '8',
+    common = ['--full', '--steps', '1', '--warmup', '1', '--no-cpu', '--n-train', '96', '--cg-n-train', '160', '--cg-inducing', '8',
               '--cg-iters', '5', '--no-to-tol']
 
     def line(extra):
@@ -152,6 +153,48 @@ def test_bench_lines_for_one_and_two_ranks_carry_the_same_metric(tmp_path):
     cg2 = line(['--workload', 'cg', '--gpus', '2', '--comm', 'host'])
     assert cg1['metric'] == cg2['metric'] and cg1['config']['workload'] == cg2['config']['workload']
     assert cg1['value'] > 0 and cg2['value'] > 0 and (cg1['n_gpus'], cg2['n_gpus']) == (1, 2)
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path, ctx):
+    """`python bench.py --steps 2 --warmup 1 --dump-outputs DIR` (no --full) at a reduced size: ONE JSON line with the
+    headline keys and `steps` as asked, none of the --full measurements, and DIR/alphas, E, F of the last timed step: the
+    alphas solve the benchmark's system (residual through the matrix-free operator at the contract), E / F are the
+    predictions of the model they define for the query batch."""
+    import json
+    import subprocess
+
+    import bench
+
+    N, M, B, sig, lam = 21, 96, 64, 20.0, 1e-10
+    out = tmp_path / 'outputs'
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--n-train', str(M),
+                        '--n-query', str(B), '--dump-outputs', str(out)], env=dict(os.environ, OMP_NUM_THREADS='2'),
+                       capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert p.returncode == 0, p.stderr[-3000:]
+    rows = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+    assert len(rows) == 1, p.stdout[-2000:]
+    line = json.loads(rows[0])
+    assert line['steps'] == 2 and line['warmup'] == 1 and line['value'] > 0 and line['ms_per_step'] > 0
+    assert (line['unit'], line['dtype'], line['higher_is_better']) == ('s', 'f64', False)
+    assert line['metric'] == bench.line_skeleton('analytic', N, M, 1)['metric']
+    assert not {'solve_rel_residual', 'roofline_predict', 'symmetry_search', 'configs', 'cpu_baseline'} & set(line)
+
+    got = {k: np.load(str(out / (k + '.npy'))) for k in ('alphas', 'E', 'F')}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got['alphas'].shape == (M * 3 * N,) and got['E'].shape == (B,) and got['F'].shape == (B, 3 * N)
+    R, E, F = bench.synth_geometries(N, M + B, seed=0)
+    Rf = R.reshape(M + B, -1)
+    y = F[:M].ravel() / np.std(F[:M].ravel())
+    tp = np.arange(N * (N - 1) // 2, dtype=np.int64)[None]
+    xd, gd = ctx.desc_from_R(Rf[:M], N)
+    ctx.train_upload(xd, gd, tp)
+    ctx.predict_upload_model(xd, np.zeros_like(xd), tp, sig, None)
+    r = ctx.kernel_matvec(lam, False, -got['alphas']) + y
+    assert np.linalg.norm(r) <= 1e-10 * np.linalg.norm(y)
+    ctx.set_alphas(got['alphas'])
+    Eq, Fq = ctx.predict(Rf[M:])
+    assert np.abs(Fq - got['F']).max() <= 1e-10 * np.abs(Fq).max()
+    assert np.abs(Eq - got['E']).max() <= 1e-10 * np.abs(Eq).max()
 
 
 def test_persistent_trailing_update_is_bitwise_the_plain_one(ctx):

@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-$(dirname $0)/..}
 for o in "$@"; do
   [ "$o" = "-" ] && unset GDML_OPTIONS || export GDML_OPTIONS=$o
-  python bench.py --steps ${STEPS:-2} --warmup 1 --no-cpu --no-configs 2>/tmp/bench_opts.err | tail -1 > /tmp/bench_opts.json
+  python bench.py --full --steps ${STEPS:-2} --warmup 1 --no-cpu --no-configs 2>/tmp/bench_opts.err | tail -1 > /tmp/bench_opts.json
   python - "$o" <<'PY'
 import json, sys
 try:
