@@ -124,36 +124,17 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *                         from the registers, 24 bytes per lane and row; 0 = through LDS in four passes of full-row stores), asm.perm2_chunk (12) pair
  *                         entries per lane and task, asm.perm2_i_chunk (16) row points per workgroup, asm.perm2_debug (0)
  *                         timing-only ablation mask (results are wrong when set)
- *   gemm.debug (0)        ablation mask of the GEMM kernel (separate instantiation; 0 = production kernel)
- *   gemm.persist (0)      1: fused trailing updates of at least four rounds run as 2 resident workgroups per CU that pull tiles
- *                         from per-XCD counters (round 6; measured 1.5 % slower than one workgroup per tile: off)
- *   gemm.n64 (0)          1: trailing updates on 128 x 64 tiles with three workgroups per CU (A/B: profiles/r06_gemm_n64_ab.txt)
- *   gemm.fill_tiles (0)   prediction contractions (D > 256): 128 x 64 tiles when they fill the chip better than 128 x 128 ones
- *                         (measured slower on the launch it was meant for: profiles/r06_matvec_probe.txt)
  *   predict.wide_pad (1)  the same contractions on tables / queries padded to whole tiles (no edge tiles); 0 = round 5's shapes
  *   predict.tn_fill (1)   split count of the prediction back contraction (D > 256) chosen so that its units fill whole rounds of the
  *                         chip (0 = round 5's rule: at least three rounds' worth)
  *   nys.syrk_split (1)    Gram matrix K_nm^T K_nm of the Nystroem build cut along the rows into up to 8 partial sums when its tile
  *                         count is only a few rounds of the chip (a tile's k loop is as long as the factor is tall); 0 = one pass
  *   nys.trsm_left (1)     tall triangular solves of the Nystroem build left-looking (one deep product per 512-column strip); 0 = right-looking
- *   gemm.trace (0)        k > 0: the k-th fused launch runs the traced instantiation and leaves gemm_trace.bin (tools/gemm_trace.py)
- *   gemm.nt_c (0)         non-temporal loads / stores of the C tile (after rocBLAS's Tensile kernel for this shape:
- *                         profiles/r03_vendor_kernels.txt; no gain measured)
- *   gemm.lds16 (3)        fused GEMM launches: 3 = the production loop (16-byte LDS layout, operand pairs of the next half k-tile
- *                         requested 16 MFMAs ahead, last k-tile peeled); 2 = the same with the last k-tile inside the loop (A/B).
- *                         The 8-byte layout, the late-commit and the load-subtract-store variants of rounds 2-3 are gone from
- *                         the fused kernel (their A/Bs: profiles/r03_gemm_*.txt)
- *   chol.nb (512: a multiple of 64 up to 512, anything else falls back to 512), chol.fused_diag (1), chol.fused_min_rows (12288), chol.panel_kernel (1), chol.panel_fused (1),
- *   chol.small_update (1) rank-64 updates inside the panel chain through rank64_update_kernel (0: the GEMM tile kernel; A/B)
- *   chol.lookahead (1)    factorisation schedule (fused_diag = 0: the round-1 second-stream look-ahead schedule)
- *   chol.outer (1024)     panel pairs: K = 2 nb trailing update in two launches (= chol.nb: single panels only)
+ *   chol.nb (512)         panel width of the blocked Cholesky (a multiple of 64 up to 512, anything else falls back to 512)
+ *   chol.fused_min_rows (12288)  trailing rows from which a panel's diagonal block is factored inside the trailing-update launch
+ *   chol.outer (1024)     panel pairs: K = 2 nb trailing update in two launches (= chol.nb, or chol.nb not a multiple of 128:
+ *                         single panels only)
  *   chol.outer_min_rows (16384)  trailing rows below which new panels are single again
- *   chol.block (0)        W > 0 (multiple of 1024, >= 2048, n >= 3 W): two-level factorisation -- column blocks of W columns, each
- *                         factored with all rows below it carried along, then one lower update of depth W (0.90 of the peak instead
- *                         of 0.86) for everything to its right; the blocks' own factorisation eats the gain: 0.6-1.3 % slower
- *                         (profiles/r06_chol_block.txt).  chol.block_f (2): weight of rows x columns in a tall block's thresholds
- *   chol.merge_gemm1 (1)  the pair's own columns as first super-tile column of the trailing-update launch
- *   chol.tail_lookahead (1)  tail: step chain of the next panel on the high-priority stream
  *   trsm.debug (0)        timing-only ablation mask of the row-local panel solve (results are wrong when set)
  *   trsv.persist (1)      backward substitution as one persistent launch
  *   predict.wave_only (0), predict.mfma (1), predict.mfma_wide (1), predict.fill   prediction kernel choice

@@ -716,7 +716,7 @@ static int tall_trsm(gdml_ctx* ctx, const double* L, double* X, int64_t n, int64
     if (left && k0 > 0)  // X[:, k0:k0+nb] -= X[:, 0:k0] L[k0:k0+nb, 0:k0]^T
       GDML_TRY(launch_gemm_nt_sub(ctx, st, X, ld, L + k0 * ld, ld, X + k0, ld, n, nb, k0, 0));
     const bool aligned = ((reinterpret_cast<uintptr_t>(L) | reinterpret_cast<uintptr_t>(X)) & 31) == 0 && (ld % 4 == 0);
-    if (nb % 64 == 0 && aligned && ctx_opt_i(ctx, "chol.panel_kernel", 1)) {
+    if (nb % 64 == 0 && aligned) {
       // whole NB-wide strip in one row-local launch (the kernel of the Cholesky panels) instead of 8 x (trsm64 + K = 64 GEMM)
       GDML_TRY(launch_panel_trsm(ctx, st, L + k0 * ld + k0, X + k0, ld, (int)nb, n));
     } else

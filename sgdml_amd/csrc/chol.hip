@@ -17,9 +17,9 @@
 // block is factored by the multi-workgroup 64-wide step chain (potrf_trsm64 + K = 64 GEMM) instead.
 // A right-hand side stored as an extra row is carried through (forward substitution for free); the backward
 // substitution is one persistent launch with a per-block fallback.  n^3/3 of the flops are in gemm_nt_sub.
-// The round-1 schedule (step chain on a second stream with one panel of look-ahead) is still selectable with option
-// chol.fused_diag = 0; profiles/r02_panel_fusion_ab.txt has the comparison.  The CU-masked / split-stream / chunked
-// variants measured in rounds 1-2 (profiles/r01_chol_timeline_split.txt, r02_sched_probe.txt) are gone.
+// The round-1 schedule (step chain on a second stream with one panel of look-ahead; profiles/r02_panel_fusion_ab.txt), the
+// CU-masked / split-stream / chunked variants of rounds 1-2 (profiles/r01_chol_timeline_split.txt, r02_sched_probe.txt) and the
+// two-level, persistent and narrow-tile forms of round 6 were measured slower and are gone.
 #include "common.h"
 #include <type_traits>
 #include <utility>
@@ -31,18 +31,13 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 // C[M x N] -= A[M x K] * B[N x K]^T     (row-major, leading dimensions lda/ldb/ldc)
 // lower != 0: C is square-symmetric-updated, only tiles with tile_row >= tile_col are computed.
 // Workgroup: 256 threads = 4 waves (2 x 2), tile 128 x 128, each wave 64 x 64 = 4 x 4 MFMA tiles.
-// LDS: [row][BK+1] doubles per operand and stage: pitch 17 doubles = 34 dwords makes the MFMA operand
-// pattern lane -> (row = l&15, k = l>>4) conflict-free for ds_read_b64 AND for the ds_read2_b64 the
-// compiler merges them into (16-lane groups, 32 banks: 34 i mod 32 = 2 i), and the 8-byte row writes too.
+// LDS: two stages of the A and B tiles in the 16-byte layout of gemm_store_tile16.  The array keeps the pitch-17 size
+// (GT * GPITCH doubles per operand and stage) of the round-1 8-byte layout: the diagonal-block role of the fused launch
+// uses it as its scratch.
 // ------------------------------------------------------------------------------------------
 #define GT 128
 #define GBK 16
 #define GPITCH 17
-#define G6N 64  // tile columns of the 128 x 64 kernel (gemm.n64)
-#ifndef GEMM_COMMIT_KS
-#define GEMM_COMMIT_KS 12  // k-step after which the prefetched tile is written to LDS (0,4,8,12): 12 = as late as possible,
-                           // the global loads of the next tile get the whole tile to arrive (4 -> 12: -1.1 % factorisation time)
-#endif
 
 struct GemmArgs {
   const double* A;
@@ -65,8 +60,6 @@ struct GemmArgs {
   int diag_nbw;     // nb / 64
   int64_t diag_off; // global index of its first row (LAPACK info)
   int* diag_info;
-  int dbg;          // option gemm.debug: ablation bits: 1 no epilogue, 2 no tile loads, 4 no LDS reads, 8 no barrier
-  int nt_c;         // option gemm.nt_c: non-temporal loads / stores of the C tile (it is streamed: keep the L2 for the panels)
   // merged trailing update (lower): the first super-tile COLUMN (the next outer panel's own columns) is enumerated
   // first; the tiles of its leading ready_rows x ready_rows tile block (the diagonal block workgroup 0 is about to
   // factor) count themselves into *ready when their C tile is stored, workgroup 0 waits for ready_target
@@ -81,19 +74,9 @@ struct GemmArgs {
   double* C2;
   int64_t M2, N2, K2;
   int tiles2;
-  // persistent launch (gemm_nt_sub_persist_kernel): 8 tile counters, one per XCD, 64 bytes apart; total work items
-  unsigned* queue;
-  int64_t n_items;
-  // option gemm.trace (tools/gemm_trace.py): per-tile shader-clock stamps of the traced instantiation, 8 words per workgroup
-  unsigned long long* trace;
 };
 
-template <bool PIPE, bool CACC, int CKS = GEMM_COMMIT_KS>
 __global__ void __launch_bounds__(256, 2) gemm_nt_sub_diag_kernel(GemmArgs g);
-__global__ void __launch_bounds__(256, 2) gemm_nt_sub_diag_trace_kernel(GemmArgs g);
-template <int CKS, int FLAGS = 2>
-__global__ void __launch_bounds__(256, 2) gemm_nt_sub_persist_kernel(GemmArgs g);
-__global__ void __launch_bounds__(256, 3) gemm_nt_sub_n64_kernel(GemmArgs g);
 
 template <bool FULL>
 __device__ __forceinline__ void gemm_load_tile(const double* __restrict__ G, int64_t ld,
@@ -120,19 +103,17 @@ __device__ __forceinline__ void gemm_load_tile(const double* __restrict__ G, int
   }
 }
 
-// 16-byte layout (option gemm.lds16): element (row, kq = k / 2) is the pair (k, k + 1) of a row, stored at d2 index
-// kq * 128 + (row ^ kq).  One ds_write_b128 per chunk instead of two ds_write_b64, one ds_read_b128 per operand block and
-// PAIR of k-steps instead of two 8-byte reads; the XOR keeps both conflict free: a group of 8 store lanes holds one row and
-// kq = 0..7 (8 different bank quads), a 16-lane read group holds 16 different (row ^ kq) & 15 (searched by script, see
-// DESIGN 3.2).  The MFMA's k index is a label: lane group g = lane >> 4 feeds k = 4 g + s into k-step s (both operands), so
-// that a lane's four k of a tile are contiguous.
+// 16-byte layout: element (row, kq = k / 2) is the pair (k, k + 1) of a row, stored at d2 index kq * 128 + (row ^ kq).  One
+// ds_write_b128 per chunk instead of two ds_write_b64, one ds_read_b128 per operand block and PAIR of k-steps instead of two
+// 8-byte reads; the XOR keeps both conflict free: a group of 8 store lanes holds one row and kq = 0..7 (8 different bank
+// quads), a 16-lane read group holds 16 different (row ^ kq) & 15 (searched by script).  The MFMA's k index is
+// a label: lane group g = lane >> 4 feeds k = 4 g + s into k-step s (both operands), so that a lane's four k of a tile are
+// contiguous.
 // Full tiles, 16-byte aligned: wave-uniform base (tile corner + k offset: SGPRs) + the thread's constant 32-bit byte offsets
 // (row * ld + kc of its four chunks; a tile spans < 2^31 bytes): saddr-form loads, no 64-bit address arithmetic per k-tile.
-// Full tiles, 16-byte aligned: wave-uniform base (tile corner + k offset) + the thread's constant 32-bit byte offsets (row * ld + kc
-// of its four chunks; a tile spans < 2^31 bytes).  Round 6 measured the same loads as BUFFER loads (tile corner in a resource, lane
-// offset as voffset, k offset as soffset: no 64-bit lane arithmetic at all): 2.0-2.2 % SLOWER factorisation on two boxes
-// (profiles/r06_gemm_variants.txt); and issuing them 16 MFMAs later (after the first MFMA group): +5.8 % -- the 48 MFMAs
-// between issue and LDS commit are needed.
+// Round 6 measured the same loads as BUFFER loads (tile corner in a resource, lane offset as voffset, k offset as soffset: no
+// 64-bit lane arithmetic at all): 2.0-2.2 % SLOWER factorisation on two boxes (profiles/r06_gemm_variants.txt); and issuing
+// them 16 MFMAs later (after the first MFMA group): +5.8 % -- the 48 MFMAs between issue and LDS commit are needed.
 __device__ __forceinline__ void gemm_load_tile_g(const double* __restrict__ base, const unsigned (&off)[4], d2 (&r)[4]) {
   typedef const __attribute__((address_space(1))) char* gcptr;
   typedef const __attribute__((address_space(1))) d2* gd2ptr;
@@ -153,41 +134,17 @@ __device__ __forceinline__ void gemm_store_tile16(double* __restrict__ S, int ti
   }
 }
 
-__device__ __forceinline__ void gemm_store_tile(double* __restrict__ S, int tid, const d2 (&r)[4]) {
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    int cidx = tid + 256 * s;
-    int row = cidx >> 3, kc = (cidx & 7) * 2;
-    S[row * GPITCH + kc] = r[s].x;
-    S[row * GPITCH + kc + 1] = r[s].y;
-  }
-}
-
-// ABL = true only in the ablation instantiation (option gemm.debug != 0): the production kernel carries
-// none of the ablation branches.
-// FLAGS: 1 = traced instantiation; 2 = persistent caller: lane-derived values are recomputed per tile from an opaque copy of the
-// thread index (otherwise they are hoisted out of the tile loop and spilled across the k loop)
-template <bool FULL, bool ABL, bool PIPE = false, bool CACC = true, int CKS = GEMM_COMMIT_KS, int FLAGS = 0>
-__device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, double (*lds)[2][GT * GPITCH],
-                                               int64_t row0, int64_t col0, int64_t trace_slot = 0, unsigned* s_next = nullptr) {
-  const int dbg = ABL ? g.dbg : 0;
-  // traced instantiation only: stamps of the tile's phases and the time parked before / in the k-tile barrier
-  unsigned long long tr_t0 = 0, tr_t1 = 0, tr_t3 = 0, tr_vm = 0, tr_bar = 0, tr_mx = 0;
-  constexpr bool TR = (FLAGS & 1) != 0;
-  if constexpr (TR) tr_t0 = __builtin_amdgcn_s_memtime();
-  int tid_ = threadIdx.x;
-  if constexpr ((FLAGS & 2) != 0) asm volatile("" : "+v"(tid_));
-  const int tid = tid_, lane = tid & 63, wave = tid >> 6;
+// OW: overwrite, C = -A B^T (C is not read: the caller need not clear it)
+template <bool FULL, bool OW>
+__device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, double (*lds)[2][GT * GPITCH], int64_t row0, int64_t col0) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int li = lane & 15, lk = lane >> 4;
 
-  // C -= A B^T as acc = C; acc += (-A) B^T; C = acc for interior tiles: the 64 C loads per lane are issued with the first
+  // C -= A B^T as acc = -C; acc += A B^T; C = -acc for interior tiles: the 64 C loads per lane are issued with the first
   // operand tiles (their latency is paid once, together with the prologue's), the epilogue is stores only -- instead of
-  // four load->store round trips after the last MFMA.  f64 MFMA C/D layout: col = lane & 15, row = (lane >> 4) + 4 r.
-  constexpr bool OW = (FLAGS & 4) != 0;  // overwrite: C = -A B^T (C is not read: the caller need not clear it)
-  constexpr bool CIN = FULL && !ABL && CACC;
-  constexpr double SGN = PIPE ? -1.0 : 1.0;  // 16-byte layout: the accumulator holds -C + A B^T
-  double* Cw = g.C + (row0 + wm * 64 + lk) * g.ldc + col0 + wn * 64 + li;
+  // four load->store round trips after the last MFMA.  The sign lives in the accumulator: no negation of A operands in the
+  // loop.  f64 MFMA C/D layout: col = lane & 15, row = (lane >> 4) + 4 r.
   // wave-uniform tile corner + 32-bit lane offset: the 64 row addresses stay in SGPRs (saddr form), no address VGPRs
   const int wu = __builtin_amdgcn_readfirstlane(wave);
   double* const Ct = g.C + (row0 + (wu >> 1) * 64) * g.ldc + col0 + (wu & 1) * 64;
@@ -197,264 +154,102 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, double (*lds)[
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (CIN && !OW) {
-        if (g.nt_c) {
+      if (FULL && !OW) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][r] = SGN * __builtin_nontemporal_load((Ct + (int64_t)(i * 16 + 4 * r) * g.ldc) + coff + j * 16);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][r] = SGN * (Ct + (int64_t)(i * 16 + 4 * r) * g.ldc)[coff + j * 16];
-        }
+        for (int r = 0; r < 4; ++r) acc[i][j][r] = -(Ct + (int64_t)(i * 16 + 4 * r) * g.ldc)[coff + j * 16];
       } else {
         acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
       }
     }
 
-  const int64_t nk = (g.K + GBK - 1) / GBK;
-  // (a staggered k start per tile, after Tensile's StaggerU, was tried and cost 1.5 %: profiles/r03_gemm_ntc_stagger_ab.txt;
-  //  its 64-bit wrap-around compare in the loop head is gone with it)
-  auto kofs = [&](int64_t kt) -> int64_t { return kt * GBK; };
+  // (a staggered k start per tile, after Tensile's StaggerU, was tried and cost 1.5 %: profiles/r03_gemm_ntc_stagger_ab.txt)
+  const int nk32 = (int)((g.K + GBK - 1) / GBK);
   d2 ra[4], rb[4];
-  gemm_load_tile<FULL>(g.A, g.lda, row0, g.M, kofs(0), g.K, tid, ra);
-  gemm_load_tile<FULL>(g.B, g.ldb, col0, g.N, kofs(0), g.K, tid, rb);
-  if constexpr (PIPE) {
-    gemm_store_tile16(lds[0][0], tid, ra);
-    gemm_store_tile16(lds[0][1], tid, rb);
-  } else {
-    gemm_store_tile(lds[0][0], tid, ra);
-    gemm_store_tile(lds[0][1], tid, rb);
-  }
+  gemm_load_tile<FULL>(g.A, g.lda, row0, g.M, 0, g.K, tid, ra);
+  gemm_load_tile<FULL>(g.B, g.ldb, col0, g.N, 0, g.K, tid, rb);
+  gemm_store_tile16(lds[0][0], tid, ra);
+  gemm_store_tile16(lds[0][1], tid, rb);
   __syncthreads();
-  if constexpr (TR) tr_t1 = __builtin_amdgcn_s_memtime();
 
-  if constexpr (PIPE) {
-    // ---- 16-byte LDS layout (gemm_store_tile16): per k-tile two batches of 8 ds_read_b128 + 32 MFMAs.  The sign lives in
-    // the accumulator here (acc = -C, acc += A B^T, C = -acc): no negation of A operands in the loop.
-    const int c16 = lane & 15, gq = lane >> 4;
-    // full tiles: saddr-form loads (wave-uniform tile corner + the thread's four constant 32-bit byte offsets)
-    unsigned offA[4], offB[4];
+  // ---- per k-tile two batches of 8 ds_read_b128 + 32 MFMAs
+  const int c16 = lane & 15, gq = lane >> 4;
+  // full tiles: saddr-form loads (wave-uniform tile corner + the thread's four constant 32-bit byte offsets)
+  unsigned offA[4], offB[4];
 #pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-      const int cidx = tid + 256 * s4;
-      offA[s4] = (unsigned)(((int64_t)(cidx >> 3) * g.lda + (cidx & 7) * 2) * 8);
-      offB[s4] = (unsigned)(((int64_t)(cidx >> 3) * g.ldb + (cidx & 7) * 2) * 8);
-    }
-    const double* const Abase = g.A + row0 * g.lda;
-    const double* const Bbase = g.B + col0 * g.ldb;
-    auto load_ab = [&](int64_t kt_, d2 (&ra_)[4], d2 (&rb_)[4]) {
-      if constexpr (FULL) {
-        const int64_t ko = kofs(kt_);
-        gemm_load_tile_g(Abase + ko, offA, ra_);
-        gemm_load_tile_g(Bbase + ko, offB, rb_);
-      } else {
-        gemm_load_tile<FULL>(g.A, g.lda, row0, g.M, kofs(kt_), g.K, tid, ra_);
-        gemm_load_tile<FULL>(g.B, g.ldb, col0, g.N, kofs(kt_), g.K, tid, rb_);
-      }
-    };
-    if constexpr (CKS == 4 || CKS == 5) {
-      // read-ahead form (gemm.lds16 = 2): the operand pairs of the NEXT half are requested while 16 MFMAs of the current
-      // one are still to issue, across the tile boundary (the barrier sits before the tile's last 16 MFMAs)
-      auto read_half = [&](d2 (&a_)[4], d2 (&b_)[4], int buf, int h) {
-        const int kq = 2 * gq + h;
-        const int cx = c16 ^ kq;
-        const d2* Ap = reinterpret_cast<const d2*>(lds[buf][0]) + kq * 128 + wm * 64 + cx;
-        const d2* Bp = reinterpret_cast<const d2*>(lds[buf][1]) + kq * 128 + wn * 64 + cx;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a_[i] = Ap[16 * i];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b_[j] = Bp[16 * j];
-      };
-      auto mfma16 = [&](const d2 (&a_)[4], const d2 (&b_)[4], int t) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(t ? a_[i].y : a_[i].x, t ? b_[j].y : b_[j].x, acc[i][j], 0, 0, 0);
-      };
-      d2 a0[4], b0[4], a1[4], b1[4];
-      read_half(a0, b0, 0, 0);
-      const int nk32 = (int)nk;
-      if constexpr (CKS == 4) {
-        for (int kt = 0; kt < nk32; ++kt) {
-          const int cur = kt & 1;
-          if (kt + 1 < nk32) load_ab(kt + 1, ra, rb);
-          mfma16(a0, b0, 0);
-          read_half(a1, b1, cur, 1);
-          mfma16(a0, b0, 1);
-          mfma16(a1, b1, 0);
-          if (kt + 1 < nk32) {
-            gemm_store_tile16(lds[cur ^ 1][0], tid, ra);
-            gemm_store_tile16(lds[cur ^ 1][1], tid, rb);
-          }
-          __syncthreads();
-          if (kt + 1 < nk32) read_half(a0, b0, cur ^ 1, 0);
-          mfma16(a1, b1, 1);
-        }
-      } else {
-        // CKS = 5 (production): the same schedule with the last k-tile peeled -- no conditionals inside the loop, -0.3 % of the
-        // factorisation (1322 -> 1318 and 1289 -> 1286 ms on two boxes, profiles/r04_gemm_peel_stagger_ab.txt).  The schedule
-        // is pinned by a sched_barrier at EVERY phase boundary: with one missing (between the first MFMA group and the
-        // read-ahead) a later, unrelated edit of this file made the scheduler sink the reads behind two groups and the kernel
-        // lost 3 % (1322 vs 1282 ms on one box) without any change to this loop's source.  Committing the prefetched tile to
-        // LDS 16 MFMAs earlier (so that its ds_writes have drained at the barrier) was measured with it: +0.3 %, not kept.
-        auto step = [&](int kt, auto has_next_t) {
-          constexpr bool HN = decltype(has_next_t)::value;
-          const int cur = kt & 1;
-          // (sched_barrier: without the loop's conditionals the machine scheduler hoists the commit and the barrier to the
-          //  20th MFMA and sinks the read-ahead behind the last one)
-          if constexpr (HN) load_ab(kt + 1, ra, rb);
-          __builtin_amdgcn_sched_barrier(0);
-          mfma16(a0, b0, 0);
-          __builtin_amdgcn_sched_barrier(0);  // (between the groups too: in one region the reads were sunk behind BOTH groups and
-          read_half(a1, b1, cur, 1);          //  the third group waited for them -- +3 % factorisation time on a fast box)
-          __builtin_amdgcn_sched_barrier(0);
-          mfma16(a0, b0, 1);
-          __builtin_amdgcn_sched_barrier(0);
-          mfma16(a1, b1, 0);
-          __builtin_amdgcn_sched_barrier(0);
-          unsigned long long ta_ = 0, tm_ = 0;
-          if constexpr (TR && HN) {
-            ta_ = __builtin_amdgcn_s_memtime();
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            tm_ = __builtin_amdgcn_s_memtime();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          }
-          if constexpr (HN) {
-            gemm_store_tile16(lds[cur ^ 1][0], tid, ra);
-            gemm_store_tile16(lds[cur ^ 1][1], tid, rb);
-          }
-          if constexpr (HN) {
-            __syncthreads();
-            if constexpr (TR) {
-              const unsigned long long tb_ = __builtin_amdgcn_s_memtime();
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-              const unsigned long long dv = tm_ - ta_, db = tb_ - tm_;
-              tr_vm += dv; tr_bar += db;
-              const unsigned long long mv = tr_mx >> 32, mb = tr_mx & 0xffffffffull;
-              tr_mx = ((dv > mv ? dv : mv) << 32) | (db > mb ? db : mb);
-            }
-            read_half(a0, b0, cur ^ 1, 0);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          mfma16(a1, b1, 1);
-          __builtin_amdgcn_sched_barrier(0);
-        };
-        for (int kt = 0; kt + 1 < nk32; ++kt) step(kt, std::true_type{});
-        // persistent caller: the index of the workgroup's NEXT tile is requested here -- the counter's round trip (device
-        // scope: microseconds) passes under the last 64 MFMAs and the stores.  Requested at the top of a tile it sat in
-        // front of the tile's own loads (memory operations of a wavefront return in order: every tile started with the
-        // round trip exposed, 11 k cycles between two tiles of a slot -- no better than a workgroup launch).
-        unsigned nxt_ = 0;
-        if constexpr ((FLAGS & 2) != 0 && FULL) {
-          if (tid == 0) nxt_ = atomicAdd(g.queue, 1u);
-        }
-        step(nk32 - 1, std::false_type{});
-        if constexpr ((FLAGS & 2) != 0 && FULL) {
-          if (tid == 0) {
-            s_next[0] = nxt_;
-            s_next[1] = 1u;  // "fetched"
-          }
-        }
-      }
-    } else
-    for (int64_t kt = 0; kt < nk; ++kt) {
-      const int cur = (int)(kt & 1);
-      if (kt + 1 < nk && !(dbg & 2)) {
-        gemm_load_tile<FULL>(g.A, g.lda, row0, g.M, kofs(kt + 1), g.K, tid, ra);
-        gemm_load_tile<FULL>(g.B, g.ldb, col0, g.N, kofs(kt + 1), g.K, tid, rb);
-      }
-      const d2* Ad = reinterpret_cast<const d2*>(lds[cur][0]);
-      const d2* Bd = reinterpret_cast<const d2*>(lds[cur][1]);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int kq = 2 * gq + h;
-        const int cx = c16 ^ kq;
-        const d2* Ap = Ad + kq * 128 + wm * 64 + cx;
-        const d2* Bp = Bd + kq * 128 + wn * 64 + cx;
-        d2 a[4], bb[4];
-        if (dbg & 4) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) a[i] = bb[i] = (d2){(double)(lane + i + h), (double)(lane - i)};
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) a[i] = Ap[16 * i];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) bb[j] = Bp[16 * j];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].x, bb[j].x, acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i].y, bb[j].y, acc[i][j], 0, 0, 0);
-        if (h == (CKS >= 8 ? 1 : 0) && kt + 1 < nk && !(dbg & 2)) {
-          gemm_store_tile16(lds[cur ^ 1][0], tid, ra);
-          gemm_store_tile16(lds[cur ^ 1][1], tid, rb);
-        }
-      }
-      if (!(dbg & 8)) __syncthreads();
-    }
-  } else {
-    for (int64_t kt = 0; kt < nk; ++kt) {
-      const int cur = (int)(kt & 1);
-      if (kt + 1 < nk && !(dbg & 2)) {
-        gemm_load_tile<FULL>(g.A, g.lda, row0, g.M, kofs(kt + 1), g.K, tid, ra);
-        gemm_load_tile<FULL>(g.B, g.ldb, col0, g.N, kofs(kt + 1), g.K, tid, rb);
-      }
-      const double* As = lds[cur][0] + (wm * 64 + li) * GPITCH + lk;
-      const double* Bs = lds[cur][1] + (wn * 64 + li) * GPITCH + lk;
-  #pragma unroll
-      for (int ks = 0; ks < GBK; ks += 4) {
-        double a[4], bb[4];
-        if (dbg & 4) {
-  #pragma unroll
-          for (int i = 0; i < 4; ++i) a[i] = bb[i] = (double)(lane + i + ks);
-        } else {
-  #pragma unroll
-          for (int i = 0; i < 4; ++i) a[i] = -As[i * 16 * GPITCH + ks];
-  #pragma unroll
-          for (int j = 0; j < 4; ++j) bb[j] = Bs[j * 16 * GPITCH + ks];
-        }
-  #pragma unroll
-        for (int i = 0; i < 4; ++i)
-  #pragma unroll
-          for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], bb[j], acc[i][j], 0, 0, 0);
-        if (ks == CKS && kt + 1 < nk && !(dbg & 2)) {
-          // the next tile's global loads were issued ~32 MFMAs ago: write them to the other LDS
-          // buffer now so that the stores drain under the remaining MFMAs of this tile
-          gemm_store_tile(lds[cur ^ 1][0], tid, ra);
-          gemm_store_tile(lds[cur ^ 1][1], tid, rb);
-        }
-      }
-      if (!(dbg & 8)) __syncthreads();
-    }
+  for (int s4 = 0; s4 < 4; ++s4) {
+    const int cidx = tid + 256 * s4;
+    offA[s4] = (unsigned)(((int64_t)(cidx >> 3) * g.lda + (cidx & 7) * 2) * 8);
+    offB[s4] = (unsigned)(((int64_t)(cidx >> 3) * g.ldb + (cidx & 7) * 2) * 8);
   }
-  if (dbg & 1) {
-    if (acc[0][0][0] == 1.2345e-300) g.C[0] = 0.0;  // keep the accumulators alive
-    return;
-  }
-
-  // ---- epilogue: C -= acc.  f64 MFMA C/D layout: col = lane & 15, row = (lane >> 4) + 4 r.
-  // All loads of a 64x16 column strip are issued before the first use (no serialised round trips).
-  if constexpr (TR) tr_t3 = __builtin_amdgcn_s_memtime();
-  auto trace_out = [&]() {
-    if constexpr (TR) {
-      if (g.trace != nullptr && (threadIdx.x & 63) == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t4 = __builtin_amdgcn_s_memtime();
-        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        unsigned long long* o = g.trace + (trace_slot * 4 + (threadIdx.x >> 6)) * 8;
-        o[0] = tr_t0; o[1] = tr_t1; o[2] = tr_t3; o[3] = t4; o[4] = tr_vm; o[5] = tr_bar; o[6] = tr_mx;
-        o[7] = ((unsigned long long)xcc << 32) | hw;
-      }
+  const double* const Abase = g.A + row0 * g.lda;
+  const double* const Bbase = g.B + col0 * g.ldb;
+  auto load_ab = [&](int64_t kt_, d2 (&ra_)[4], d2 (&rb_)[4]) {
+    if constexpr (FULL) {
+      const int64_t ko = kt_ * GBK;
+      gemm_load_tile_g(Abase + ko, offA, ra_);
+      gemm_load_tile_g(Bbase + ko, offB, rb_);
+    } else {
+      gemm_load_tile<FULL>(g.A, g.lda, row0, g.M, kt_ * GBK, g.K, tid, ra_);
+      gemm_load_tile<FULL>(g.B, g.ldb, col0, g.N, kt_ * GBK, g.K, tid, rb_);
     }
   };
-  if (CIN) {
+  // read-ahead: the operand pairs of the NEXT half are requested while 16 MFMAs of the current one are still to issue, across
+  // the tile boundary (the barrier sits before the tile's last 16 MFMAs)
+  auto read_half = [&](d2 (&a_)[4], d2 (&b_)[4], int buf, int h) {
+    const int kq = 2 * gq + h;
+    const int cx = c16 ^ kq;
+    const d2* Ap = reinterpret_cast<const d2*>(lds[buf][0]) + kq * 128 + wm * 64 + cx;
+    const d2* Bp = reinterpret_cast<const d2*>(lds[buf][1]) + kq * 128 + wn * 64 + cx;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a_[i] = Ap[16 * i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b_[j] = Bp[16 * j];
+  };
+  auto mfma16 = [&](const d2 (&a_)[4], const d2 (&b_)[4], int t) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(t ? a_[i].y : a_[i].x, t ? b_[j].y : b_[j].x, acc[i][j], 0, 0, 0);
+  };
+  d2 a0[4], b0[4], a1[4], b1[4];
+  read_half(a0, b0, 0, 0);
+  // The last k-tile is peeled -- no conditionals inside the loop, -0.3 % of the factorisation (1322 -> 1318 and 1289 -> 1286 ms
+  // on two boxes, profiles/r04_gemm_peel_stagger_ab.txt).  The schedule is pinned by a sched_barrier at EVERY phase boundary:
+  // with one missing (between the first MFMA group and the read-ahead) a later, unrelated edit of this file made the scheduler
+  // sink the reads behind two groups and the kernel lost 3 % (1322 vs 1282 ms on one box) without any change to this loop's
+  // source.  Committing the prefetched tile to LDS 16 MFMAs earlier (so that its ds_writes have drained at the barrier) was
+  // measured with it: +0.3 %, not kept.
+  auto step = [&](int kt, auto has_next_t) {
+    constexpr bool HN = decltype(has_next_t)::value;
+    const int cur = kt & 1;
+    // (sched_barrier: without the loop's conditionals the machine scheduler hoists the commit and the barrier to the
+    //  20th MFMA and sinks the read-ahead behind the last one)
+    if constexpr (HN) load_ab(kt + 1, ra, rb);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma16(a0, b0, 0);
+    __builtin_amdgcn_sched_barrier(0);  // (between the groups too: in one region the reads were sunk behind BOTH groups and
+    read_half(a1, b1, cur, 1);          //  the third group waited for them -- +3 % factorisation time on a fast box)
+    __builtin_amdgcn_sched_barrier(0);
+    mfma16(a0, b0, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma16(a1, b1, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (HN) {
+      gemm_store_tile16(lds[cur ^ 1][0], tid, ra);
+      gemm_store_tile16(lds[cur ^ 1][1], tid, rb);
+      __syncthreads();
+      read_half(a0, b0, cur ^ 1, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    mfma16(a1, b1, 1);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  for (int kt = 0; kt + 1 < nk32; ++kt) step(kt, std::true_type{});
+  step(nk32 - 1, std::false_type{});
+
+  // ---- epilogue.  f64 MFMA C/D layout: col = lane & 15, row = (lane >> 4) + 4 r.
+  if (FULL) {
     // recompute the store addresses from laundered copies: the compiler otherwise keeps the prologue's 32 load addresses
     // alive across the main loop (spilled to scratch)
     double* Ct2g = Ct;
@@ -462,22 +257,12 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, double (*lds)[
     asm volatile("" : "+v"(Ct2g), "+v"(coff2));
     // (the laundered pointer is generic: back to the global address space, or the 64 stores are FLAT stores)
     __attribute__((address_space(1))) double* Ct2 = (__attribute__((address_space(1))) double*)Ct2g;
-    if (g.nt_c) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) __builtin_nontemporal_store(SGN * acc[i][j][r], (Ct2 + (int64_t)(i * 16 + 4 * r) * g.ldc) + coff2 + j * 16);
-      return;
-    }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) (Ct2 + (int64_t)(i * 16 + 4 * r) * g.ldc)[coff2 + j * 16] = SGN * acc[i][j][r];
-    trace_out();
+        for (int r = 0; r < 4; ++r) (Ct2 + (int64_t)(i * 16 + 4 * r) * g.ldc)[coff2 + j * 16] = -acc[i][j][r];
     return;
   }
   if constexpr (OW) {  // edge tile of an overwriting product: guarded stores, nothing read
@@ -489,51 +274,38 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, double (*lds)[
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int64_t gr = row0 + wm * 64 + i * 16 + lk + 4 * r;
-          if (gc < g.N && gr < g.M) g.C[gr * g.ldc + gc] = SGN * acc[i][j][r];
+          if (gc < g.N && gr < g.M) g.C[gr * g.ldc + gc] = -acc[i][j][r];
         }
     }
     return;
   }
+  // edge tile: the accumulator holds A B^T; all loads of a 64x16 column strip are issued before the first use
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     double cv[4][4];
-    if (FULL) {
+    const int64_t gc = col0 + wn * 64 + j * 16 + li;
+    const bool cok = gc < g.N;
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) cv[i][r] = Cw[(i * 16 + 4 * r) * g.ldc + j * 16];
+      for (int r = 0; r < 4; ++r) {
+        const int64_t gr = row0 + wm * 64 + i * 16 + lk + 4 * r;
+        const int64_t cr = gr < g.M ? gr : g.M - 1, cc = cok ? gc : g.N - 1;
+        cv[i][r] = g.C[cr * g.ldc + cc];
+      }
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) Cw[(i * 16 + 4 * r) * g.ldc + j * 16] = cv[i][r] + SGN * acc[i][j][r];
-    } else {
-      const int64_t gc = col0 + wn * 64 + j * 16 + li;
-      const bool cok = gc < g.N;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t gr = row0 + wm * 64 + i * 16 + lk + 4 * r;
-          const bool ok = cok && gr < g.M;
-          const int64_t cr = gr < g.M ? gr : g.M - 1, cc = cok ? gc : g.N - 1;
-          cv[i][r] = g.C[cr * g.ldc + cc];
-          (void)ok;
-        }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t gr = row0 + wm * 64 + i * 16 + lk + 4 * r;
-          if (cok && gr < g.M) g.C[gr * g.ldc + gc] = cv[i][r] + SGN * acc[i][j][r];
-        }
-    }
+      for (int r = 0; r < 4; ++r) {
+        const int64_t gr = row0 + wm * 64 + i * 16 + lk + 4 * r;
+        if (cok && gr < g.M) g.C[gr * g.ldc + gc] = cv[i][r] - acc[i][j][r];
+      }
   }
 }
 
 // block index -> tile (XCD-aware 8x8 super tiles: block b runs on XCD b % 8) and the tile's GEMM
-template <bool ABL, bool PIPE = false, bool CACC = true, int CKS = GEMM_COMMIT_KS, int FLAGS = 0>
-__device__ __forceinline__ void gemm_block(const GemmArgs& g, double (*lds)[2][GT * GPITCH], int64_t b, unsigned* s_next = nullptr) {
-  const int64_t b_launch = b;
+template <bool OW>
+__device__ __forceinline__ void gemm_block(const GemmArgs& g, double (*lds)[2][GT * GPITCH], int64_t b) {
   if (b < g.tiles2) {  // second problem (workgroup-uniform branch)
     const int tn2 = (int)((g.N2 + GT - 1) / GT);
     const int64_t ti = b / tn2, tj = b - ti * tn2;
@@ -544,9 +316,9 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& g, double (*lds)[2][G
     const int64_t row0 = ti * GT, col0 = tj * GT;
     const bool full = (row0 + GT <= h.M) && (col0 + GT <= h.N) && ((h.K & (GBK - 1)) == 0) && h.aligned;
     if (full)
-      gemm_tile_body<true, ABL, PIPE, CACC, CKS, (FLAGS & 2)>(h, lds, row0, col0, 0, s_next);
+      gemm_tile_body<true, false>(h, lds, row0, col0);
     else
-      gemm_tile_body<false, ABL, PIPE, CACC, CKS, (FLAGS & 2)>(h, lds, row0, col0);
+      gemm_tile_body<false, false>(h, lds, row0, col0);
     if (g.ready && ti < g.ready_rows && tj < g.ready_rows) {
       __threadfence();
       __syncthreads();
@@ -590,9 +362,9 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& g, double (*lds)[2][G
   }
   const bool full = (row0 + GT <= g.M) && (col0 + GT <= g.N) && ((g.K & (GBK - 1)) == 0) && g.aligned;
   if (full)
-    gemm_tile_body<true, ABL, PIPE, CACC, CKS, FLAGS>(g, lds, row0, col0, b_launch, s_next);
+    gemm_tile_body<true, OW>(g, lds, row0, col0);
   else
-    gemm_tile_body<false, ABL, PIPE, CACC, CKS, (FLAGS & 6)>(g, lds, row0, col0);
+    gemm_tile_body<false, OW>(g, lds, row0, col0);
   if (g.ready && g.tiles2 == 0 && ti < g.ready_rows && tj < g.ready_rows) {  // publish the tile (release: every thread's stores, then one count)
     __threadfence();
     __syncthreads();
@@ -600,12 +372,9 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& g, double (*lds)[2][G
   }
 }
 
-template <bool ABL>
 __global__ void __launch_bounds__(256, 2) gemm_nt_sub_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) double lds[2][2][GT * GPITCH];
-  // production instantiation: the 16-byte LDS layout with read-ahead of the fused kernel (gemm.lds16 = 3); the ablation
-  // instantiation keeps the 8-byte layout its masks were written for
-  gemm_block<ABL, !ABL, true, ABL ? GEMM_COMMIT_KS : 5>(g, lds, blockIdx.x);
+  gemm_block<false>(g, lds, blockIdx.x);
 }
 
 
@@ -613,7 +382,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_sub_kernel(GemmArgs g) {
 // is a fresh work buffer (the prediction contractions cleared 1.8 GB per mat-vec at configs[3] only to have it read back)
 __global__ void __launch_bounds__(256, 2) gemm_nt_neg_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) double lds[2][2][GT * GPITCH];
-  gemm_block<false, true, true, 5, 4>(g, lds, blockIdx.x);
+  gemm_block<true>(g, lds, blockIdx.x);
 }
 
 // f0, f1: the launch covers the super tiles [f0 * n_super, f1 * n_super) (whole update: 0, 1);
@@ -633,13 +402,10 @@ struct DiagJob {
   int64_t M2 = 0, N2 = 0, K2 = 0;
 };
 
-static bool gemm_use_n64(gdml_ctx* ctx) { return ctx_opt_i(ctx, "gemm.n64", 0) != 0; }
-
 static int launch_gemm_nt_sub_part(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda,
                                    const double* B, int64_t ldb, double* C, int64_t ldc, int64_t M,
                                    int64_t N, int64_t K, int lower, double f0, double f1, bool timed,
-                                   const DiagJob* diag = nullptr, const CyclicLower* cyc = nullptr, int tile_n64 = -1,
-                                   bool overwrite = false) {
+                                   const DiagJob* diag = nullptr, const CyclicLower* cyc = nullptr, bool overwrite = false) {
   if (M <= 0 || N <= 0 || K <= 0) return GDML_OK;
   GemmArgs g;
   g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
@@ -649,18 +415,12 @@ static int launch_gemm_nt_sub_part(gdml_ctx* ctx, hipStream_t st, const double* 
   g.col0_first = (diag && diag->col0_first) ? 1 : 0;
   g.ready = nullptr; g.ready_target = 0; g.ready_rows = 0;
   g.A2 = g.B2 = nullptr; g.C2 = nullptr; g.M2 = g.N2 = g.K2 = 0; g.tiles2 = 0;
-  g.trace = nullptr; g.queue = nullptr; g.n_items = 0;
   if (cyc) { g.cyc_W = cyc->W; g.cyc_rank = cyc->rank; g.cyc_lb0 = cyc->lb0; g.cyc_nb = cyc->nb; g.cyc_col0 = cyc->col0; g.cyc_block_rows = cyc->block_rows; }
-  g.dbg = ctx_opt_i(ctx, "gemm.debug", 0);
-  g.nt_c = ctx_opt_i(ctx, "gemm.nt_c", 0);
   g.aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 &&
               (lda % 2 == 0) && (ldb % 2 == 0);
-  // gemm.n64: 128 x 64 tiles, three workgroups per CU (gemm_nt_sub_n64_kernel); super tiles stay 1024 x 1024
-  const bool n64 = (tile_n64 >= 0 ? tile_n64 != 0 : gemm_use_n64(ctx)) && !cyc && g.dbg == 0 && !overwrite;
-  const int TN = n64 ? G6N : GT, super_cols = n64 ? 16 : 8;
   g.tiles_m = (int)((M + GT - 1) / GT);
-  g.tiles_n = (int)((N + TN - 1) / TN);
-  int64_t sm = (g.tiles_m + 7) / 8, sn = (g.tiles_n + super_cols - 1) / super_cols;
+  g.tiles_n = (int)((N + GT - 1) / GT);
+  int64_t sm = (g.tiles_m + 7) / 8, sn = (g.tiles_n + 7) / 8;
   g.super_n = (int)sn;
   const int64_t n_super_all = lower ? sm * (sm + 1) / 2 : sm * sn;
   g.s_begin = (int64_t)(f0 * (double)n_super_all);
@@ -671,73 +431,20 @@ static int launch_gemm_nt_sub_part(gdml_ctx* ctx, hipStream_t st, const double* 
     g.n_super = g.s_begin;  // empty tile range: the launch still carries the diagonal-block workgroup
   }
   int64_t groups = (g.n_super - g.s_begin + 7) / 8;  // each group of 8 super tiles = 8 XCDs x 64 blocks
-  int64_t blocks = groups * (n64 ? 1024 : 512);
+  int64_t blocks = groups * 512;
   const int slot = (timed && st == (ctx->kt_stream ? ctx->kt_stream : ctx->stream)) ? ktime_begin(ctx) : -1;
   if (has_diag) {
     g.diagA = diag->A; g.diag_nbw = diag->nbw; g.diag_off = diag->off; g.diag_info = ctx->d_info;
     if (diag->ready) { g.ready = diag->ready; g.ready_target = diag->ready_target; g.ready_rows = diag->nbw * 64 / GT; }
     if (diag->A2 && diag->M2 > 0) {
       g.A2 = diag->A2; g.B2 = diag->B2; g.C2 = diag->C2; g.M2 = diag->M2; g.N2 = diag->N2; g.K2 = diag->K2;
-      g.tiles2 = (int)(ceil_div(g.M2, GT) * ceil_div(g.N2, TN));
+      g.tiles2 = (int)(ceil_div(g.M2, GT) * ceil_div(g.N2, GT));
     }
-    const dim3 grid((unsigned)(blocks + 1 + g.tiles2));
-    if (n64) hipLaunchKernelGGL(gemm_nt_sub_n64_kernel, grid, dim3(256), 0, st, g);
-    else {
-    // gemm.trace = k > 0: the k-th fused launch since the option was set runs the traced instantiation and leaves
-    // gemm_trace.bin (header: blocks, tiles2, tiles_m, s_begin, n_super, col0_first; then 4 x 8 words per workgroup)
-    const int trace_k = ctx_opt_i(ctx, "gemm.trace", 0);
-    if (trace_k > 0 && ++ctx->gemm_trace_seen == trace_k) {
-      const size_t words = (size_t)(blocks + g.tiles2) * 32;
-      unsigned long long* d_tr = nullptr;
-      GDML_TRY(ctx_alloc(ctx, (void**)&d_tr, (int64_t)(words * 8)));
-      HIP_CHECK(ctx, hipMemsetAsync(d_tr, 0, words * 8, st));
-      g.trace = d_tr;
-      const int64_t resident_t = 2 * (int64_t)ctx->num_cus;
-      if (ctx_opt_i(ctx, "gemm.persist", 0) != 0 && blocks + g.tiles2 >= 4 * resident_t && ctx->gemm_queue != nullptr) {
-        if (ctx->gemm_queue_next >= ctx->gemm_queue_sets) {
-          HIP_CHECK(ctx, hipMemsetAsync(ctx->gemm_queue, 0, (size_t)ctx->gemm_queue_sets * 512, st));
-          ctx->gemm_queue_next = 0;
-        }
-        g.queue = ctx->gemm_queue + (size_t)(ctx->gemm_queue_next++) * 128;
-        g.n_items = blocks + g.tiles2;
-        hipLaunchKernelGGL((gemm_nt_sub_persist_kernel<5, 3>), dim3((unsigned)resident_t), dim3(256), 0, st, g);
-      } else
-      hipLaunchKernelGGL(gemm_nt_sub_diag_trace_kernel, grid, dim3(256), 0, st, g);
-      std::vector<unsigned long long> h(words + 8);
-      HIP_CHECK(ctx, hipMemcpyAsync(h.data() + 8, d_tr, words * 8, hipMemcpyDeviceToHost, st));
-      HIP_CHECK(ctx, hipStreamSynchronize(st));
-      h[0] = (unsigned long long)blocks; h[1] = (unsigned long long)g.tiles2; h[2] = (unsigned long long)g.tiles_m;
-      h[3] = (unsigned long long)g.s_begin; h[4] = (unsigned long long)g.n_super; h[5] = (unsigned long long)g.col0_first;
-      h[6] = (unsigned long long)K; h[7] = (unsigned long long)M;
-      if (FILE* f = fopen("gemm_trace.bin", "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-      GDML_TRY(ctx_free(ctx, d_tr));
-      ktime_end(ctx, slot, "gemm_nt_sub_diag_traced", 0.0);
-      ctx->launch_counter++;
-      return GDML_OK;
-    }
-    // gemm.persist (default 0: measured 1.5 % slower, profiles/r06_gemm_variants.txt): resident workgroups pulling tiles from per-XCD counters, for launches of at least four rounds
-    const int64_t resident = 2 * (int64_t)ctx->num_cus;
-    if (ctx_opt_i(ctx, "gemm.persist", 0) != 0 && blocks + g.tiles2 >= 4 * resident && ctx->gemm_queue != nullptr) {
-      if (ctx->gemm_queue_next >= ctx->gemm_queue_sets) {  // (chol_factor_device zeroes the ring; a caller that does not gets a fresh one here)
-        HIP_CHECK(ctx, hipMemsetAsync(ctx->gemm_queue, 0, (size_t)ctx->gemm_queue_sets * 512, st));
-        ctx->gemm_queue_next = 0;
-      }
-      g.queue = ctx->gemm_queue + (size_t)(ctx->gemm_queue_next++) * 128;
-      g.n_items = blocks + g.tiles2;
-      hipLaunchKernelGGL((gemm_nt_sub_persist_kernel<5>), dim3((unsigned)resident), dim3(256), 0, st, g);
-    } else
-    // gemm.lds16 = 2: the loop with its last k-tile inside (A/B reference of the peeled production loop)
-    if (ctx_opt_i(ctx, "gemm.lds16", 3) == 2) hipLaunchKernelGGL((gemm_nt_sub_diag_kernel<true, true, 4>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((gemm_nt_sub_diag_kernel<true, true, 5>), grid, dim3(256), 0, st, g);
-    }
+    hipLaunchKernelGGL(gemm_nt_sub_diag_kernel, dim3((unsigned)(blocks + 1 + g.tiles2)), dim3(256), 0, st, g);
   } else if (overwrite)
     hipLaunchKernelGGL(gemm_nt_neg_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g);
-  else if (n64)
-    hipLaunchKernelGGL(gemm_nt_sub_n64_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g);
-  else if (g.dbg)
-    hipLaunchKernelGGL(gemm_nt_sub_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, g);
   else
-    hipLaunchKernelGGL(gemm_nt_sub_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, g);
+    hipLaunchKernelGGL(gemm_nt_sub_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g);
   const double part = (double)(g.n_super - g.s_begin) / (double)n_super_all;  // share of the tile list in this launch
   // the fused launches (trailing update + diagonal-block workgroup) are the dominant kernel: timed under their own name
   ktime_end(ctx, slot, has_diag ? "gemm_nt_sub_diag" : "gemm_nt_sub",
@@ -754,25 +461,9 @@ int launch_gemm_nt_sub(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t l
   return launch_gemm_nt_sub_part(ctx, st, A, lda, B, ldb, C, ldc, M, N, K, lower, 0.0, 1.0, true);
 }
 
-// Plain product whose tile shape is chosen by how well the tile count fills the chip: 128 x 128 tiles run two workgroups per CU
-// (512 slots), 128 x 64 tiles three (768 slots) at 0.93 of the wide tile's rate inside the k loop (profiles/r06_gemm_n64_ab.txt).
-// A launch of 1128 wide tiles (the configs[4] mat-vec: 6016 x 3072) is 2.2 rounds of 512 -- 0.73 full; as 2256 narrow tiles it
-// is 2.94 rounds of 768 -- 0.98 full.  Only for callers that ask (the prediction contractions), and OFF by default (option
-// gemm.fill_tiles): measured on exactly that launch the narrow tiles lose -- mat-vec 9.37 ms against 8.43 ms with wide tiles
-// (profiles/r06_matvec_probe.txt): the wide launch's third round is short, not a full round long.
 int launch_gemm_nt_neg(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb,
                        double* C, int64_t ldc, int64_t M, int64_t N, int64_t K) {  // C = -A B^T, C not read
-  return launch_gemm_nt_sub_part(ctx, st, A, lda, B, ldb, C, ldc, M, N, K, 0, 0.0, 1.0, true, nullptr, nullptr, 0, true);
-}
-
-int launch_gemm_nt_sub_fill(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb,
-                            double* C, int64_t ldc, int64_t M, int64_t N, int64_t K) {
-  const int64_t slots = 2 * (int64_t)ctx->num_cus;
-  const int64_t t_w = (int64_t)ceil_div(M, GT) * ceil_div(N, GT), t_n = (int64_t)ceil_div(M, GT) * ceil_div(N, G6N);
-  const double fill_w = (double)t_w / (double)((int64_t)ceil_div(t_w, slots) * slots);
-  const double fill_n = 0.93 * (double)t_n / (double)((int64_t)ceil_div(t_n, slots * 3 / 2) * (slots * 3 / 2));
-  const int pick = ctx_opt_i(ctx, "gemm.fill_tiles", 0) != 0 && fill_n > fill_w ? 1 : 0;
-  return launch_gemm_nt_sub_part(ctx, st, A, lda, B, ldb, C, ldc, M, N, K, 0, 0.0, 1.0, true, nullptr, nullptr, pick);
+  return launch_gemm_nt_sub_part(ctx, st, A, lda, B, ldb, C, ldc, M, N, K, 0, 0.0, 1.0, true, nullptr, nullptr, true);
 }
 
 int launch_gemm_nt_sub_cyclic(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb,
@@ -887,12 +578,12 @@ __device__ __forceinline__ double quad_bcast(double v, int q) {
 // of an LDS permute round trip), the L values of column c + 1 are fetched from LDS while column c is applied, and the
 // column steps are expanded at compile time (a 64-trip loop of this size is only partially unrolled even under
 // #pragma unroll, which turns t[c >> 3] into a dynamically indexed register array).
-template <int LP, bool TRL = false>
+template <int LP>
 __device__ __forceinline__ void subst64_row8(double (&t)[8], const double* __restrict__ Lt, const double* __restrict__ rinv,
                                              int sq) {
   double ln[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) ln[i] = TRL ? Lt[(sq + 8 * i) * LP] : Lt[sq + 8 * i];
+  for (int i = 0; i < 8; ++i) ln[i] = Lt[sq + 8 * i];
   double rn = rinv[0];
   auto column = [&](auto cc) __attribute__((always_inline)) {
     constexpr int c = decltype(cc)::value;
@@ -905,7 +596,7 @@ __device__ __forceinline__ void subst64_row8(double (&t)[8], const double* __res
       rn = rinv[c + 1];
 #pragma unroll
       for (int i = 0; i < 8; ++i)
-        if (i >= ((c + 1) >> 3)) ln[i] = TRL ? Lt[(sq + 8 * i) * LP + (c + 1)] : Lt[(c + 1) * LP + sq + 8 * i];
+        if (i >= ((c + 1) >> 3)) ln[i] = Lt[(c + 1) * LP + sq + 8 * i];
     }
     const double xq = quad_bcast(t[ic] * rc, qc & 3);                      // lane (qc & 3) of the own quad
     const double xo = (qc < 4) ? dpp_mov<0x114>(xq) : dpp_mov<0x104>(xq);  // the other quad's: row_shr:4 / row_shl:4
@@ -968,16 +659,12 @@ __device__ __forceinline__ int potrf64_wg(double* T, double* colbuf /* 2 x 64 */
   return fail;
 }
 
-// SMALL: no transposed copy of L_jj (the substitution reads the factored block in T column-wise: pitch 65 is conflict free both
-// ways) -- 35 KB of LDS instead of 68, for the 128 x 64-tile kernel that runs three workgroups per CU on 48 KB each
-template <bool SMALL = false>
 __device__ __forceinline__ void diag_block_role(double* __restrict__ D, int64_t ld, int nbw, int64_t global_off,
                                              int* __restrict__ info, double* lds) {
-  double* T = lds;                   // 64 x 65 (potrf); afterwards reused as S: 32 x 66 row block of the substitution
+  double* T = lds;                   // 64 x 65 (potrf)
   double* Lt = lds + 64 * 65;        // L_jj^T, pitch 65
-  double* rinv = SMALL ? lds + 64 * 65 : Lt + 64 * 65;  // 64
+  double* rinv = Lt + 64 * 65;       // 64
   double* col = rinv + 64;           // 2 x 64
-  double* S = T;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lk = lane >> 4;
   const int srow = tid >> 3, sq = tid & 7;
@@ -995,7 +682,7 @@ __device__ __forceinline__ void diag_block_role(double* __restrict__ D, int64_t 
     for (int e = tid; e < 64 * 64; e += 256) {
       const int r = e >> 6, c = e & 63;
       const double v = (c <= r) ? T[r * 65 + c] : 0.0;
-      if constexpr (!SMALL) Lt[c * 65 + r] = v;
+      Lt[c * 65 + r] = v;
       if (c <= r) Ad[(int64_t)r * ld + c] = v;
       if (c == r) rinv[r] = 1.0 / v;
     }
@@ -1008,8 +695,7 @@ __device__ __forceinline__ void diag_block_role(double* __restrict__ D, int64_t 
       double t[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) t[i] = xr[sq + 8 * i];
-      if constexpr (SMALL) subst64_row8<65, true>(t, T, rinv, sq);
-      else subst64_row8<65>(t, Lt, rinv, sq);
+      subst64_row8<65>(t, Lt, rinv, sq);
 #pragma unroll
       for (int i = 0; i < 8; ++i) xr[sq + 8 * i] = t[i];
     }
@@ -1060,11 +746,10 @@ __device__ __forceinline__ void diag_block_role(double* __restrict__ D, int64_t 
     }
     __syncthreads();
   }
-  (void)S;
 }
 
+
 // Trailing update + (workgroup 0) the next panel's diagonal block.
-template <bool PIPE, bool CACC, int CKS>
 __global__ void __launch_bounds__(256, 2) gemm_nt_sub_diag_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) double lds[2][2][GT * GPITCH];
   static_assert(sizeof(double) * 2 * 2 * GT * GPITCH >= sizeof(double) * (2 * 64 * 65 + 64 + 128), "LDS of the diagonal role");
@@ -1086,333 +771,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_sub_diag_kernel(GemmArgs g) {
     diag_block_role(g.diagA, g.ldc, g.diag_nbw, g.diag_off, g.diag_info, &lds[0][0][0]);
     return;
   }
-  gemm_block<false, PIPE, CACC, CKS>(g, lds, (int64_t)blockIdx.x - 1);
-}
-
-// ------------------------------------------------------------------------------------------
-// 128 x 64 tiles, THREE workgroups per CU (round 6, option gemm.n64).  The traced 128 x 128 kernel loses its time in the state
-// "one of the CU's two workgroups is between tiles, the other runs alone at 0.76 of the pipe" (14 % of the time,
-// profiles/r06_gemm_trace.txt); with three narrower workgroups (64 accumulator registers per lane instead of 128: 168 VGPRs,
-// 48 KB of LDS each) two of them are still in their k loops while the third turns over.  Price: 1.5 x the operand traffic
-// per flop from L2 and a barrier every 32 MFMAs instead of 64.  Same loop as the production kernel's (16-byte LDS layout,
-// operand pairs of the next half k-tile read ahead, last k-tile peeled, schedule pinned by sched_barriers); wave (wm, wn)
-// owns 64 rows x 32 columns = 4 x 2 MFMA tiles.
-// ------------------------------------------------------------------------------------------
-#define G6_STAGE ((GT + G6N) * GBK)  // doubles per LDS stage: A tile (128 x 16), then B tile (64 x 16)
-
-template <bool FULL>
-__device__ __forceinline__ void gemm_tile_body_n64(const GemmArgs& g, double* __restrict__ lds, int64_t row0, int64_t col0) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int c16 = lane & 15, gq = lane >> 4;
-  const int wu = __builtin_amdgcn_readfirstlane(wave);
-  double* const Ct = g.C + (row0 + (wu >> 1) * 64) * g.ldc + col0 + (wu & 1) * 32;
-  const unsigned coff = (unsigned)gq * (unsigned)g.ldc + (unsigned)c16;
-  d4 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if constexpr (FULL) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[i][j][r] = -(Ct + (int64_t)(i * 16 + 4 * r) * g.ldc)[coff + j * 16];
-      } else {
-        acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
-      }
-    }
-  const int nk32 = (int)((g.K + GBK - 1) / GBK);
-  unsigned offA[4], offB[2];
-#pragma unroll
-  for (int s4 = 0; s4 < 4; ++s4) {
-    const int cidx = tid + 256 * s4;
-    offA[s4] = (unsigned)(((int64_t)(cidx >> 3) * g.lda + (cidx & 7) * 2) * 8);
-    if (s4 < 2) offB[s4] = (unsigned)(((int64_t)(cidx >> 3) * g.ldb + (cidx & 7) * 2) * 8);
-  }
-  const double* const Abase = g.A + row0 * g.lda;
-  const double* const Bbase = g.B + col0 * g.ldb;
-  d2 ra[4], rb[2];
-  auto load_ab = [&](int kt_) {
-    const int64_t ko = (int64_t)kt_ * GBK;
-    if constexpr (FULL) {
-      typedef const __attribute__((address_space(1))) char* gcptr;
-      typedef const __attribute__((address_space(1))) d2* gd2ptr;
-      const uint64_t pa = reinterpret_cast<uint64_t>(Abase + ko), pb = reinterpret_cast<uint64_t>(Bbase + ko);
-      const uint32_t alo = __builtin_amdgcn_readfirstlane((uint32_t)pa), ahi = __builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32));
-      const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)pb), bhi = __builtin_amdgcn_readfirstlane((uint32_t)(pb >> 32));
-      gcptr ba = (gcptr)(((uint64_t)ahi << 32) | alo);
-      gcptr bb = (gcptr)(((uint64_t)bhi << 32) | blo);
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) ra[s4] = *(gd2ptr)(ba + offA[s4]);
-#pragma unroll
-      for (int s4 = 0; s4 < 2; ++s4) rb[s4] = *(gd2ptr)(bb + offB[s4]);
-    } else {
-      // branch-free guarded loads: clamp the address, then zero what is out of range
-      auto guarded = [&](const double* __restrict__ G, int64_t ld, int64_t r0, int64_t nrows, int cidx) -> d2 {
-        const int64_t gr = r0 + (cidx >> 3), gk = ko + (cidx & 7) * 2;
-        const int64_t cr = gr < nrows ? gr : nrows - 1;
-        const int64_t ck0 = gk < g.K ? gk : g.K - 1, ck1 = gk + 1 < g.K ? gk + 1 : g.K - 1;
-        const double v0 = G[cr * ld + ck0], v1 = G[cr * ld + ck1];
-        d2 v;
-        v.x = (gr < nrows && gk < g.K) ? v0 : 0.0;
-        v.y = (gr < nrows && gk + 1 < g.K) ? v1 : 0.0;
-        return v;
-      };
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) ra[s4] = guarded(g.A, g.lda, row0, g.M, tid + 256 * s4);
-#pragma unroll
-      for (int s4 = 0; s4 < 2; ++s4) rb[s4] = guarded(g.B, g.ldb, col0, g.N, tid + 256 * s4);
-    }
-  };
-  // element (row, kq = k / 2) of a tile = the pair (k, k + 1) at d2 index kq * rows + (row ^ kq)  (gemm_store_tile16's layout)
-  auto commit = [&](int buf) {
-    d2* SA = reinterpret_cast<d2*>(lds + buf * G6_STAGE);
-    d2* SB = SA + GT * GBK / 2;
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) {
-      const int cidx = tid + 256 * s4;
-      const int row = cidx >> 3, kq = cidx & 7;
-      SA[kq * GT + (row ^ kq)] = ra[s4];
-      if (s4 < 2) SB[kq * G6N + (row ^ kq)] = rb[s4];
-    }
-  };
-  auto read_half = [&](d2 (&a_)[4], d2 (&b_)[2], int buf, int h) {
-    const int kq = 2 * gq + h;
-    const int cx = c16 ^ kq;
-    const d2* Ap = reinterpret_cast<const d2*>(lds + buf * G6_STAGE) + kq * GT + wm * 64 + cx;
-    const d2* Bp = reinterpret_cast<const d2*>(lds + buf * G6_STAGE) + GT * GBK / 2 + kq * G6N + wn * 32 + cx;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a_[i] = Ap[16 * i];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) b_[j] = Bp[16 * j];
-  };
-  auto mfma8 = [&](const d2 (&a_)[4], const d2 (&b_)[2], int t) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(t ? a_[i].y : a_[i].x, t ? b_[j].y : b_[j].x, acc[i][j], 0, 0, 0);
-  };
-  load_ab(0);
-  commit(0);
-  __syncthreads();
-  d2 a0[4], b0[2], a1[4], b1[2];
-  read_half(a0, b0, 0, 0);
-  auto step = [&](int kt, auto has_next_t) {
-    constexpr bool HN = decltype(has_next_t)::value;
-    const int cur = kt & 1;
-    if constexpr (HN) load_ab(kt + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma8(a0, b0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    read_half(a1, b1, cur, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma8(a0, b0, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma8(a1, b1, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (HN) {
-      commit(cur ^ 1);
-      __syncthreads();
-      read_half(a0, b0, cur ^ 1, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    mfma8(a1, b1, 1);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  for (int kt = 0; kt + 1 < nk32; ++kt) step(kt, std::true_type{});
-  step(nk32 - 1, std::false_type{});
-
-  // ---- epilogue: the accumulator holds -C + A B^T (full tiles) or A B^T (edge tiles)
-  if constexpr (FULL) {
-    double* Ct2g = Ct;
-    unsigned coff2 = coff;
-    asm volatile("" : "+v"(Ct2g), "+v"(coff2));
-    __attribute__((address_space(1))) double* Ct2 = (__attribute__((address_space(1))) double*)Ct2g;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) (Ct2 + (int64_t)(i * 16 + 4 * r) * g.ldc)[coff2 + j * 16] = -acc[i][j][r];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int64_t gc = col0 + wn * 32 + j * 16 + c16;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t gr = row0 + wm * 64 + i * 16 + gq + 4 * r;
-          if (gc < g.N && gr < g.M) g.C[gr * g.ldc + gc] -= acc[i][j][r];
-        }
-    }
-  }
-}
-
-// block index -> tile: super tiles of 8 x 16 tiles (1024 x 1024 elements, 128 workgroups; block b runs on XCD b % 8)
-__device__ __forceinline__ void gemm_block_n64(const GemmArgs& g, double* __restrict__ lds, int64_t b) {
-  if (b < g.tiles2) {  // second problem
-    const int tn2 = (int)((g.N2 + G6N - 1) / G6N);
-    const int64_t ti = b / tn2, tj = b - ti * tn2;
-    if (ti * GT < g.N2 && tj * G6N > ti * GT + GT - 1) return;  // above the diagonal of its leading N2 x N2 block
-    GemmArgs h = g;
-    h.A = g.A2; h.B = g.B2; h.C = g.C2; h.M = g.M2; h.N = g.N2; h.K = g.K2;
-    h.aligned = ((reinterpret_cast<uintptr_t>(g.A2) | reinterpret_cast<uintptr_t>(g.B2)) & 15) == 0 && g.aligned;
-    const int64_t row0 = ti * GT, col0 = tj * G6N;
-    const bool full = (row0 + GT <= h.M) && (col0 + G6N <= h.N) && ((h.K & (GBK - 1)) == 0) && h.aligned;
-    if (full) gemm_tile_body_n64<true>(h, lds, row0, col0);
-    else gemm_tile_body_n64<false>(h, lds, row0, col0);
-    if (g.ready && ti < g.ready_rows && col0 < (int64_t)g.ready_rows * GT) {
-      __threadfence();
-      __syncthreads();
-      if (threadIdx.x == 0) atomicAdd(g.ready, 1);
-    }
-    return;
-  }
-  b -= g.tiles2;
-  const int64_t xcd = b & 7, loc = b >> 3;
-  const int64_t s = g.s_begin + (loc >> 7) * 8 + xcd;
-  const int within = (int)(loc & 127);
-  if (s >= g.n_super) return;
-  int64_t SI, SJ;
-  if (g.lower) {
-    int64_t sr = s, shift = 0;
-    const int64_t sm = (g.tiles_m + 7) / 8;
-    if (g.col0_first) {
-      if (s < sm) { SI = s; SJ = 0; sr = -1; }
-      else { sr = s - sm; shift = 1; }
-    }
-    if (sr >= 0) {
-      SI = (int64_t)((sqrt(8.0 * (double)sr + 1.0) - 1.0) * 0.5);
-      while (SI * (SI + 1) / 2 > sr) --SI;
-      while ((SI + 1) * (SI + 2) / 2 <= sr) ++SI;
-      SJ = sr - SI * (SI + 1) / 2;
-      SI += shift; SJ += shift;
-    }
-  } else {
-    SI = s / g.super_n;
-    SJ = s - SI * g.super_n;
-  }
-  const int64_t ti = SI * 8 + (within >> 4), tj = SJ * 16 + (within & 15);
-  if (ti >= g.tiles_m || tj >= g.tiles_n) return;
-  const int64_t row0 = ti * GT, col0 = tj * G6N;
-  if (g.lower && col0 > row0 + GT - 1) return;
-  const bool full = (row0 + GT <= g.M) && (col0 + G6N <= g.N) && ((g.K & (GBK - 1)) == 0) && g.aligned;
-  if (full) gemm_tile_body_n64<true>(g, lds, row0, col0);
-  else gemm_tile_body_n64<false>(g, lds, row0, col0);
-  if (g.ready && g.tiles2 == 0 && ti < g.ready_rows && col0 < (int64_t)g.ready_rows * GT) {
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(g.ready, 1);
-  }
-}
-
-__global__ void __launch_bounds__(256, 3) gemm_nt_sub_n64_kernel(GemmArgs g) {
-  __shared__ __attribute__((aligned(16))) double lds[2 * G6_STAGE];  // 48 KB
-  static_assert(2 * G6_STAGE >= 64 * 65 + 64 + 128, "LDS of the diagonal role (SMALL form)");
-  int64_t b = blockIdx.x;
-  if (g.diagA != nullptr) {
-    if (b == 0) {
-      if (g.ready) {
-        if (threadIdx.x == 0) {
-          int spins = 0;
-          while (__hip_atomic_load(g.ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < g.ready_target) {
-            __builtin_amdgcn_s_sleep(8);
-            if (++spins > (1 << 24)) { atomicExch(g.ready + 1, 1); break; }
-          }
-        }
-        __syncthreads();
-        __threadfence();
-      }
-      diag_block_role<true>(g.diagA, g.ldc, g.diag_nbw, g.diag_off, g.diag_info, lds);
-      return;
-    }
-    b -= 1;
-  }
-  gemm_block_n64(g, lds, b);
-}
-
-// Persistent form of the fused launch (round 6, option gemm.persist): 2 workgroups per CU stay resident and pull tiles
-// from per-XCD counters in the order the hardware dispatcher would have started them (item i of XCD x = block 8 i + x:
-// the same super-tile -> L2 mapping), so a slot never waits for a workgroup launch between two tiles (measured with the
-// traced kernel: 8-22 k cycles from a tile's last store to the first instruction of the next workgroup on that CU, during
-// which the CU's other workgroup runs alone at ~0.7 of the pipe -- profiles/r06_gemm_trace.txt).  The index of the NEXT
-// tile is requested before a tile's last k-tile (gemm_tile_body); workgroup 0 factors the diagonal block first and then joins.
-template <int CKS, int FLAGS>
-__global__ void __launch_bounds__(256, 2) gemm_nt_sub_persist_kernel(GemmArgs g) {
-  __shared__ __attribute__((aligned(16))) double lds[2][2][GT * GPITCH];
-  __shared__ unsigned s_item[2];
-  if (blockIdx.x == 0 && g.diagA != nullptr) {
-    if (g.ready) {
-      if (threadIdx.x == 0) {
-        int spins = 0;
-        while (__hip_atomic_load(g.ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < g.ready_target) {
-          __builtin_amdgcn_s_sleep(8);
-          if (++spins > (1 << 24)) { atomicExch(g.ready + 1, 1); break; }
-        }
-      }
-      __syncthreads();
-      __threadfence();
-    }
-    diag_block_role(g.diagA, g.ldc, g.diag_nbw, g.diag_off, g.diag_info, &lds[0][0][0]);
-    __syncthreads();
-  }
-  const unsigned xcd = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;  // XCC_ID: the XCD this workgroup really runs on
-  unsigned* const q = g.queue + xcd * 16;
-  // items of this XCD: first the second problem's blocks v = 8 i + xcd < tiles2, then the tile list's blocks
-  const unsigned n2 = (unsigned)g.tiles2 > xcd ? ((unsigned)g.tiles2 - xcd + 7u) / 8u : 0u;
-  const unsigned n_mine = n2 + (unsigned)((g.n_items - g.tiles2) / 8);
-  if (threadIdx.x == 0) s_item[0] = atomicAdd(q, 1u);
-  __syncthreads();
-  unsigned item = __builtin_amdgcn_readfirstlane(s_item[0]);
-  while (item < n_mine) {
-    if (threadIdx.x == 0) s_item[1] = 0u;  // set by the tile body once it has requested the next item
-    // the arguments are re-read from the kernarg segment per tile (an opaque pointer): kept live across the tile body they
-    // cost ~300 SGPR spills
-    // (constant address space: scalar loads; through a generic pointer they would be vector loads and every tile
-    //  parameter a lane value)
-#if defined(__HIP_DEVICE_COMPILE__)  // (the host pass of hipcc parses kernel bodies too and has no address spaces)
-    typedef const __attribute__((address_space(4))) GemmArgs* kernarg_ptr;
-    kernarg_ptr gp = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();  // GemmArgs is the kernel's only argument
-    asm volatile("" : "+s"(gp));
-    GemmArgs gl = *gp;
-#else
-    GemmArgs gl = g;
-#endif
-    gl.queue = q;  // this XCD's counter
-    const int64_t v = item < n2 ? (int64_t)item * 8 + xcd : (int64_t)gl.tiles2 + (int64_t)(item - n2) * 8 + xcd;
-    gemm_block<false, true, true, CKS, FLAGS>(gl, lds, v, s_item);
-    // every wavefront is done with the LDS tiles; s_item is visible.  LDS-only barriers: __syncthreads() carries a vmcnt(0),
-    // i.e. it would wait for the tile's 64 stores per lane to drain (5-12 k cycles) before the next tile's loads are issued
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (s_item[1] == 0u) {  // a skipped or ragged tile: nothing was requested on the way (workgroup-uniform)
-      if (threadIdx.x == 0) s_item[0] = atomicAdd(q, 1u);
-      __syncthreads();
-    }
-    item = __builtin_amdgcn_readfirstlane(s_item[0]);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // (s_item is rewritten at the top)
-  }
-}
-
-// Traced instantiation of the production loop (option gemm.trace): the same launch, every full tile leaves its stamps.
-__global__ void __launch_bounds__(256, 2) gemm_nt_sub_diag_trace_kernel(GemmArgs g) {
-  __shared__ __attribute__((aligned(16))) double lds[2][2][GT * GPITCH];
-  if (blockIdx.x == 0) {
-    if (g.ready) {
-      if (threadIdx.x == 0) {
-        int spins = 0;
-        while (__hip_atomic_load(g.ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < g.ready_target) {
-          __builtin_amdgcn_s_sleep(8);
-          if (++spins > (1 << 24)) { atomicExch(g.ready + 1, 1); break; }
-        }
-      }
-      __syncthreads();
-      __threadfence();
-    }
-    diag_block_role(g.diagA, g.ldc, g.diag_nbw, g.diag_off, g.diag_info, &lds[0][0][0]);
-    return;
-  }
-  gemm_block<false, true, true, 5, 1>(g, lds, (int64_t)blockIdx.x - 1);
+  gemm_block<false>(g, lds, (int64_t)blockIdx.x - 1);
 }
 
 __global__ void __launch_bounds__(64) potrf64_kernel(double* __restrict__ A, int64_t ld, int w,
@@ -1897,16 +1256,16 @@ __global__ void __launch_bounds__(256) rank64_update_kernel(const double* __rest
         if (crow[i][r] < m && ccol[j] < ncols) C[(int64_t)crow[i][r] * ld + ccol[j]] = acc[i][j][r];
 }
 
-// Factor one panel: columns [k0, k0+nb), rows [k0, n), 64-wide sub-steps (potrf64 / trsm64 / K=64 gemm).
+// Factor one panel: columns [k0, k0+nb), rows [k0, n), 64-wide sub-steps (potrf_trsm64 / rank-64 update).
 int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int64_t ld, int64_t k0, int64_t nb);
 
 // Panel = diagonal block (the 64-wide step chain, but only over the nb rows of the block) + ONE row-local solve of
-// all rows below (option chol.panel_kernel = 1, default); the step chain over the whole strip otherwise.
+// all rows below; the step chain over the whole strip for ragged or unaligned panels.
 static int panel_factor(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int64_t ld, int64_t k0,
                         int64_t nb) {
   const int64_t below = n - k0 - nb;
   const bool aligned = (reinterpret_cast<uintptr_t>(A) & 31) == 0 && (ld % 4 == 0) && (k0 % 4 == 0);
-  if (ctx_opt_i(ctx, "chol.panel_kernel", 1) && nb % 64 == 0 && nb <= 512 && below > 0 && aligned) {
+  if (nb % 64 == 0 && nb <= 512 && below > 0 && aligned) {
     GDML_TRY(panel_factor_steps(ctx, st, A, k0 + nb, ld, k0, nb));
     return launch_panel_trsm(ctx, st, A + k0 * ld + k0, A + (k0 + nb) * ld + k0, ld, (int)nb, below);
   }
@@ -1915,10 +1274,8 @@ static int panel_factor(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int
 
 int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int64_t ld, int64_t k0,
                        int64_t nb) {
-  const int fused = ctx_opt_i(ctx, "chol.panel_fused", 1);  // 0: separate potrf64 / trsm64 launches
-  const int small_upd = ctx_opt_i(ctx, "chol.small_update", 1);  // 0: the rank-64 updates of the chain through the GEMM tile kernel (A/B)
   double* save = nullptr;  // two 64 x 64 slots for the deferred write-back of the diagonal blocks
-  if (fused) GDML_TRY(ctx_slot(ctx, 5, 2 * 4096 * 8, &save));
+  GDML_TRY(ctx_slot(ctx, 5, 2 * 4096 * 8, &save));
   const double* Lprev = nullptr;
   double* Aprev = nullptr;
   int wprev = 0, flip = 0;
@@ -1927,7 +1284,7 @@ int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int6
     const int w = (int)((nb - jj < 64) ? nb - jj : 64);
     double* Ad = A + c0 * ld + c0;
     const int64_t m = n - c0 - w;
-    if (fused && m > 0) {
+    if (m > 0) {
       double* X = A + (c0 + w) * ld + c0;
       double* Lsave = save + flip * 4096;
       hipLaunchKernelGGL(potrf_trsm64_kernel, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, st, Ad, X, ld, w, m,
@@ -1937,28 +1294,11 @@ int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int6
       Aprev = Ad;
       wprev = w;
       flip ^= 1;
-    } else {
-      if (Lprev) {  // flush the pending diagonal block before a plain step
-        hipLaunchKernelGGL(writeback_block_kernel, dim3(1), dim3(256), 0, st, Lprev, Aprev, ld, wprev);
-        ctx->launch_counter++;
-        Lprev = nullptr;
-      }
-      hipLaunchKernelGGL(potrf64_kernel, dim3(1), dim3(64), 0, st, Ad, ld, w, c0, ctx->d_info);
-      ctx->launch_counter++;
-      if (m > 0) {
-        double* X = A + (c0 + w) * ld + c0;
-        hipLaunchKernelGGL(trsm64_kernel, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, st, Ad, X, ld,
-                           w, m, ld);
-        ctx->launch_counter++;
-      }
-    }
-    if (m > 0) {
-      double* X = A + (c0 + w) * ld + c0;
       const int64_t ncols = k0 + nb - (c0 + w);
       if (ncols > 0) {
         // rest of the panel:  C[c0+w:n, c0+w:k0+nb] -= X[c0+w:n, :] X[c0+w:k0+nb, :]^T
         const bool al32 = (reinterpret_cast<uintptr_t>(X) & 31) == 0 && (ld % 4 == 0);
-        if (w == 64 && m <= 2048 && al32 && small_upd) {  // a handful of tiles: one wavefront per 32 x 32 tile
+        if (w == 64 && m <= 2048 && al32) {  // a handful of tiles: one wavefront per 32 x 32 tile
           const int tiles = (int)(ceil_div(m, 32) * ceil_div(ncols, 32));
           hipLaunchKernelGGL(rank64_update_kernel, dim3((unsigned)ceil_div(tiles, 4)), dim3(256), 0, st, X, X,
                              A + (c0 + w) * ld + (c0 + w), ld, (int)m, (int)ncols, 1);
@@ -1967,6 +1307,14 @@ int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int6
           GDML_TRY(launch_gemm_nt_sub(ctx, st, X, ld, X, ld, A + (c0 + w) * ld + (c0 + w), ld, m, ncols, w, 0));
         }
       }
+    } else {  // last block of the matrix: flush the pending diagonal block, then factor this one alone
+      if (Lprev) {
+        hipLaunchKernelGGL(writeback_block_kernel, dim3(1), dim3(256), 0, st, Lprev, Aprev, ld, wprev);
+        ctx->launch_counter++;
+        Lprev = nullptr;
+      }
+      hipLaunchKernelGGL(potrf64_kernel, dim3(1), dim3(64), 0, st, Ad, ld, w, c0, ctx->d_info);
+      ctx->launch_counter++;
     }
   }
   if (Lprev) {
@@ -1978,119 +1326,86 @@ int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int6
 
 // n: order of the matrix; n_rows >= n: rows n..n_rows-1 are carried along (right-hand sides stored as extra
 // rows: they go through the panel solves and trailing updates, i.e. through the forward substitution)
-static int chol_factor_level(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int* info_out, int64_t n_rows) {
+int chol_factor_device(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int* info_out, int64_t n_rows) {
   if (n_rows < n) n_rows = n;
   HIP_CHECK(ctx, hipMemsetAsync(ctx->d_info, 0, sizeof(int), ctx->stream));
-  if (ctx->gemm_queue) {  // tile counters of the persistent trailing updates: one zeroed set per launch
-    HIP_CHECK(ctx, hipMemsetAsync(ctx->gemm_queue, 0, (size_t)ctx->gemm_queue_sets * 512, ctx->stream));
-    ctx->gemm_queue_next = 0;
-  }
   int64_t NB = (int64_t)ctx_opt(ctx, "chol.nb", 512);  // outer panel width (multiple of 64)
   if (NB < 64 || NB % 64 || NB > 512) NB = 512;  // the diagonal-block role and the row-local solve hold at most 8 x 64 columns
-  const bool lookahead = ctx_opt_i(ctx, "chol.lookahead", 1) != 0;
-  // ---- default schedule: ONE stream.  Per panel k:  GEMM1 (columns of panel k+1)  ->  SYRK of the rest, whose
-  // workgroup 0 factors the diagonal block of panel k+1 meanwhile  ->  row-local solve of panel k+1's rows.
-  // The 64-wide step chain of the diagonal block is hidden inside the SYRK launch; only the row-local solve
-  // (one launch) stays between two GEMM launches.  Near the end (SYRK shorter than the single-workgroup block
-  // factorisation) the block is factored by the multi-workgroup step chain instead.
-  if (ctx_opt_i(ctx, "chol.fused_diag", 1) && lookahead) {
-    hipStream_t st = ctx->stream;
-    const int64_t min_rows = (int64_t)ctx_opt(ctx, "chol.fused_min_rows", 12288);
-    // Panel PAIRS: while the trailing matrix is large, two NB-wide panels a | b form an outer panel of OB = 2 NB columns
-    // and the bulk of the trailing update runs with K = OB, which halves the C read-modify-write traffic per flop of the
-    // SYRK (its epilogue is ~6 % of the launch at K = 512).  The bulk launch is split in two halves of its tile list so
-    // that each of the two NB x NB diagonal blocks still has a long launch to hide behind:
-    //   GEMM1 (columns of a | b, K = OB)  ->  bulk half 1 + [block a]  ->  solve rows below a  ->  K = NB GEMM onto b's columns
-    //   ->  bulk half 2 + [block b]  ->  solve rows below b.
-    // Once the bulk gets too short (n - t1 < chol.outer_min_rows) new panels are single NB-wide ones again.
-    int64_t OB = (int64_t)ctx_opt(ctx, "chol.outer", 1024);
-    if (OB != 2 * NB) OB = NB;
-    const int64_t outer_min_rows = (int64_t)ctx_opt(ctx, "chol.outer_min_rows", 16384);
-    // "how much trailing matrix is left behind column t": its columns for the square systems of rounds 1-5; for a TALL block
-    // (round 6, two-level schedule below: n columns, n_rows >> n rows carried along) the geometric mean of rows and columns,
-    // so that the long launches of a tall block keep the paired / fused forms.  floor(sqrt((n_rows - t)(n - t))) = n - t for
-    // n_rows = n and n_rows = n + 1 (carried right-hand side): the square schedule is unchanged.
-    const double tall_f = ctx_opt(ctx, "chol.block_f", 2.0);
-    auto left_at = [&](int64_t t) -> int64_t {
-      if (t >= n) return 0;
-      if (n_rows - n <= 1) return n - t;
-      // (tall: the update is a full rectangle, the square case's a triangle; chol.block_f weighs that -- tuned by measurement)
-      return (int64_t)sqrt(tall_f * (double)(n_rows - t) * (double)(n - t));
-    };
-    auto width_at = [&](int64_t c0) -> int64_t {  // width of the panel that starts at column c0
-      const int64_t w = (OB > NB && n - (c0 + OB) > 0 && left_at(c0 + OB) >= outer_min_rows) ? OB : NB;
-      return (n - c0 < w) ? n - c0 : w;
-    };
-    // first panel: always one level (nothing to hide its diagonal block behind)
-    int64_t k0 = 0, nb = (n < NB) ? n : NB;
-    int ready_count = 0;  // cumulative target of the tile counter d_info[6]
-    HIP_CHECK(ctx, hipMemsetAsync(ctx->d_info + 6, 0, 2 * sizeof(int), ctx->stream));  // counter, wait-timeout flag
-    GDML_TRY(panel_factor(ctx, st, A, n_rows, ld, 0, nb));
-    for (;;) {
-      const int64_t t0 = k0 + nb;
-      if (t0 >= n) break;
-      const int64_t nb2 = width_at(t0);
-      const int64_t t1 = t0 + nb2;
-      const double* P = A + t0 * ld + k0;
-      const bool fuse = (nb2 % 64 == 0) && (left_at(t1) >= min_rows) && (n_rows - t1 > 0);
-      // the merged schedule counts finished GT x GT tiles of a diagonal block: NB must be a whole number of tiles, or the
-      // counter target is too small and the block is factored before its last update arrived
-      const bool merged = fuse && nb2 == 2 * NB && NB % GT == 0 && ctx_opt_i(ctx, "chol.merge_gemm1", 1) != 0;
-      if (!merged) GDML_TRY(launch_gemm_nt_sub(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, nb2, nb, 0));
-      if (merged) {
-        // ONE lower SYRK over everything right of the finished panel, in two launches of its super-tile list.  The first
-        // super-tile column is exactly the columns of a | b (2 NB = 8 tiles): it is enumerated first, workgroup 0 of the
-        // first launch waits for the 10 tiles of block a (counter) and factors it while the rest of the launch runs.
-        const int64_t ta = t0 + NB;  // first row / column of b
-        const int64_t sm = (ceil_div(n_rows - t0, GT) + 7) / 8, n_super_all = sm * (sm + 1) / 2;
-        int64_t s_split = n_super_all / 2;
-        if (s_split < sm) s_split = sm;
-        const double fs = ((double)s_split + 0.5) / (double)n_super_all;
-        DiagJob dj;
-        dj.A = A + t0 * ld + t0; dj.nbw = (int)(NB / 64); dj.off = t0;
-        dj.col0_first = true;
-        dj.ready = ctx->d_info + 6;
-        // (tiles of a diagonal block: lower 128 x 128 tiles, or with gemm.n64 the 128 x 64 tiles that touch its lower triangle)
-        const int block_tiles = gemm_use_n64(ctx) ? (int)((NB / GT) * (NB / GT + 1)) : (int)((NB / GT) * (NB / GT + 1) / 2);
-        ready_count += block_tiles;
-        dj.ready_target = ready_count;
-        GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, 0.0, fs, true,
-                                         &dj));
-        double* Xa = A + ta * ld + t0;  // rows below block a (they include b's rows of the outer panel)
-        GDML_TRY(launch_panel_trsm(ctx, st, A + t0 * ld + t0, Xa, ld, (int)NB, n_rows - ta));
-        // second launch: the K = NB update of b's columns by panel a rides in front of the remaining SYRK tiles; workgroup 0
-        // waits for the tiles of block b and factors it
-        dj.A = A + ta * ld + ta; dj.off = ta;
-        dj.A2 = Xa; dj.B2 = Xa; dj.C2 = A + ta * ld + ta; dj.M2 = n_rows - ta; dj.N2 = NB; dj.K2 = NB;
-        ready_count += block_tiles;
-        dj.ready_target = ready_count;
-        GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, fs, 1.0, true,
-                                         &dj));
-        GDML_TRY(launch_panel_trsm(ctx, st, A + ta * ld + ta, A + t1 * ld + ta, ld, (int)NB, n_rows - t1));
-      } else if (fuse && nb2 == 2 * NB) {
-        const double* P1 = A + t1 * ld + k0;
-        const int64_t ta = t0 + NB;  // first row / column of b
-        DiagJob dj;
-        dj.A = A + t0 * ld + t0; dj.nbw = (int)(NB / 64); dj.off = t0;
-        GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P1, ld, P1, ld, A + t1 * ld + t1, ld, n_rows - t1, n - t1, nb, 1, 0.0,
-                                         0.5, true, &dj));
-        double* Xa = A + ta * ld + t0;  // rows below block a (they include b's rows of the outer panel)
-        GDML_TRY(launch_panel_trsm(ctx, st, A + t0 * ld + t0, Xa, ld, (int)NB, n_rows - ta));
-        GDML_TRY(launch_gemm_nt_sub(ctx, st, Xa, ld, Xa, ld, A + ta * ld + ta, ld, n_rows - ta, NB, NB, 0));
-        dj.A = A + ta * ld + ta; dj.off = ta;
-        GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P1, ld, P1, ld, A + t1 * ld + t1, ld, n_rows - t1, n - t1, nb, 1, 0.5,
-                                         1.0, true, &dj));
-        GDML_TRY(launch_panel_trsm(ctx, st, A + ta * ld + ta, A + t1 * ld + ta, ld, (int)NB, n_rows - t1));
-      } else if (fuse) {
+  // ONE stream.  Per panel k:  GEMM1 (columns of panel k+1)  ->  SYRK of the rest, whose workgroup 0 factors the diagonal
+  // block of panel k+1 meanwhile  ->  row-local solve of panel k+1's rows.  The 64-wide step chain of the diagonal block is
+  // hidden inside the SYRK launch; only the row-local solve (one launch) stays between two GEMM launches.  Near the end (SYRK
+  // shorter than the single-workgroup block factorisation) the block is factored by the multi-workgroup step chain instead.
+  hipStream_t st = ctx->stream;
+  const int64_t min_rows = (int64_t)ctx_opt(ctx, "chol.fused_min_rows", 12288);
+  // Panel PAIRS: while the trailing matrix is large, two NB-wide panels a | b form an outer panel of OB = 2 NB columns
+  // and the bulk of the trailing update runs with K = OB, which halves the C read-modify-write traffic per flop of the
+  // SYRK (its epilogue is ~6 % of the launch at K = 512).  ONE lower SYRK covers everything right of the finished panel, in
+  // two launches of its super-tile list, so that each of the two NB x NB diagonal blocks has a long launch to hide behind:
+  //   bulk half 1 + [block a]  ->  solve rows below a  ->  bulk half 2 + K = NB update of b's columns by a + [block b]
+  //   ->  solve rows below b.
+  // The diagonal-block workgroup counts finished GT x GT tiles of its block, so pairs need NB % GT == 0 (a block of a
+  // ragged NB would be factored before its last update arrived): other NB run single panels.  Once the bulk gets too
+  // short (n - t1 < chol.outer_min_rows) new panels are single NB-wide ones again.
+  int64_t OB = (int64_t)ctx_opt(ctx, "chol.outer", 1024);
+  if (OB != 2 * NB || NB % GT != 0) OB = NB;
+  const int64_t outer_min_rows = (int64_t)ctx_opt(ctx, "chol.outer_min_rows", 16384);
+  auto width_at = [&](int64_t c0) -> int64_t {  // width of the panel that starts at column c0
+    const int64_t left = n - (c0 + OB);  // trailing matrix behind the pair
+    const int64_t w = (OB > NB && left > 0 && left >= outer_min_rows) ? OB : NB;
+    return (n - c0 < w) ? n - c0 : w;
+  };
+  // first panel: nothing to hide its diagonal block behind
+  int64_t k0 = 0, nb = (n < NB) ? n : NB;
+  int ready_count = 0;  // cumulative target of the tile counter d_info[6]
+  HIP_CHECK(ctx, hipMemsetAsync(ctx->d_info + 6, 0, 2 * sizeof(int), ctx->stream));  // counter, wait-timeout flag
+  GDML_TRY(panel_factor(ctx, st, A, n_rows, ld, 0, nb));
+  for (;;) {
+    const int64_t t0 = k0 + nb;
+    if (t0 >= n) break;
+    const int64_t nb2 = width_at(t0);
+    const int64_t t1 = t0 + nb2;
+    const double* P = A + t0 * ld + k0;
+    const bool fuse = (nb2 % 64 == 0) && (n - t1 >= min_rows) && (n_rows - t1 > 0);
+    if (fuse && nb2 == 2 * NB) {
+      // The first super-tile column of the SYRK is exactly the columns of a | b (2 NB = 8 tiles): it is enumerated first,
+      // workgroup 0 of the first launch waits for the 10 tiles of block a (counter) and factors it while the rest runs.
+      const int64_t ta = t0 + NB;  // first row / column of b
+      const int64_t sm = (ceil_div(n_rows - t0, GT) + 7) / 8, n_super_all = sm * (sm + 1) / 2;
+      int64_t s_split = n_super_all / 2;
+      if (s_split < sm) s_split = sm;
+      const double fs = ((double)s_split + 0.5) / (double)n_super_all;
+      DiagJob dj;
+      dj.A = A + t0 * ld + t0; dj.nbw = (int)(NB / 64); dj.off = t0;
+      dj.col0_first = true;
+      dj.ready = ctx->d_info + 6;
+      const int block_tiles = (int)((NB / GT) * (NB / GT + 1) / 2);  // lower GT x GT tiles of a diagonal block
+      ready_count += block_tiles;
+      dj.ready_target = ready_count;
+      GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, 0.0, fs, true,
+                                       &dj));
+      double* Xa = A + ta * ld + t0;  // rows below block a (they include b's rows of the outer panel)
+      GDML_TRY(launch_panel_trsm(ctx, st, A + t0 * ld + t0, Xa, ld, (int)NB, n_rows - ta));
+      // second launch: the K = NB update of b's columns by panel a rides in front of the remaining SYRK tiles; workgroup 0
+      // waits for the tiles of block b and factors it
+      dj.A = A + ta * ld + ta; dj.off = ta;
+      dj.A2 = Xa; dj.B2 = Xa; dj.C2 = A + ta * ld + ta; dj.M2 = n_rows - ta; dj.N2 = NB; dj.K2 = NB;
+      ready_count += block_tiles;
+      dj.ready_target = ready_count;
+      GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, fs, 1.0, true,
+                                       &dj));
+      GDML_TRY(launch_panel_trsm(ctx, st, A + ta * ld + ta, A + t1 * ld + ta, ld, (int)NB, n_rows - t1));
+    } else {
+      GDML_TRY(launch_gemm_nt_sub(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, nb2, nb, 0));
+      const double* P1 = A + t1 * ld + k0;
+      if (fuse) {
         DiagJob dj;
         dj.A = A + t0 * ld + t0;
         dj.nbw = (int)(nb2 / 64);
         dj.off = t0;
-        const double* P1 = A + t1 * ld + k0;
         GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P1, ld, P1, ld, A + t1 * ld + t1, ld, n_rows - t1, n - t1, nb, 1, 0.0,
                                          1.0, true, &dj));
         GDML_TRY(launch_panel_trsm(ctx, st, A + t0 * ld + t0, A + t1 * ld + t0, ld, (int)nb2, n_rows - t1));
-      } else if (ctx_opt_i(ctx, "chol.tail_lookahead", 1) && t1 < n) {
+      } else if (t1 < n) {
         // tail: the SYRK is too short to hide the single-workgroup block factorisation; the multi-workgroup step chain and
         // the row-local solve of panel k+1 run on the high-priority stream next to the (small) SYRK grid of panel k
         hipStream_t sp = ctx->stream2;
@@ -2098,96 +1413,22 @@ static int chol_factor_level(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, in
         HIP_CHECK(ctx, hipStreamWaitEvent(sp, ctx->ev_la[0], 0));
         GDML_TRY(panel_factor(ctx, sp, A, n_rows, ld, t0, nb2));
         HIP_CHECK(ctx, hipEventRecord(ctx->ev_la[1], sp));
-        const double* P1 = A + t1 * ld + k0;
         GDML_TRY(launch_gemm_nt_sub(ctx, st, P1, ld, P1, ld, A + t1 * ld + t1, ld, n_rows - t1, n - t1, nb, 1));
         HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_la[1], 0));
       } else {
         GDML_TRY(panel_factor(ctx, st, A, n_rows, ld, t0, nb2));
-        if (t1 < n) {
-          const double* P1 = A + t1 * ld + k0;
-          GDML_TRY(launch_gemm_nt_sub(ctx, st, P1, ld, P1, ld, A + t1 * ld + t1, ld, n_rows - t1, n - t1, nb, 1));
-        }
       }
-      k0 = t0;
-      nb = nb2;
     }
-    HIP_CHECK(ctx, hipGetLastError());
-    int info8[8] = {0};
-    HIP_CHECK(ctx, hipMemcpyAsync(info8, ctx->d_info, sizeof(info8), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (info8[7] != 0)
-      return gdml_fail(ctx, GDML_ERR_HIP, "Cholesky: the diagonal-block workgroup gave up waiting for its tiles (schedule bug)");
-    if (info_out) *info_out = info8[0];
-    return GDML_OK;
-  }
-  // ---- round-1 schedule (option chol.fused_diag = 0; A/B reference): the step chain of panel k+1 on a second
-  // stream with one panel of look-ahead (the hardware hardly overlaps it: profiles/r02_sched_probe.txt), or fully
-  // sequential on one stream with chol.lookahead = 0
-  hipStream_t sm = ctx->stream, sp = ctx->stream2;
-  hipEvent_t evA = ctx->ev_la[0], evB = ctx->ev_la[1];
-  GDML_TRY(panel_factor(ctx, sm, A, n_rows, ld, 0, n < NB ? n : NB));
-  for (int64_t k0 = 0; k0 < n; k0 += NB) {
-    const int64_t nb = (n - k0 < NB) ? n - k0 : NB;
-    const int64_t t0 = k0 + nb;
-    if (t0 >= n) break;
-    const int64_t nb2 = (n - t0 < NB) ? n - t0 : NB;
-    const int64_t t1 = t0 + nb2;
-    const double* P = A + t0 * ld + k0;  // rows t0.. of panel k
-    // (1) next panel's columns: C[t0:n, t0:t1] -= P[t0:n] P[t0:t1]^T
-    GDML_TRY(launch_gemm_nt_sub(ctx, sm, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, nb2, nb, 0));
-    if (lookahead) {
-      HIP_CHECK(ctx, hipEventRecord(evA, sm));
-      HIP_CHECK(ctx, hipStreamWaitEvent(sp, evA, 0));
-      GDML_TRY(panel_factor(ctx, sp, A, n_rows, ld, t0, nb2));
-      HIP_CHECK(ctx, hipEventRecord(evB, sp));
-    }
-    // (2) rest of the trailing matrix: C[t1:n, t1:n] -= P[t1:n] P[t1:n]^T  (lower)
-    if (t1 < n) {
-      const double* P1 = A + t1 * ld + k0;
-      GDML_TRY(launch_gemm_nt_sub(ctx, sm, P1, ld, P1, ld, A + t1 * ld + t1, ld, n_rows - t1, n - t1, nb, 1));
-    }
-    if (lookahead)
-      HIP_CHECK(ctx, hipStreamWaitEvent(sm, evB, 0));
-    else
-      GDML_TRY(panel_factor(ctx, sm, A, n_rows, ld, t0, nb2));
+    k0 = t0;
+    nb = nb2;
   }
   HIP_CHECK(ctx, hipGetLastError());
-  int info = 0;
-  HIP_CHECK(ctx, hipMemcpyAsync(&info, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  int info8[8] = {0};
+  HIP_CHECK(ctx, hipMemcpyAsync(info8, ctx->d_info, sizeof(info8), hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  if (info_out) *info_out = info;
-  return GDML_OK;
-}
-
-// Two-level schedule (round 6, option chol.block = W > 0): the matrix is factored in column blocks of W columns.  A block --
-// W columns, ALL rows below its diagonal carried along -- goes through the schedule above (its trailing updates stay inside the
-// block's columns), then ONE lower update of depth W brings everything right of the block up to date.  The bulk of the flops
-// (1 - 1.5 W / n of them) runs in products of depth W instead of 1024: a C tile is read and written n / W times instead of
-// n / 1024 times and the tile turnover that costs the K = 1024 update 14 % of its time shrinks with it (by shape, idle chip, zero
-// operands: K = 1024 0.885, K = 4096 0.927, K = 16384 0.934 of the peak: profiles/r06_gemm_shapes.txt).
-int chol_factor_device(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int* info_out, int64_t n_rows) {
-  if (n_rows < n) n_rows = n;
-  int64_t W = (int64_t)ctx_opt(ctx, "chol.block", 0);
-  if (W % 1024 != 0 || W < 2048) W = 0;
-  if (W == 0 || n < 3 * W || ctx_opt_i(ctx, "chol.fused_diag", 1) == 0 || ctx_opt_i(ctx, "chol.lookahead", 1) == 0)
-    return chol_factor_level(ctx, A, n, ld, info_out, n_rows);
-  if (info_out) *info_out = 0;
-  for (int64_t c0 = 0; c0 < n;) {
-    int64_t w = (n - c0 < W) ? n - c0 : W;
-    if (n - (c0 + w) < W / 2) w = n - c0;  // no sliver at the end: the last block takes it
-    int inf = 0;
-    GDML_TRY(chol_factor_level(ctx, A + c0 * ld + c0, w, ld, &inf, n_rows - c0));
-    if (inf != 0) {
-      if (info_out) *info_out = (int)(c0 + inf);
-      return GDML_OK;
-    }
-    const int64_t t1 = c0 + w;
-    if (t1 < n_rows && t1 < n) {
-      const double* P = A + t1 * ld + c0;  // rows below the block, the block's columns
-      GDML_TRY(launch_gemm_nt_sub(ctx, ctx->stream, P, ld, P, ld, A + t1 * ld + t1, ld, n_rows - t1, n - t1, w, 1));
-    }
-    c0 = t1;
-  }
+  if (info8[7] != 0)
+    return gdml_fail(ctx, GDML_ERR_HIP, "Cholesky: the diagonal-block workgroup gave up waiting for its tiles (schedule bug)");
+  if (info_out) *info_out = info8[0];
   return GDML_OK;
 }
 

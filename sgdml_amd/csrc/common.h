@@ -97,9 +97,6 @@ struct gdml_ctx {
   unsigned* d_fused_counter = nullptr;
   unsigned long long fused_seq = 0;
   int64_t launch_counter = 0;
-  unsigned* gemm_queue = nullptr;    // ring of tile-counter sets (8 x 64 bytes each) of the persistent GEMM launches
-  int gemm_queue_sets = 256, gemm_queue_next = 0;
-  int gemm_trace_seen = 0;           // fused GEMM launches seen since option gemm.trace was set (chol.hip)
   bool profiling = false;
   std::map<std::string, KernelStat> kstats;
   std::vector<PendingTiming> pending;
@@ -246,8 +243,6 @@ int launch_gemm_nt_sub(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t l
                        int64_t ldb, double* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int lower);
 int launch_gemm_nt_neg(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb,
                        double* C, int64_t ldc, int64_t M, int64_t N, int64_t K);  // C = -A B^T (C is not read)
-int launch_gemm_nt_sub_fill(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb,
-                            double* C, int64_t ldc, int64_t M, int64_t N, int64_t K);  // tile shape by chip fill
 // lower structure of a block-row-cyclic local matrix (see GemmArgs in chol.hip)
 struct CyclicLower {
   int W = 0, rank = 0;

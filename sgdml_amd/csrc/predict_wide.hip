@@ -343,7 +343,7 @@ int predict_wide_device(gdml_ctx* ctx, const double* d_xq, int64_t B, double* pa
     // S = -X_p X_q^T, T = -JA_p X_q^T  (zero padding contributes nothing)
     // one launch for both: [Xpad; Jpad] and [S; T] are contiguous stacks of 2 MP rows
     if (pad) GDML_TRY(launch_gemm_nt_neg(ctx, st, Xpad, Dp, Qpad, Dp, S, Bc, 2 * MPp, bcp, Dp));
-    else GDML_TRY(launch_gemm_nt_sub_fill(ctx, st, Xpad, Dp, Qpad, Dp, S, Bc, 2 * MPp, bcp, Dp));
+    else GDML_TRY(launch_gemm_nt_sub(ctx, st, Xpad, Dp, Qpad, Dp, S, Bc, 2 * MPp, bcp, Dp, 0));
     hipLaunchKernelGGL(matern_pairs_kernel, dim3(ceil_div(bc, 256), nparts), dim3(256), 0, st, S, T, Bc, MP, bc, nx, nX, cX,
                        md.has_aE ? md.aE : nullptr, md.sig, rows_per, pw, pe);
     double* Fx = part_F + q0 * D;

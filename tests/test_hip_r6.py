@@ -197,58 +197,37 @@ def test_plain_bench_line_and_dumped_outputs(tmp_path, ctx):
     assert np.abs(Eq - got['E']).max() <= 1e-10 * np.abs(Eq).max()
 
 
-def test_persistent_trailing_update_is_bitwise_the_plain_one(ctx):
-    """Option gemm.persist = 1 (resident workgroups pulling tiles from per-XCD counters, csrc/chol.hip) against the default
-    launch-per-tile schedule at a size whose trailing updates are long enough to take it (n = 9450: 2 775 lower tiles in the
-    first fused launch, the threshold is four rounds of 512): every tile is the same arithmetic in the same order, so the
-    factor's solution is BIT-identical, with the right-hand side carried through and with the merged schedule's tile counter
-    (the diagonal-block workgroup waits for tiles that persistent workgroups compute)."""
+def test_factorisation_at_n9450_with_the_carried_right_hand_side(ctx):
+    """The blocked Cholesky (csrc/chol.hip) at n = 9450 (N = 21, M = 150) with the right-hand side carried as an extra row: edge
+    tiles in both dimensions, the K = 64 updates inside the panel factorisation, the step chain of the tail on the second
+    stream; then with the thresholds lowered, so that the same system also runs panel pairs with the merged first launch (whose
+    diagonal-block workgroup waits on the tile counter) and fused single panels.  Each solution is inside the operator's
+    residual contract, and a matrix that is not positive definite (lam far below zero) reports a failing leading minor."""
     N, M = 21, 150
     ds = orc.synth_dataset(N, M, seed=4, jitter=0.3)
     xd, gd = orc.desc_from_R(ds['R'].reshape(M, -1))
     tp = orc.tril_perms_from_atom_perms(np.arange(N)[None])
     y = ds['F'].ravel() / np.std(ds['F'])
     ctx.train_upload(xd, gd, tp)
-    sols = {}
-    for persist in (0, 1):
-        ctx.set_option('gemm.persist', persist)
+    sols = []
+    for opts in ({}, {'chol.outer_min_rows': 2048, 'chol.fused_min_rows': 1024}):
+        for k, v in opts.items():
+            ctx.set_option(k, v)
         ctx.assemble_K(20.0, False, alloc_extra_rows=1, for_cholesky=1e-10)
         ctx.chol_set_rhs(y)
-        assert ctx.chol_factor(1e-10) == 0
-        sols[persist] = ctx.chol_solve(None)
-    assert np.array_equal(sols[0], sols[1])
+        assert ctx.chol_factor(1e-10) == 0, opts
+        sols.append(ctx.chol_solve(None))
+        ctx.assemble_K(20.0, False, alloc_extra_rows=1, for_cholesky=-1e-3)
+        ctx.chol_set_rhs(y)
+        try:
+            info = ctx.chol_factor(-1e-3)
+        except np.linalg.LinAlgError as e:
+            info = str(e)
+        assert info != 0, (opts, info)
     ctx.predict_upload_model(xd, np.zeros_like(xd), tp, 20.0, None)
-    r = ctx.kernel_matvec(1e-10, False, -sols[1]) + y
-    assert np.linalg.norm(r) <= 1e-10 * np.linalg.norm(y)
-
-
-def test_narrow_tile_trailing_update_solves_the_same_system(ctx):
-    """Option gemm.n64 = 1 (128 x 64 tiles, three workgroups per CU, its own diagonal-block role without the transposed copy
-    of L_jj -- csrc/chol.hip; measured 6.8 % slower, profiles/r06_gemm_n64_ab.txt, so it stays an A/B option): same system,
-    same solution up to the rounding of a different summation order, residual inside the contract.  n = 9450 with the carried
-    right-hand-side row: merged schedule with the tile counter (20 narrow tiles per diagonal block), edge tiles in both
-    dimensions, the K = 64 updates inside the panel factorisation and the plain launches of the schedule's tail."""
-    N, M = 21, 150
-    ds = orc.synth_dataset(N, M, seed=4, jitter=0.3)
-    xd, gd = orc.desc_from_R(ds['R'].reshape(M, -1))
-    tp = orc.tril_perms_from_atom_perms(np.arange(N)[None])
-    y = ds['F'].ravel() / np.std(ds['F'])
-    ctx.train_upload(xd, gd, tp)
-    sols = {}
-    try:
-        for n64 in (0, 1):
-            ctx.set_option('gemm.n64', n64)
-            ctx.assemble_K(20.0, False, alloc_extra_rows=1, for_cholesky=1e-10)
-            ctx.chol_set_rhs(y)
-            assert ctx.chol_factor(1e-10) == 0
-            sols[n64] = ctx.chol_solve(None)
-    finally:
-        ctx.set_option('gemm.n64', 0)
-    ctx.predict_upload_model(xd, np.zeros_like(xd), tp, 20.0, None)
-    for n64 in (0, 1):
-        r = ctx.kernel_matvec(1e-10, False, -sols[n64]) + y
+    for sol in sols:
+        r = ctx.kernel_matvec(1e-10, False, -sol) + y
         assert np.linalg.norm(r) <= 1e-10 * np.linalg.norm(y)
-    assert np.linalg.norm(sols[1] - sols[0]) <= 1e-6 * np.linalg.norm(sols[0])  # cond(K) ~ 1e9 times the fp64 rounding of the two orders
 
 
 def test_whole_point_index_lists_run_on_the_perm2_kernel(ctx):
@@ -621,50 +600,6 @@ def test_energy_constraint_system_of_several_row_blocks_against_the_reference(ct
     E, F = GDMLPredict(model).predict(g['R_test'].reshape(nt, -1))
     assert np.abs(F - g['F_test']).max() <= 1e-7 * np.abs(g['F_test']).max()
     assert np.abs(E - g['E_test']).max() <= 1e-7 * max(1.0, np.abs(g['E_test']).max())
-
-
-@pytest.mark.parametrize('W,f', [(2048, 2.0), (2048, 64.0), (3072, 8.0)])
-def test_two_level_factorisation_solves_the_same_system(ctx, W, f):
-    """Option chol.block = W (csrc/chol.hip, round 6: column blocks of W columns, each factored with all rows below it carried along,
-    then ONE lower update of depth W for everything to its right; measured 0.8 % slower than the one-level schedule --
-    profiles/r06_chol_block.txt -- so it stays an A/B option): same system, residual inside the contract, same solution up to the
-    rounding of a different summation order.  n = 9450 with the carried right-hand-side row: four / three blocks, the last
-    taking the sliver; chol.block_f moves the point where a tall block leaves the fused / paired forms (both ends exercised).
-    A failing pivot is reported at its global position."""
-    N, M = 21, 150
-    ds = orc.synth_dataset(N, M, seed=4, jitter=0.3)
-    xd, gd = orc.desc_from_R(ds['R'].reshape(M, -1))
-    tp = orc.tril_perms_from_atom_perms(np.arange(N)[None])
-    y = ds['F'].ravel() / np.std(ds['F'])
-    ctx.train_upload(xd, gd, tp)
-    sols = {}
-    try:
-        for blk in (0, W):
-            ctx.set_option('chol.block', blk)
-            ctx.set_option('chol.block_f', f)
-            ctx.assemble_K(20.0, False, alloc_extra_rows=1, for_cholesky=1e-10)
-            ctx.chol_set_rhs(y)
-            assert ctx.chol_factor(1e-10) == 0
-            sols[blk] = ctx.chol_solve(None)
-        # not positive definite (lam far below zero): both schedules stop at the same leading minor
-        infos = []
-        for blk in (0, W):
-            ctx.set_option('chol.block', blk)
-            ctx.assemble_K(20.0, False, alloc_extra_rows=1, for_cholesky=-1e-3)
-            ctx.chol_set_rhs(y)
-            try:
-                infos.append(ctx.chol_factor(-1e-3))
-            except np.linalg.LinAlgError as e:
-                infos.append(str(e))
-        assert infos[0] == infos[1] and infos[0] != 0, infos
-    finally:
-        ctx.set_option('chol.block', 0)
-        ctx.set_option('chol.block_f', 2.0)
-    ctx.predict_upload_model(xd, np.zeros_like(xd), tp, 20.0, None)
-    for blk in (0, W):
-        r = ctx.kernel_matvec(1e-10, False, -sols[blk]) + y
-        assert np.linalg.norm(r) <= 1e-10 * np.linalg.norm(y)
-    assert np.linalg.norm(sols[W] - sols[0]) <= 1e-6 * np.linalg.norm(sols[0])
 
 
 def test_fill_aware_split_counts_change_nothing_but_the_order_of_sums(ctx):

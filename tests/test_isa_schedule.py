@@ -1,6 +1,6 @@
 """Static checks of compiled code (no GPU): the instruction schedule of the dominant kernel's inner loop.
 
-The trailing-update GEMM of the blocked Cholesky (csrc/chol.hip, gemm_nt_sub_diag_kernel<true, true, 5>: SURVEY.md 8(d), the
+The trailing-update GEMM of the blocked Cholesky (csrc/chol.hip, gemm_nt_sub_diag_kernel: SURVEY.md 8(d), the
 kernel `roofline` is quoted on) depends on the ORDER of its phases inside one k-tile: operand pairs of the second half are read
 from LDS behind the first 16 MFMAs, the prefetched tile is committed and the barrier passed behind 48, the first half of the
 next tile is read behind the barrier and covered by the last 16.  The order is pinned with sched_barriers; in round 4 one was
@@ -101,9 +101,9 @@ def test_step_chain_prologues_keep_their_loads_in_flight():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
-def test_trailing_update_loop_keeps_its_schedule():
+def test_fused_trailing_update_loop_keeps_its_schedule():
     text = _assembly('chol')
-    sym = '_Z23gemm_nt_sub_diag_kernelILb1ELb1ELi5EEv8GemmArgs'
+    sym = '_Z23gemm_nt_sub_diag_kernel8GemmArgs'
     start = text.index('\n' + sym + ':')
     kern = text[start:text.index('.Lfunc_end', start)]  # (the kernel has several exits since it carries the panel-solve strips)
     # inner loops = from an "Inner Loop Header" label to the backward branch to that label
