@@ -164,6 +164,8 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *   pcg.f32_gram_rows (2048)  fp32 form: rows per chunk of the compensated Gram sum of the rounded factor
  *   pcg.f32_inplace (1)   fp32 form: the rounded factor overlays the fp64 factor in the matrix buffer (no second n x m buffer; the
  *                         leverage scores are cached first); 0 = a separate fp32 copy beside the fp64 factor (round 5)
+ *   predict.hess_generic (0)   1: gdml_predict_hessian keeps F_x in memory instead of registers (the path of N > 157; tests)
+ *   predict.hess_chunk_rows (0)  cap on the table rows per chunk of gdml_predict_hessian (0 = sized by memory; tests)
  *   pcg.f32_min_pivot (1e-7)  fp32 form: smallest squared Cholesky pivot of the rounded factor's Gram matrix below which the
  *                         reference's fp64 form is kept (gdml_get_option("pcg.f32_last_min_pivot") reads the last value seen)
  * Unknown keys return GDML_ERR_INVALID. */
@@ -283,6 +285,22 @@ int gdml_predict(gdml_ctx* ctx, const double* R, int64_t B, const double* lat,
  * pointers (hipMalloc'd by the caller or gdml_dev_alloc); nothing crosses PCIe. */
 int gdml_predict_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat,
                      const double* lat_inv, double* E_dev, double* F_dev);
+
+/* Analytic Hessians (force constants) H' = d^2 E' / dR^2 of B geometries, unscaled like gdml_predict (the caller
+ * multiplies by std).  The reference has no counterpart: its users take finite differences of predict().
+ * With the predictor's per-row quantities (d = x - X_rho, n = sqrt5 |d|, b = 5/(3 sig^3) exp(-n/sig), a = d . v_rho,
+ * e_rho = alphas_E entry or 0), u = J_x^T d and w = J_x^T v_rho:
+ *   H' = sum_rho [ gam u u^T + s (w u^T + u w^T) ] + tau J_x^T J_x - sum_k F_x[k] grad^2_R x_k
+ *   s = -(5/sig) b, gam = 25 a b / (sig^2 n) + (5/sig) e_rho b, tau = sum_rho [ -(5/sig) a b - e_rho b (n + sig) ]
+ * (csrc/predict_hess.hip has the derivation's symbols and the kernels).  Outputs: E_out (B) = E', F_out (B,3N) = F (both
+ * may be NULL), H_out (B,3N,3N) row-major, coordinate index 3 atom + axis, both triangles written (H is symmetric).
+ * R may not be NULL (no training-set mode); lat / lat_inv both or neither.  fp64 throughout, no atomics: the same input on
+ * the same context gives bit-identical results, and the _dev variant (device pointers throughout) equals the host one.
+ * Molecules up to N = 197; larger ones return GDML_ERR_UNSUPPORTED. */
+int gdml_predict_hessian(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv,
+                         double* E_out, double* F_out, double* H_out);
+int gdml_predict_hessian_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat,
+                             const double* lat_inv, double* E_dev, double* F_dev, double* H_dev);
 
 /* Test / validation error sums evaluated on the device (replaces the body of the reference's
  * cli.test loop, sgdml/cli.py:1564-1605 with _online_err :1170): predicts B host geometries R,

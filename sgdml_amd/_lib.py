@@ -47,6 +47,8 @@ SIGNATURES = {
     'gdml_set_alphas': (C.c_int, [_vp, _vp, _vp]),
     'gdml_predict': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     'gdml_predict_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
+    'gdml_predict_hessian': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_predict_hessian_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_kernel_matvec': (C.c_int, [_vp, C.c_double, C.c_int, _vp, C.c_int64, _vp]),
     'gdml_predict_errors': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     'gdml_nystroem_factor': (C.c_int, [_vp, C.c_double, _vp, C.c_int64, _vp, _vp, C.POINTER(C.c_int)]),
@@ -527,6 +529,36 @@ class Context(object):
             self._check(self._lib.gdml_predict(self._h, _ptr(R[b0:b1]), b1 - b0, _ptr(lat), _ptr(lat_inv), _ptr(Ec),
                                                _ptr(F[b0:b1])))
         return E, F
+
+    def hessian_batch(self):
+        """Geometries per gdml_predict_hessian call: max_query_batch scaled down by the 3N-fold larger output (9N^2 vs 3N)."""
+        return max(1, self.max_query_batch // (3 * self.model_n_atoms))
+
+    def predict_hessian(self, R, lat_and_inv=None):
+        """Unscaled E' (B,), F (B,3N) and Hessian H' = d^2 E'/dR^2 (B,3N,3N) of geometries R (B,3N) (gdml_predict_hessian)."""
+        if R is None:
+            raise ValueError('predict_hessian needs geometries (there is no training-set mode)')
+        n3 = 3 * self.model_n_atoms
+        R = f64(R).reshape(-1, n3)
+        B = R.shape[0]
+        E, F, H = np.empty(B), np.empty((B, n3)), np.empty((B, n3, n3))
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        step = self.hessian_batch()
+        for b0 in range(0, max(B, 1), step):
+            b1 = min(B, b0 + step)
+            self._check(self._lib.gdml_predict_hessian(self._h, _ptr(R[b0:b1]), b1 - b0, _ptr(lat), _ptr(lat_inv),
+                                                       _ptr(E[b0:b1]), _ptr(F[b0:b1]), _ptr(H[b0:b1])))
+        return E, F, H
+
+    def predict_hessian_dev(self, R_dev, B, E_dev, F_dev, H_dev, lat_and_inv=None):
+        """gdml_predict_hessian_dev on device pointers (ints or c_void_p; E_dev / F_dev may be None)."""
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        self._check(self._lib.gdml_predict_hessian_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), E_dev, F_dev,
+                                                       H_dev))
 
     def predict_errors(self, R, F_ref, E_ref=None, std=1.0, c=0.0, lat_and_inv=None):
         """Eight error sums of a labelled batch, evaluated on the GPU (see gdml_predict_errors)."""

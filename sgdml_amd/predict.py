@@ -84,6 +84,7 @@ class GDMLPredict(object):
             )
         self._replicas_stale = False
         self._min_shard = 64  # geometries per device below which a batch is not worth splitting
+        self._min_shard_hessian = 4  # the same for predict_hessian (one Hessian is the arithmetic of ~10 predictions)
         self._train_resident = False
 
     def __del__(self):
@@ -93,12 +94,12 @@ class GDMLPredict(object):
         if ctx is not None and getattr(self, '_owns_ctx', True):
             ctx.close()
 
-    def _sharded(self, n_items, fn):
+    def _sharded(self, n_items, fn, min_shard=None):
         """fn(ctx, lo, hi) for contiguous query shards, one per device, concurrently (ctypes releases the GIL inside the
         library calls); results in shard order.  One shard when the batch is small or the replicas do not hold the current
         coefficients (set_alphas re-targets only the first context)."""
         ctxs = [self._ctx] + ([] if self._replicas_stale else self._replicas)
-        n_sh = min(len(ctxs), max(1, n_items // self._min_shard))
+        n_sh = min(len(ctxs), max(1, n_items // (self._min_shard if min_shard is None else min_shard)))
         if n_sh <= 1:
             return [fn(self._ctx, 0, n_items)]
         import threading
@@ -199,6 +200,24 @@ class GDMLPredict(object):
         return out
 
     # ---- prediction
+
+    def predict_hessian(self, R):
+        """Energies (B,), forces (B,3N) and analytic Hessians d^2E/dR^2 (B,3N,3N) for geometries R (B,3N) or (3N,),
+        scaled like predict() (E std + c, F std, H std).  No training-set mode: R is required."""
+        if R is None:
+            raise ValueError('predict_hessian needs geometries R (there is no training-set mode)')
+        R = np.asarray(R, dtype=np.float64)
+        if R.ndim == 1:
+            R = R[None, :]
+        R = R.reshape(R.shape[0], -1)
+        parts = self._sharded(R.shape[0], lambda ctx, lo, hi: ctx.predict_hessian(R[lo:hi], self.lat_and_inv),
+                              min_shard=self._min_shard_hessian)
+        E, F, H = (parts[0] if len(parts) == 1 else [np.concatenate([p_[i] for p_ in parts]) for i in range(3)])
+        E *= self.std
+        E += self.c
+        F *= self.std
+        H *= self.std
+        return E, F, H
 
     def predict(self, R=None, return_E=True):
         """Energies (B,) and forces (B,3N) for geometries R (B,3N); R=None -> training-set mode."""
