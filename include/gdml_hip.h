@@ -166,6 +166,9 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *                         leverage scores are cached first); 0 = a separate fp32 copy beside the fp64 factor (round 5)
  *   predict.hess_generic (0)   1: gdml_predict_hessian keeps F_x in memory instead of registers (the path of N > 157; tests)
  *   predict.hess_chunk_rows (0)  cap on the table rows per chunk of gdml_predict_hessian (0 = sized by memory; tests)
+ *   predict.cov_chunk (64)     geometries per pass of gdml_predict_cov / gdml_uncert_cross (their rows of the cross-kernel are 3N n
+ *                         doubles each; fewer when free memory is short)
+ *   predict.cov_global (0)    1: the cross-kernel keeps its per-permutation vectors in global memory (the path of N > 374; tests)
  *   pcg.f32_min_pivot (1e-7)  fp32 form: smallest squared Cholesky pivot of the rounded factor's Gram matrix below which the
  *                         reference's fp64 form is kept (gdml_get_option("pcg.f32_last_min_pivot") reads the last value seen)
  * Unknown keys return GDML_ERR_INVALID. */
@@ -301,6 +304,37 @@ int gdml_predict_hessian(gdml_ctx* ctx, const double* R, int64_t B, const double
                          double* E_out, double* F_out, double* H_out);
 int gdml_predict_hessian_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat,
                              const double* lat_inv, double* E_dev, double* F_dev, double* H_dev);
+
+/* Posterior force covariance of the Gaussian process behind the model (active learning, leaving the training distribution):
+ *   cov F(x*) = k(x*,x*) - K*^T (K + lam I)^-1 K*.  The reference has no counterpart (its solve runs on the host and drops the
+ * factor).  In the library's conventions -- K the un-negated matrix of gdml_assemble_K, A = -K + lam I = L L^T, labels
+ * normalised by std -- and for one query geometry q:
+ *   Kx_q (3N x n, n = 3N M): block j = the 3N x 3N block of train.py:97-232 for row point q (un-permuted) and column point j;
+ *   k_qq (3N x 3N): the same with i = j = q;   Z_q = (-Kx_q) L^-T;   Sig_q = -k_qq - Z_q Z_q^T.
+ * The caller multiplies by std^2.  (The variance of E is not offered: forces fix E up to a constant, its posterior variance
+ * stays near 0.7 of the prior everywhere.)
+ * gdml_uncert_prepare: needs the training set of gdml_train_upload (Cartesian geometries are not part of a model file: the
+ *   caller computes their descriptors, gdml_desc_from_R).  Assembles A (gdml_assemble_A), factors it in place
+ *   (gdml_chol_factor: *info > 0 and GDML_ERR_NOT_PD for a matrix that is not positive definite) and marks the factor as
+ *   prepared.  The n x n matrix stays resident; anything that overwrites it (an assembly, a Nystroem build, an LU, a new
+ *   training set) clears the mark.  gdml_uncert_release frees the matrix and the work buffers.
+ * gdml_uncert_cross: host copies of the UN-negated Kx (B 3N x n) and k_qq (B,3N,3N) of B host geometries (either may be
+ *   NULL).  Needs only the training set, not the factor; the length scale is that of the last assembly on the context
+ *   (gdml_uncert_prepare, gdml_assemble_*), else the uploaded model's.
+ * gdml_predict_cov: cov_out (B,3N) marginal variances (full = 0) or (B,3N,3N) covariances (full != 0, both triangles), R
+ *   (B,3N) host geometries; the _dev variant takes device pointers for R and the output and gives the same bits.  fp64
+ *   throughout (the Gram step on the MFMA pipe), no atomics: repeated calls give bit-identical results and the variances
+ *   equal the diagonal of the full form bit for bit.  Batches go through in chunks (option predict.cov_chunk).
+ * GDML_ERR_STATE without a prepared factor, GDML_ERR_INVALID for a NULL R, B < 0 or a lattice without its inverse,
+ * GDML_ERR_UNSUPPORTED when the resident system carries energy-constraint rows. */
+int gdml_uncert_prepare(gdml_ctx* ctx, double sig, double lam, int* info);
+int gdml_uncert_release(gdml_ctx* ctx);
+int gdml_uncert_cross(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv,
+                      double* Kx_out, double* kqq_out);
+int gdml_predict_cov(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv, int full,
+                     double* cov_out);
+int gdml_predict_cov_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat, const double* lat_inv,
+                         int full, double* cov_dev);
 
 /* Test / validation error sums evaluated on the device (replaces the body of the reference's
  * cli.test loop, sgdml/cli.py:1564-1605 with _online_err :1170): predicts B host geometries R,

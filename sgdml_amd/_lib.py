@@ -49,6 +49,11 @@ SIGNATURES = {
     'gdml_predict_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_uncert_prepare': (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_int)]),
+    'gdml_uncert_release': (C.c_int, [_vp]),
+    'gdml_uncert_cross': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
+    'gdml_predict_cov': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
+    'gdml_predict_cov_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
     'gdml_kernel_matvec': (C.c_int, [_vp, C.c_double, C.c_int, _vp, C.c_int64, _vp]),
     'gdml_predict_errors': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     'gdml_nystroem_factor': (C.c_int, [_vp, C.c_double, _vp, C.c_int64, _vp, _vp, C.POINTER(C.c_int)]),
@@ -559,6 +564,54 @@ class Context(object):
             lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
         self._check(self._lib.gdml_predict_hessian_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), E_dev, F_dev,
                                                        H_dev))
+
+    def uncert_prepare(self, sig, lam):
+        """Factor A = -K + lam I of the resident training set and keep it for predict_cov (gdml_uncert_prepare).  Raises
+        numpy.linalg.LinAlgError when A is not positive definite, MemoryError when the n x n matrix does not fit."""
+        info = C.c_int(0)
+        self._check(self._lib.gdml_uncert_prepare(self._h, float(sig), float(lam), C.byref(info)))
+        return info.value
+
+    def uncert_release(self):
+        """Free the factor and the work buffers of predict_cov (gdml_uncert_release)."""
+        self._check(self._lib.gdml_uncert_release(self._h))
+
+    def uncert_cross(self, R, lat_and_inv=None):
+        """Un-negated cross-kernel rows Kx (B 3N, n) between geometries R and the resident training set, and k_qq (B,3N,3N)
+        (gdml_uncert_cross)."""
+        if not hasattr(self, 'n_atoms'):
+            raise GDMLHipError('uncert_cross: no training set resident (train_upload)')
+        n3 = 3 * self.n_atoms
+        R = f64(R).reshape(-1, n3)
+        B = R.shape[0]
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        Kx, kqq = np.empty((B * n3, self.n_train * n3)), np.empty((B, n3, n3))
+        self._check(self._lib.gdml_uncert_cross(self._h, _ptr(R), B, _ptr(lat), _ptr(lat_inv), _ptr(Kx), _ptr(kqq)))
+        return Kx, kqq
+
+    def predict_cov(self, R, lat_and_inv=None, full=False):
+        """Posterior force covariance in normalised units (gdml_predict_cov): (B,3N) variances, or (B,3N,3N) with full."""
+        if not hasattr(self, 'n_atoms'):
+            raise GDMLHipError('predict_cov: no training set resident (train_upload, uncert_prepare)')
+        n3 = 3 * self.n_atoms
+        R = f64(R).reshape(-1, n3)
+        B = R.shape[0]
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        out = np.empty((B, n3, n3) if full else (B, n3))
+        self._check(self._lib.gdml_predict_cov(self._h, _ptr(R), B, _ptr(lat), _ptr(lat_inv), int(bool(full)), _ptr(out)))
+        return out
+
+    def predict_cov_dev(self, R_dev, B, cov_dev, lat_and_inv=None, full=False):
+        """gdml_predict_cov_dev on device pointers (ints or c_void_p)."""
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        self._check(self._lib.gdml_predict_cov_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), int(bool(full)),
+                                                   cov_dev))
 
     def predict_errors(self, R, F_ref, E_ref=None, std=1.0, c=0.0, lat_and_inv=None):
         """Eight error sums of a labelled batch, evaluated on the GPU (see gdml_predict_errors)."""

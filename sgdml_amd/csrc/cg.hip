@@ -707,10 +707,10 @@ __global__ void __launch_bounds__(256) vec_axpy_kernel(double* __restrict__ y, c
 // owe it in ONE product of depth k0 and is then solved, instead of being read, updated by 512 and written back once per earlier
 // strip -- m / 1024 times less traffic on X and long k loops (the K = 512 update ran at 0.55 of the MFMA peak inside the
 // configs[3] build, profiles/r06_cfg34_kernel_stats.txt).  Same flops, same operations in another order.
-static int tall_trsm(gdml_ctx* ctx, const double* L, double* X, int64_t n, int64_t m, int64_t ld) {
+int tall_trsm(gdml_ctx* ctx, const double* L, double* X, int64_t n, int64_t m, int64_t ld, int look) {
   const int64_t NB = 512;
   hipStream_t st = ctx->stream;
-  const bool left = ctx_opt_i(ctx, "nys.trsm_left", 1) != 0;
+  const bool left = look < 0 ? ctx_opt_i(ctx, "nys.trsm_left", 1) != 0 : look != 0;
   for (int64_t k0 = 0; k0 < m; k0 += NB) {
     const int64_t nb = (m - k0 < NB) ? m - k0 : NB;
     if (left && k0 > 0)  // X[:, k0:k0+nb] -= X[:, 0:k0] L[k0:k0+nb, 0:k0]^T

@@ -114,6 +114,7 @@ struct gdml_ctx {
   bool K_rhs_row = false;   // row K_rows of the buffer carries a right-hand side (gdml_chol_set_rhs)
   double* d_rhs = nullptr;  // device copy of that right-hand side (iterative refinement)
   double K_lam = 0, K_sig = 0;
+  bool uncert_ready = false; // the factor in K is the one gdml_uncert_prepare built for the resident training set (uncert.hip)
   int K_use_E = 0;
 
   // Nystroem preconditioner L^-1 K_mn (m x n)
@@ -142,8 +143,8 @@ struct gdml_ctx {
   // scratch
   double* scratch = nullptr;
   int64_t scratch_bytes = 0;
-  double* slot[13] = {};  // cached work buffers (ctx_slot)
-  int64_t slot_bytes[13] = {};
+  double* slot[15] = {};  // cached work buffers (ctx_slot)
+  int64_t slot_bytes[15] = {};
   int* d_info = nullptr;
 
   // comm
@@ -258,6 +259,8 @@ int launch_panel_trsm(gdml_ctx* ctx, hipStream_t st, const double* L, double* X,
                       int64_t ldl = 0);
 int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int64_t ld, int64_t k0, int64_t nb);
 int chol_bwd_device(gdml_ctx* ctx, const double* L, int64_t n, int64_t ld, double* d_z, double* d_x);
+// X[:, 0:m] <- X L^-T for the n rows of X (cg.hip).  look: 1 left-looking, 0 right-looking, -1 = option nys.trsm_left
+int tall_trsm(gdml_ctx* ctx, const double* L, double* X, int64_t n, int64_t m, int64_t ld, int look = -1);
 int ctx_slot(gdml_ctx* ctx, int slot, int64_t bytes, double** out);
 void shard_points(const gdml_ctx* ctx, int64_t M, int64_t* p0, int64_t* p1, int64_t* pts_per);
 // Layout of the replicated device vectors of the sharded solvers (Nystroem factor rows, PCG vectors, mat-vec in / out).

@@ -161,6 +161,7 @@ extern "C" int gdml_train_upload(gdml_ctx* ctx, const double* R_desc, const doub
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
   TrainSet& ts = ctx->ts;
   int D = N * (N - 1) / 2;
+  ctx->uncert_ready = false;  // a prepared factor belongs to the training set it was built from
   GDML_TRY(upload_perms(ctx, tril_perms, P, N, ts.h_tp, ts.h_perm, ts.h_pinv));
   GDML_TRY(ctx_free(ctx, ts.x));
   GDML_TRY(ctx_free(ctx, ts.g));

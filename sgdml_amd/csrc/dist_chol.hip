@@ -163,7 +163,7 @@ extern "C" int gdml_dist_chol_solve(gdml_ctx* ctx, double sig, double lam, const
   }
   ctx->precon = nullptr;
   ctx->K_rows = Lr; ctx->K_cols = n; ctx->K_extra = 1; ctx->K_ld = ld;
-  ctx->K_factored = false; ctx->K_is_A = false; ctx->K_rhs_row = false; ctx->K_sharded = true;
+  ctx->K_factored = false; ctx->uncert_ready = false; ctx->K_is_A = false; ctx->K_rhs_row = false; ctx->K_sharded = true;
   ctx->K_destroyed = true;  // nothing but this function understands the layout
   double* A = ctx->K;
 

@@ -283,6 +283,7 @@ extern "C" int gdml_lu_solve(gdml_ctx* ctx, double lam, const double* y, int64_t
     phase_begin(ctx);
     hipLaunchKernelGGL(negate_shift_full_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, ctx->K, n, ld, lam);
     ctx->K_destroyed = true;  // whatever happens below, the buffer no longer holds K
+    ctx->uncert_ready = false;
     GDML_TRY(lu_factor_device(ctx, ctx->K, n, ld, d_piv, &inf));
     GDML_TRY(phase_end(ctx, "factor"));
     if (inf != 0) return GDML_OK;

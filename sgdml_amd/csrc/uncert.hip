@@ -1,0 +1,490 @@
+// Posterior force covariance of the Gaussian process behind an sGDML model (no counterpart in the reference, whose solve
+// runs in SciPy on the host and discards the factor).
+//
+// Conventions: K is the un-negated matrix of gdml_assemble_K, A = -K + lam I = L L^T the factored system
+// matrix resident in ctx->K (lower triangle, row-major, pitch K_ld), n = 3N M.  For a query geometry q
+//   Kx_q  (3N x n)   cross-kernel rows: block j = the 3N x 3N block of train.py:97-232 for row point q (un-permuted) and
+//                    column point j (permuted);  k_qq (3N x 3N) the same with i = j = q
+//   Z_q   = (-Kx_q) L^-T                                   (tall_trsm of cg.hip, right-looking: few rows, long factor)
+//   Sig_q = (-k_qq) - Z_q Z_q^T                            (cov_gram_kernel + cov_reduce_kernel)
+// in the units of the normalised labels; the host multiplies by std^2 (and its calibration factor).
+//
+// cross_rows_kernel, with x, g the descriptor / compressed Jacobian of q and X, G those of column point j, pi = pi_p,
+// s(a, b) = -1 if a > b else +1 (the sign of atom a's entry in the Jacobian row of the pair {a, b}, desc.py:422-471):
+//   d_p[AB]   = x[AB] - X[pi A, pi B]            n_p = sqrt5 |d_p|      b_p = 5 exp(-n_p / sig) / (3 sig^4)
+//   w_p[A,:]  = sum_B s(A,B) g[AB,:] d_p[AB]                       (= J_q^T d_p)
+//   u_p[piA,:]= sum_B s(piA,piB) G[piA piB,:] d_p[AB]              (= (J_j^p)^T d_p)
+//   T_p[(A,.),(a,.)] = J_q^T J_j^p: for a = pi A   sum_B s(A,B) s(piA,piB) g[AB,:] (x) G[piA piB,:]   (N - 1 terms)
+//                                   otherwise      s(A,B) s(a,piA) g[AB,:] (x) G[piA a,:],  B = pi^-1 a   (one term)
+//   block = sum_p [ 5 b_p w_p (x) u_p - (sig^2 + sig n_p) b_p T_p ]
+// One workgroup per (query, column point); the permutations go through LDS in groups (w, u, the diagonal blocks of T and
+// the pair sums of |d|^2 per atom), every output element is summed over a group in registers by the one thread that owns it.
+#include "common.h"
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+#define UC_SLOT_WS 13    // queries, descriptors, -k_qq, partial Gram tiles, staged output
+#define UC_SLOT_ROWS 14  // (3N B) x K_ld row buffer
+#define UC_LDS_DOUBLES 6000  // per workgroup of the cross kernel (48 KB: two workgroups per CU keep their LDS)
+
+struct CrossArgs {
+  const double* xq;     // (B,D)   query descriptors
+  const double* gq;     // (B,D,3) query compressed Jacobians
+  const double* xt;     // (M,D)   training descriptors
+  const double* gt;     // (M,D,3)
+  const int32_t* perm;  // (P,N)
+  const int32_t* pinv;  // (P,N)
+  double* rows;         // (B 3N) x ld: sgn * Kx, pad columns [n, ld) zeroed
+  double* kqq;          // (B,3N,3N):   sgn * k_qq
+  double* gws;          // per-workgroup workspace in global memory when a permutation's vectors do not fit LDS, else null
+  int64_t ld, M, items;
+  int B, N, D, P, PG, WS;
+  double sig, sgn;
+};
+
+__global__ void __launch_bounds__(256) cross_rows_kernel(CrossArgs a) {
+  extern __shared__ double uc_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int N = a.N, n3 = 3 * N, D = a.D;
+  double* const ws = a.gws ? a.gws + (int64_t)blockIdx.x * a.WS : uc_lds;
+  const double sq5 = 2.23606797749978969641;
+  const double sig = a.sig, base_div = 3.0 * sig * sig * sig * sig;
+  for (int64_t item = blockIdx.x; item < a.items; item += gridDim.x) {
+    const int q = (int)(item / (a.M + 1));
+    const int64_t j = item - (int64_t)q * (a.M + 1);
+    const bool self = j == a.M;
+    const double* __restrict__ xq = a.xq + (int64_t)q * D;
+    const double* __restrict__ gq = a.gq + (int64_t)q * D * 3;
+    const double* __restrict__ xj = self ? xq : a.xt + j * D;
+    const double* __restrict__ gj = self ? gq : a.gt + j * D * 3;
+    double* const out = self ? a.kqq + (int64_t)q * n3 * n3 : a.rows + (int64_t)q * n3 * a.ld + j * n3;
+    const int64_t out_ld = self ? n3 : a.ld;
+    if (self) {  // pad columns of this query's rows (the solve and the Gram kernel read whole 16-column groups)
+      const int64_t n = a.M * n3, npad = a.ld - n;
+      for (int64_t e = tid; e < npad * n3; e += 256) a.rows[((int64_t)q * n3 + e / npad) * a.ld + n + e % npad] = 0.0;
+    }
+    for (int p0 = 0; p0 < a.P; p0 += a.PG) {
+      const int pg = a.P - p0 < a.PG ? a.P - p0 : a.PG;
+      __syncthreads();  // the previous group's (item's) vectors are no longer read
+      // ---- per (permutation, row atom A): w_p[A], u_p[pi A], diagonal block of T_p, sum_B d_p[AB]^2
+      for (int t = wave; t < pg * N; t += 4) {
+        const int pl = t / N, A = t - pl * N;
+        const int32_t* __restrict__ pi = a.perm + (int64_t)(p0 + pl) * N;
+        const int piA = pi[A];
+        double w0 = 0, w1 = 0, w2 = 0, u0 = 0, u1 = 0, u2 = 0, nn = 0;
+        double t00 = 0, t01 = 0, t02 = 0, t10 = 0, t11 = 0, t12 = 0, t20 = 0, t21 = 0, t22 = 0;
+        for (int Bq = lane; Bq < N; Bq += 64) {
+          if (Bq == A) continue;
+          const int piB = pi[Bq];
+          const int kq = pair_idx(A, Bq), kj = pair_idx(piA, piB);
+          const double d = xq[kq] - xj[kj];
+          const double sa = A > Bq ? -1.0 : 1.0, sp = piA > piB ? -1.0 : 1.0;
+          const double g0 = sa * gq[3 * kq], g1 = sa * gq[3 * kq + 1], g2 = sa * gq[3 * kq + 2];
+          const double h0 = sp * gj[3 * kj], h1 = sp * gj[3 * kj + 1], h2 = sp * gj[3 * kj + 2];
+          w0 += g0 * d; w1 += g1 * d; w2 += g2 * d;
+          u0 += h0 * d; u1 += h1 * d; u2 += h2 * d;
+          nn += d * d;
+          t00 += g0 * h0; t01 += g0 * h1; t02 += g0 * h2;
+          t10 += g1 * h0; t11 += g1 * h1; t12 += g1 * h2;
+          t20 += g2 * h0; t21 += g2 * h1; t22 += g2 * h2;
+        }
+        w0 = wave_sum(w0); w1 = wave_sum(w1); w2 = wave_sum(w2);
+        u0 = wave_sum(u0); u1 = wave_sum(u1); u2 = wave_sum(u2);
+        nn = wave_sum(nn);
+        t00 = wave_sum(t00); t01 = wave_sum(t01); t02 = wave_sum(t02);
+        t10 = wave_sum(t10); t11 = wave_sum(t11); t12 = wave_sum(t12);
+        t20 = wave_sum(t20); t21 = wave_sum(t21); t22 = wave_sum(t22);
+        if (lane == 0) {
+          double* v = ws + (int64_t)pl * a.WS;
+          double* W = v + 3 * A;
+          double* U = v + n3 + 3 * piA;
+          double* T = v + 2 * n3 + 9 * A;
+          W[0] = w0; W[1] = w1; W[2] = w2;
+          U[0] = u0; U[1] = u1; U[2] = u2;
+          T[0] = t00; T[1] = t01; T[2] = t02; T[3] = t10; T[4] = t11; T[5] = t12; T[6] = t20; T[7] = t21; T[8] = t22;
+          v[15 * N + A] = nn;
+        }
+      }
+      __syncthreads();
+      // ---- per permutation: |d_p|^2 (every pair was counted from both of its atoms), the two coefficients
+      for (int pl = wave; pl < pg; pl += 4) {
+        double* v = ws + (int64_t)pl * a.WS;
+        double s = 0.0;
+        for (int A = lane; A < N; A += 64) s += v[15 * N + A];
+        s = wave_sum(s);
+        if (lane == 0) {
+          const double nrm = sq5 * sqrt(0.5 * s);
+          const double b = exp(-nrm / sig) / base_div * 5.0;
+          v[16 * N] = 5.0 * b;
+          v[16 * N + 1] = (sig * sig + sig * nrm) * b;
+        }
+      }
+      __syncthreads();
+      // ---- the block's elements, each summed over the group by its one owner
+      for (int e = tid; e < n3 * n3; e += 256) {
+        const int r = e / n3, c = e - r * n3;
+        const int A = r / 3, ax = r - 3 * A, ac = c / 3, axc = c - 3 * ac;
+        double acc = 0.0;
+        for (int pl = 0; pl < pg; ++pl) {
+          const double* v = ws + (int64_t)pl * a.WS;
+          const int64_t po = (int64_t)(p0 + pl) * N;
+          const int piA = a.perm[po + A];
+          double t;
+          if (ac == piA) {
+            t = v[2 * n3 + 9 * A + 3 * ax + axc];
+          } else {
+            const int Bq = a.pinv[po + ac];
+            const double sa = A > Bq ? -1.0 : 1.0, sp = ac > piA ? -1.0 : 1.0;
+            t = sa * gq[3 * pair_idx(A, Bq) + ax] * (sp * gj[3 * pair_idx(piA, ac) + axc]);
+          }
+          acc += v[16 * N] * v[r] * v[n3 + c] - v[16 * N + 1] * t;
+        }
+        double* o = out + (int64_t)r * out_ld + c;
+        *o = p0 == 0 ? a.sgn * acc : *o + a.sgn * acc;
+      }
+    }
+  }
+}
+
+// sgn * Kx of bc device-resident queries into `rows` (pitch ld) and sgn * k_qq into `kqq`
+static int cross_launch(gdml_ctx* ctx, const double* xq, const double* gq, int bc, double* rows, int64_t ld, double* kqq,
+                        double sgn, double sig) {
+  const TrainSet& ts = ctx->ts;
+  CrossArgs a;
+  a.xq = xq; a.gq = gq; a.xt = ts.x; a.gt = ts.g; a.perm = ts.perm; a.pinv = ts.pinv;
+  a.rows = rows; a.kqq = kqq; a.gws = nullptr;
+  a.ld = ld; a.M = ts.M; a.items = (int64_t)bc * (ts.M + 1);
+  a.B = bc; a.N = ts.N; a.D = ts.D; a.P = ts.P;
+  a.WS = 16 * ts.N + 2;
+  a.sig = sig; a.sgn = sgn;
+  const bool in_lds = a.WS <= UC_LDS_DOUBLES && !ctx_opt_i(ctx, "predict.cov_global", 0);
+  a.PG = in_lds ? UC_LDS_DOUBLES / a.WS : 1;
+  if (a.PG > ts.P) a.PG = ts.P;
+  int64_t grid = a.items;
+  size_t lds = 0;
+  if (in_lds) {
+    lds = (size_t)a.PG * a.WS * 8;
+    if (grid > ((int64_t)1 << 22)) grid = (int64_t)1 << 22;
+  } else {  // a few resident workgroups per CU walk the items: the workspace stays small
+    if (grid > 4 * (int64_t)ctx->num_cus) grid = 4 * (int64_t)ctx->num_cus;
+    void* p = nullptr;
+    GDML_TRY(ctx_alloc(ctx, &p, grid * a.WS * 8));
+    a.gws = (double*)p;
+  }
+  const int slot = ktime_begin(ctx);
+  hipLaunchKernelGGL(cross_rows_kernel, dim3((unsigned)grid), dim3(256), lds, ctx->stream, a);
+  ctx->launch_counter++;
+  // algorithmic work: bytes written
+  ktime_end(ctx, slot, "uncert_cross", (double)a.items * 9.0 * ts.N * (double)ts.N * 8.0);
+  hipError_t e = hipGetLastError();
+  int rc = e == hipSuccess ? GDML_OK : gdml_fail(ctx, GDML_ERR_HIP, "cross_rows launch: %s", hipGetErrorString(e));
+  if (a.gws) {
+    const int rc2 = ctx_free(ctx, a.gws);  // (synchronises the stream first)
+    if (rc == GDML_OK) rc = rc2;
+  }
+  return rc;
+}
+
+// ---- Gram step ---------------------------------------------------------------------------------------------------------
+// Sig_q = (-k_qq) - Z_q Z_q^T on the fp64 MFMA pipe.  The 3N x 3N output is cut into 64 x 64 blocks (4 x 4 MFMA tiles of
+// v_mfma_f64_16x16x4_f64); one WAVEFRONT owns (query, lower block pair (I, J), k split s): both operands are rows of Z_q and
+// come straight from global memory as 32-byte runs (lane group g = lane >> 4 feeds k = 4 g + step into MFMA step `step`, the
+// same bijection on both sides -- as in the panel solve of chol.hip), rows past 3N re-read row 3N - 1 and are never stored.
+// The pad columns [n, ld) of Z are zero, so the k loop needs no edge.  The S partial tiles of a block go to a scratch slot
+// and cov_reduce_kernel sums them in the order s = 0 .. S - 1: no atomics, bit-reproducible.  S and the split length
+// depend on n alone, and the diag_only form runs the SAME MFMA sequence for the diagonal tiles (it only leaves the others
+// out), so the marginal variances equal the diagonal of the full covariance bit for bit.
+struct GramArgs {
+  const double* Z;
+  double* part;  // full: [q][pair][s][64 x 64]; diag_only: [q][block][s][64]
+  int64_t ld, L, units;
+  int n3, nblk, npairs, S;
+};
+
+template <bool DIAG>
+__global__ void __launch_bounds__(256) cov_gram_kernel(GramArgs g) {
+  const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
+  const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (unit >= g.units) return;
+  const int s = (int)(unit % g.S);
+  const int64_t up = unit / g.S;
+  const int pr = (int)(up % g.npairs);
+  const int64_t q = up / g.npairs;
+  int I, J;
+  if (DIAG) {
+    I = J = pr;
+  } else {
+    I = (int)((sqrt(8.0 * (double)pr + 1.0) - 1.0) * 0.5);
+    while (I * (I + 1) / 2 > pr) --I;
+    while ((I + 1) * (I + 2) / 2 <= pr) ++I;
+    J = pr - I * (I + 1) / 2;
+  }
+  const int64_t k_beg = (int64_t)s * g.L;
+  const int64_t k_end = k_beg + g.L < g.ld ? k_beg + g.L : g.ld;
+  const double* pa[4];
+  const double* pb[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    int ra = I * 64 + 16 * i + li, rb = J * 64 + 16 * i + li;
+    ra = ra < g.n3 ? ra : g.n3 - 1;
+    rb = rb < g.n3 ? rb : g.n3 - 1;
+    pa[i] = g.Z + (q * g.n3 + ra) * g.ld + 4 * lk;
+    pb[i] = g.Z + (q * g.n3 + rb) * g.ld + 4 * lk;
+  }
+  d4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
+  for (int64_t k0 = k_beg; k0 < k_end; k0 += 16) {
+    d4 av[4], bv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) av[i] = *reinterpret_cast<const d4*>(pa[i] + k0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bv[i] = DIAG ? av[i] : *reinterpret_cast<const d4*>(pb[i] + k0);
+#pragma unroll
+    for (int st = 0; st < 4; ++st)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (!DIAG || i == j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i][st], bv[j][st], acc[i][j], 0, 0, 0);
+  }
+  // f64 MFMA C/D layout: col = lane & 15, row = (lane >> 4) + 4 r
+  if (DIAG) {
+    double* o = g.part + ((q * g.nblk + I) * g.S + s) * 64;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (li == lk + 4 * r) o[16 * i + li] = acc[i][i][r];
+  } else {
+    double* o = g.part + ((q * g.npairs + pr) * g.S + s) * 4096;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[(16 * i + lk + 4 * r) * 64 + 16 * j + li] = acc[i][j][r];
+  }
+}
+
+// out = sym(-k_qq) - sum_s partial_s (fixed order).  Full form: both triangles from the lower block pairs; diag_only: (B,3N).
+__global__ void __launch_bounds__(256) cov_reduce_kernel(const double* __restrict__ part, const double* __restrict__ nkqq,
+                                                         double* __restrict__ out, int n3, int nblk, int npairs, int S,
+                                                         int full, int64_t total) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  if (full) {
+    const int64_t q = t / ((int64_t)n3 * n3);
+    const int e = (int)(t - q * n3 * n3), r = e / n3, c = e - r * n3;
+    const int rr = r > c ? r : c, cc = r > c ? c : r;
+    const int I = rr >> 6, J = cc >> 6;
+    const double* p = part + ((q * npairs + I * (I + 1) / 2 + J) * S) * 4096 + (rr & 63) * 64 + (cc & 63);
+    double acc = 0.0;
+    for (int s = 0; s < S; ++s) acc += p[(int64_t)s * 4096];
+    const double* k = nkqq + q * n3 * n3;
+    out[t] = 0.5 * (k[rr * n3 + cc] + k[cc * n3 + rr]) - acc;
+  } else {
+    const int64_t q = t / n3;
+    const int r = (int)(t - q * n3);
+    const double* p = part + ((q * nblk + (r >> 6)) * S) * 64 + (r & 63);
+    double acc = 0.0;
+    for (int s = 0; s < S; ++s) acc += p[(int64_t)s * 64];
+    const double kd = nkqq[q * n3 * n3 + (int64_t)r * n3 + r];
+    out[t] = 0.5 * (kd + kd) - acc;
+  }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+static int uncert_check_queries(gdml_ctx* ctx, const char* who, const double* R, int64_t B, const double* lat,
+                                const double* lat_inv) {
+  if (!R) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: R is NULL", who);
+  if (B < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: B < 0", who);
+  if ((lat == nullptr) != (lat_inv == nullptr))
+    return gdml_fail(ctx, GDML_ERR_INVALID, "lattice and inverse must both be given or both NULL");
+  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "%s: call gdml_train_upload first", who);
+  return GDML_OK;
+}
+
+// Work buffers of one batch chunk.  The Gram split (S, L) depends on n alone.
+struct UncertPlan {
+  int N, n3, D, nblk, npairs, S;
+  int64_t n, ld, L, per_query, bc;
+  double *R, *xq, *gq, *nkqq, *part, *out, *rows;
+};
+
+// The solve runs on whole 128-row tiles (zero rows behind the last query): an interior tile of the trailing update and an
+// edge tile round differently (chol.hip: acc = -C first vs C - acc last), and which of the two a query's rows meet must not
+// depend on how the batch was cut into chunks.
+static inline int64_t uc_pad_rows(int64_t rows) { return (rows + 127) / 128 * 128; }
+
+static int uncert_plan(gdml_ctx* ctx, int64_t B, bool need_gram, UncertPlan* p) {
+  const TrainSet& ts = ctx->ts;
+  p->N = ts.N; p->n3 = 3 * ts.N; p->D = ts.D;
+  p->n = ts.M * p->n3;
+  p->ld = (p->n + 15) / 16 * 16;
+  p->nblk = (p->n3 + 63) / 64;
+  p->npairs = p->nblk * (p->nblk + 1) / 2;
+  p->S = (int)((p->n + 1023) / 1024);
+  if (p->S > 32) p->S = 32;
+  if (p->S < 1) p->S = 1;
+  p->L = ((p->ld + p->S - 1) / p->S + 15) / 16 * 16;
+  p->S = (int)((p->ld + p->L - 1) / p->L);  // no empty split
+  const int64_t n3 = p->n3;
+  const int64_t small = n3 + 4 * (int64_t)p->D + 2 * n3 * n3 + (need_gram ? (int64_t)p->npairs * p->S * 4096 : 0);
+  p->per_query = (n3 * p->ld + small) * 8;
+  // chunk of the batch: the option's cap (default 64 geometries -- 2 GB of rows at n = 63 000), less when free memory is short
+  int64_t bc = ctx_opt_i(ctx, "predict.cov_chunk", 64);
+  if (bc < 1) bc = 1;
+  if (bc > B) bc = B;
+  size_t f = 0, t = 0;
+  HIP_CHECK(ctx, hipMemGetInfo(&f, &t));
+  const int64_t have = (int64_t)f + ctx->slot_bytes[UC_SLOT_WS] + ctx->slot_bytes[UC_SLOT_ROWS];
+  while (bc > 1 && bc * p->per_query + 127 * p->ld * 8 > have / 10 * 9) bc = (bc + 1) / 2;
+  p->bc = bc;
+  double* ws;
+  GDML_TRY(ctx_slot(ctx, UC_SLOT_ROWS, uc_pad_rows(bc * n3) * p->ld * 8, &p->rows));
+  GDML_TRY(ctx_slot(ctx, UC_SLOT_WS, bc * small * 8, &ws));
+  p->R = ws;
+  p->xq = p->R + bc * n3;
+  p->gq = p->xq + bc * p->D;
+  p->nkqq = p->gq + 3 * bc * p->D;
+  p->out = p->nkqq + bc * n3 * n3;
+  p->part = p->out + bc * n3 * n3;
+  return GDML_OK;
+}
+
+extern "C" int gdml_uncert_prepare(gdml_ctx* ctx, double sig, double lam, int* info) {
+  if (!ctx) return GDML_ERR_INVALID;
+  if (info) *info = 0;
+  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_uncert_prepare: call gdml_train_upload first");
+  if (comm_active(ctx) && ctx->world > 1)
+    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_uncert_prepare: the factor of a multi-rank context is distributed");
+  ctx->uncert_ready = false;
+  GDML_TRY(gdml_assemble_A(ctx, sig, lam, 0, 0));
+  GDML_TRY(gdml_chol_factor(ctx, lam, info));
+  ctx->uncert_ready = true;
+  return GDML_OK;
+}
+
+extern "C" int gdml_uncert_release(gdml_ctx* ctx) {
+  if (!ctx) return GDML_ERR_INVALID;
+  HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ctx->uncert_ready = false;
+  for (int s : {UC_SLOT_WS, UC_SLOT_ROWS}) {
+    if (ctx->slot[s]) GDML_TRY(ctx_free(ctx, ctx->slot[s]));
+    ctx->slot[s] = nullptr;
+    ctx->slot_bytes[s] = 0;
+  }
+  if (ctx->K) {
+    GDML_TRY(ctx_free(ctx, ctx->K));
+    ctx->K = nullptr;
+    ctx->K_bytes = 0;
+    ctx->K_rows = ctx->K_cols = ctx->K_extra = ctx->K_ld = 0;
+    ctx->K_factored = false;
+    ctx->K_rhs_row = false;
+    ctx->precon = nullptr;
+    precon_release_aux(ctx);
+  }
+  return GDML_OK;
+}
+
+extern "C" int gdml_uncert_cross(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv,
+                                 double* Kx_out, double* kqq_out) {
+  if (!ctx) return GDML_ERR_INVALID;
+  GDML_TRY(uncert_check_queries(ctx, "gdml_uncert_cross", R, B, lat, lat_inv));
+  if (ctx->K_sig <= 0 && !(ctx->model.sig > 0))
+    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_uncert_cross: no length scale known (gdml_uncert_prepare or a model upload sets it)");
+  if (B == 0) return GDML_OK;
+  HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const double sig = ctx->uncert_ready || ctx->K_sig > 0 ? ctx->K_sig : ctx->model.sig;
+  UncertPlan p;
+  GDML_TRY(uncert_plan(ctx, B, false, &p));
+  const int64_t n3 = p.n3;
+  for (int64_t b0 = 0; b0 < B; b0 += p.bc) {
+    const int bc = (int)(B - b0 < p.bc ? B - b0 : p.bc);
+    HIP_CHECK(ctx, hipMemcpyAsync(p.R, R + b0 * n3, bc * n3 * 8, hipMemcpyHostToDevice, ctx->stream));
+    GDML_TRY(desc_device(ctx, p.R, bc, p.N, lat, lat_inv, p.xq, p.gq));
+    GDML_TRY(cross_launch(ctx, p.xq, p.gq, bc, p.rows, p.ld, p.nkqq, 1.0, sig));
+    if (Kx_out)
+      HIP_CHECK(ctx, hipMemcpy2DAsync(Kx_out + b0 * n3 * p.n, p.n * 8, p.rows, p.ld * 8, p.n * 8, bc * n3,
+                                      hipMemcpyDeviceToHost, ctx->stream));
+    if (kqq_out)
+      HIP_CHECK(ctx, hipMemcpyAsync(kqq_out + b0 * n3 * n3, p.nkqq, bc * n3 * n3 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return GDML_OK;
+}
+
+static int cov_common(gdml_ctx* ctx, const double* R, bool on_device, int64_t B, const double* lat, const double* lat_inv,
+                      int full, double* cov_out) {
+  GDML_TRY(uncert_check_queries(ctx, "gdml_predict_cov", R, B, lat, lat_inv));
+  if (!cov_out) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_cov: cov_out is NULL");
+  if (ctx->K && ctx->K_factored && ctx->K_use_E)
+    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_predict_cov: the resident factor carries energy-constraint rows");
+  if (!ctx->uncert_ready || !ctx->K || !ctx->K_factored)
+    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_predict_cov: no factor prepared (gdml_uncert_prepare; an assembly since then overwrote it)");
+  if (B == 0) return GDML_OK;
+  HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  UncertPlan p;
+  GDML_TRY(uncert_plan(ctx, B, true, &p));
+  if (ctx->K_rows != p.n || ctx->K_ld != p.ld)
+    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_predict_cov: the resident factor does not belong to the resident training set");
+  const int64_t n3 = p.n3, per_out = full ? n3 * n3 : n3;
+  phase_begin(ctx);
+  for (int64_t b0 = 0; b0 < B; b0 += p.bc) {
+    const int bc = (int)(B - b0 < p.bc ? B - b0 : p.bc);
+    const double* d_R = R + b0 * n3;
+    if (!on_device) {
+      HIP_CHECK(ctx, hipMemcpyAsync(p.R, R + b0 * n3, bc * n3 * 8, hipMemcpyHostToDevice, ctx->stream));
+      d_R = p.R;
+    }
+    GDML_TRY(desc_device(ctx, d_R, bc, p.N, lat, lat_inv, p.xq, p.gq));
+    GDML_TRY(cross_launch(ctx, p.xq, p.gq, bc, p.rows, p.ld, p.nkqq, -1.0, ctx->K_sig));
+    // Z = (-Kx) L^-T.  Right-looking: the rows are few and the factor is long, so every 512-column step updates the whole
+    // remaining width in one launch that fills the chip (the left-looking form of the Nystroem build would run 4 tiles deep
+    // products per 128 rows)
+    const int64_t rows = (int64_t)bc * n3, rows_pad = uc_pad_rows(rows);
+    if (rows_pad > rows)
+      HIP_CHECK(ctx, hipMemsetAsync(p.rows + rows * p.ld, 0, (rows_pad - rows) * p.ld * 8, ctx->stream));
+    int slot = ktime_begin(ctx);
+    GDML_TRY(tall_trsm(ctx, ctx->K, p.rows, rows_pad, p.n, p.ld, 0));
+    ktime_end(ctx, slot, "uncert_solve", (double)p.n * (double)p.n * (double)n3 * bc);
+    GramArgs g;
+    g.Z = p.rows; g.part = p.part; g.ld = p.ld; g.L = p.L; g.n3 = p.n3; g.nblk = p.nblk; g.S = p.S;
+    g.npairs = full ? p.npairs : p.nblk;
+    g.units = (int64_t)bc * g.npairs * g.S;
+    slot = ktime_begin(ctx);
+    if (full)
+      hipLaunchKernelGGL(cov_gram_kernel<false>, dim3((unsigned)ceil_div(g.units, 4)), dim3(256), 0, ctx->stream, g);
+    else
+      hipLaunchKernelGGL(cov_gram_kernel<true>, dim3((unsigned)ceil_div(g.units, 4)), dim3(256), 0, ctx->stream, g);
+    double* d_out = on_device ? cov_out + b0 * per_out : p.out;
+    const int64_t total = bc * per_out;
+    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, p.part, p.nkqq, d_out,
+                       p.n3, p.nblk, p.npairs, p.S, full, total);
+    ctx->launch_counter += 2;
+    ktime_end(ctx, slot, "uncert_gram", 2.0 * (double)p.ld * (full ? (double)n3 * n3 : (double)n3) * bc);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return gdml_fail(ctx, GDML_ERR_HIP, "cov_gram launch: %s", hipGetErrorString(e));
+    if (!on_device) {
+      HIP_CHECK(ctx, hipMemcpyAsync(cov_out + b0 * per_out, p.out, total * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+  }
+  GDML_TRY(phase_end(ctx, "uncert"));
+  return GDML_OK;
+}
+
+extern "C" int gdml_predict_cov(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv, int full,
+                                double* cov_out) {
+  if (!ctx) return GDML_ERR_INVALID;
+  return cov_common(ctx, R, false, B, lat, lat_inv, full, cov_out);
+}
+
+extern "C" int gdml_predict_cov_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat, const double* lat_inv,
+                                    int full, double* cov_dev) {
+  if (!ctx) return GDML_ERR_INVALID;
+  return cov_common(ctx, R_dev, true, B, lat, lat_inv, full, cov_dev);
+}

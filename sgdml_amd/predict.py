@@ -87,6 +87,13 @@ class GDMLPredict(object):
         self._min_shard_hessian = 4  # the same for predict_hessian (one Hessian is the arithmetic of ~10 predictions)
         self._train_resident = False
 
+        # posterior covariances (prepare_uncertainty): what the factorisation needs beyond the prediction tables
+        self._R_desc_train = R_desc_train
+        self._lam = float(model['lam']) if 'lam' in model else None
+        self._use_E_cstr = bool(model['use_E_cstr']) if 'use_E_cstr' in model else 'alphas_E' in model
+        self._alphas_F = np.asarray(model['alphas_F'], dtype=np.float64).ravel() if 'alphas_F' in model else None
+        self.uncertainty_scale = 1.0
+
     def __del__(self):
         for ctx in getattr(self, '_replicas', []):
             ctx.close()
@@ -218,6 +225,66 @@ class GDMLPredict(object):
         F *= self.std
         H *= self.std
         return E, F, H
+
+    # ---- posterior force covariance (csrc/uncert.hip)
+
+    def prepare_uncertainty(self, R_train, F_train=None):
+        """Build what predict_uncertainty() needs, once: the system matrix A = -K + lam I of the training set is assembled
+        and factored on the first GPU (the fp64-MFMA Cholesky of the analytic solver) and the n x n factor, n = 3N M, STAYS
+        RESIDENT there until release_uncertainty().  Models trained by the iterative solver are accepted as well: the factor
+        is built from scratch, so whether n^2 * 8 bytes fit in HBM is the only limit (MemoryError otherwise;
+        numpy.linalg.LinAlgError for a matrix that is not positive definite, as in the analytic solver).
+
+        R_train (M,3N): the Cartesian training geometries in the model's order.  A model file holds only their descriptors,
+        so they are checked against model['R_desc'] (rtol 1e-10) and a mismatch raises ValueError.
+
+        Calibration: a Gaussian process fixes its covariance only up to the signal variance s^2.  Without F_train s^2 = 1 and
+        ONLY THE RANKING of geometries by their variances is meaningful, not the magnitudes.  With F_train (M,3N), the labels
+        the model was trained on, s^2 is the maximum-likelihood value y^T A^-1 y / n = -(y . alphas_F) / n, y =
+        F_train.ravel() / std (needs model['alphas_F']); it is stored as `uncertainty_scale` and multiplies every covariance."""
+        if self._use_E_cstr:
+            raise NotImplementedError('posterior covariances of models with energy constraints are not supported')
+        if self._lam is None:
+            raise ValueError("the model carries no regularisation strength 'lam'")
+        n3 = 3 * self.n_atoms
+        R_train = np.asarray(R_train, dtype=np.float64)
+        if R_train.size != self.n_train * n3:
+            raise ValueError('R_train holds {} values, the model was trained on {} geometries of {} atoms'.format(
+                R_train.size, self.n_train, self.n_atoms))
+        R_train = R_train.reshape(self.n_train, n3)
+        xd, gd = self._ctx.desc_from_R(R_train, self.n_atoms, self.lat_and_inv)
+        if not np.allclose(xd, self._R_desc_train, rtol=1e-10, atol=0.0):
+            raise ValueError("R_train does not reproduce the model's training descriptors (wrong geometries or order)")
+        scale = 1.0
+        if F_train is not None:
+            if self._alphas_F is None:
+                raise ValueError("calibration needs the model's 'alphas_F'")
+            y = np.asarray(F_train, dtype=np.float64).ravel() / self.std
+            if y.size != self._alphas_F.size:
+                raise ValueError('F_train holds {} values, the model has {} coefficients'.format(y.size, self._alphas_F.size))
+            scale = float(-np.dot(y, self._alphas_F) / y.size)
+        self._ctx.train_upload(xd, gd, self._tril_perms)
+        self._train_resident = False  # the training-set mode uploads its own descriptors again when it is used next
+        self._ctx.uncert_prepare(self.sig, self._lam)
+        self.uncertainty_scale = scale
+
+    def release_uncertainty(self):
+        """Free the resident factor of prepare_uncertainty()."""
+        self._ctx.uncert_release()
+
+    def predict_uncertainty(self, R, full_cov=False):
+        """(E, F, var) for geometries R (B,3N) or (3N,): E, F as predict(R); var (B,3N) the marginal posterior variances of
+        the force components, or with full_cov the (B,3N,3N) posterior covariances, in the units of F squared (std^2 times
+        `uncertainty_scale`: see prepare_uncertainty on what the magnitudes mean without calibration).  Runs on the first GPU
+        only; set_alphas() does not invalidate the factor (it depends on the training geometries, sig and lam alone)."""
+        R = np.asarray(R, dtype=np.float64)
+        if R.ndim == 1:
+            R = R[None, :]
+        R = R.reshape(R.shape[0], -1)
+        cov = self._ctx.predict_cov(R, self.lat_and_inv, full=full_cov)
+        E, F = self.predict(R)
+        cov *= self.std * self.std * self.uncertainty_scale
+        return E, F, cov
 
     def predict(self, R=None, return_E=True):
         """Energies (B,) and forces (B,3N) for geometries R (B,3N); R=None -> training-set mode."""
