@@ -15,11 +15,28 @@
 // costs 2 FMAs per permutation and the kernel is bound by the HBM write of K (8 (3N)^2 bytes per
 // block).
 //
-// The kernels live in their own files: assemble_strip.hip (P = 1, 11 <= N <= 21, all columns: the benchmark path),
-// assemble_wave.hip (P = 1, N <= 21: column subsets, row-cyclic shares), assemble_pts.hip (8 <= N <= 24 with a permutation
-// group, dense columns), assemble_perm.hip (everything else: any group, any N).  This file resolves the
-// column selection (train.py:1335-1407), owns the matrix buffer, dispatches, and carries the energy-constraint columns.
-#include "common.h"
+// This file resolves the column selection (train.py:1335-1407), owns the matrix buffer, routes the request (AsmJob,
+// assemble.h) to one of the six kernels, and carries the energy-constraint columns, a separate step behind them.
+//
+// ROUTING.  assemble_dispatch walks the table below in order and launches the first kernel whose <k>_accepts(ctx, job)
+// holds; a launch that answers GDML_ERR_UNSUPPORTED (no LDS layout, no memory for a plan) passes the job on to the next.
+// This is the one place that states the order; the conditions are the accepts() of each file, in short:
+//   1 assemble_strip  P = 1 (identity), 11 <= N <= 21; the whole matrix only: every column, every row point, no E rows,
+//                     plain layout (W = 0); K or the lower form.  The benchmark path.                           asm.strip
+//   2 assemble_wave   P = 1 (identity), N <= 21; everything: ranges, index lists, row shards, E rows, the lower form, the
+//                     block-row-cyclic layout (its cyclic instantiation also for W = 1).                        asm.wave
+//   3 assemble_pts    8 <= N <= 24 with a group (P > 1; asm.pts = 2: also P = 1); dense ranges, E rows allowed, plain rows.
+//   4 assemble_big1   P = 1, 22 <= N <= 256; dense ranges, no E rows, plain rows.                               asm.big1
+//   5 assemble_perm2  P >= 6 on 36 <= N <= 42 (groups below 16 from 40 atoms; asm.perm2_min_n / _min_p); dense ranges or
+//                     index lists of whole points in list order (not in the lower form), no E rows, plain rows. asm.perm2
+//   6 assemble_perm   everything: any group, any N, any selection, E rows, the lower form, the cyclic layout for W > 1.
+// "Plain rows" is W <= 1: one rank of the cyclic layout stores every row where the plain layout does.  The lower form
+// (A = -K + lam I, blocks j <= i) exists only for the dense full range over all row points without E rows; 3 and 6 refuse
+// anything else in that form with GDML_ERR_INVALID, 4 and 5 do not accept it (so 6 refuses it), and 6 refuses a cyclic
+// layout whose row blocks are shorter than 3N with GDML_ERR_UNSUPPORTED.
+// Who asks: gdml_assemble_K / gdml_assemble_A with the plain layout (lower where the analytic solve wants A and the request
+// is the whole force matrix, option asm.lower), gdml_dist_chol_solve (dist_chol.hip) with lower = 1 and its layout.
+#include "assemble.h"
 
 __device__ __forceinline__ double block_sum(double v, double* red, int tid, int nwaves) {
   v = wave_sum(v);
@@ -195,7 +212,7 @@ static int ecol_launch(gdml_ctx* ctx, double sig, const int32_t* d_ep, const int
   E.row_mode = row_mode; E.lam = lam;
   if (i_end < 0) i_end = M;
   E.i_beg = row_mode ? 0 : i_beg;
-  E.e_row0 = (i_beg == 0 && i_end == M) ? M * N3 : (i_end - i_beg) * N3 - i_beg;
+  E.e_row0 = asm_e_row0(M, N, i_beg, i_end);
   // two outputs per thread and the descriptor tables in LDS, or (large molecules) the table-free kernel
   const bool small = N3 <= 512 && (size_t)(2 * ts.D + 32) * 8 <= (size_t)160 * 1024;
   const size_t lds = small ? (size_t)(2 * ts.D + 32) * 8 : (size_t)(ts.P + 32) * 8;
@@ -246,15 +263,29 @@ int assemble_erows_cyclic_launch(gdml_ctx* ctx, double sig, double lam, double* 
   return rc;
 }
 
-// Rows of A = -K + lam I owned by this rank in the block-row-cyclic layout of the distributed Cholesky (any P,
-// any N): full column range, lower blocks.  K: the rank's local matrix.
-int assemble_cyclic_launch(gdml_ctx* ctx, double sig, double lam, double* K, int64_t ld, int cyc_W, int cyc_rank,
-                           int cyc_nb) {
-  TrainSet& ts = ctx->ts;
-  if (assemble_wave_applicable(ctx))
-    return assemble_wave_launch(ctx, sig, 0, nullptr, nullptr, 0, ts.M, K, ld, 0, ts.M, 1, lam, cyc_W, cyc_rank, cyc_nb);
-  return assemble_perm_launch(ctx, sig, 0, nullptr, nullptr, 0, ts.M, 0, K, ld, 0, ts.M, 1, lam, cyc_W > 1 ? cyc_W : 0,
-                              cyc_rank, cyc_nb);
+// The routing table (header comment): first kernel that accepts, in this order.
+static const struct {
+  bool (*accepts)(const gdml_ctx*, const AsmJob&);
+  int (*launch)(gdml_ctx*, const AsmJob&);
+} asm_table[] = {
+    {assemble_strip_accepts, assemble_strip_launch},  // whole matrix, P = 1, 11 <= N <= 21
+    {assemble_wave_accepts, assemble_wave_launch},    // P = 1, N <= 21
+    {assemble_pts_accepts, assemble_pts_launch},      // groups on 8 <= N <= 24, dense ranges
+    {assemble_big1_accepts, assemble_big1_launch},    // P = 1, 22 <= N <= 256, dense ranges
+    {assemble_perm2_accepts, assemble_perm2_launch},  // large groups on 36 <= N <= 42, whole column points
+    {assemble_perm_accepts, assemble_perm_launch},    // everything
+};
+
+int assemble_dispatch(gdml_ctx* ctx, const AsmJob& job) {
+  if (job.n_j <= 0 || job.i_end <= job.i_beg) return GDML_OK;
+  GDML_TRY(build_dense_tables(ctx));  // every kernel but assemble_big1 reads them or packs its own tables from them
+  int rc = GDML_ERR_UNSUPPORTED;
+  for (const auto& k : asm_table) {
+    if (!k.accepts(ctx, job)) continue;
+    rc = k.launch(ctx, job);
+    if (rc != GDML_ERR_UNSUPPORTED) break;
+  }
+  return rc;  // the last kernel accepts everything: an UNSUPPORTED that ends here is its own, message set
 }
 
 // as_A: assemble for the analytic solve (gdml_assemble_A): where the register-resident kernel applies the
@@ -396,22 +427,16 @@ static int assemble_impl(gdml_ctx* ctx, double sig, int use_E_cstr, int col_kind
                                   ctx->stream));
   }
 
+  AsmJob job;
+  job.sig = sig; job.use_E = use_E_cstr;
+  job.j0 = j0; job.n_j = n_j;
+  job.d_jlist = d_jlist; job.d_colmap = d_colmap; job.h_colmap = dense ? nullptr : colmap.data();
+  job.i_beg = i_beg; job.i_end = i_end;
+  job.K = ctx->K; job.ld = ld;
+  job.lower = lower_A ? 1 : 0; job.lam = lower_A ? lam : 0.0;
+
   phase_begin(ctx);
-  int rc = GDML_OK;
-  if (n_j > 0) {
-    if (i_end <= i_beg)
-      rc = GDML_OK;
-    else if (lower_A && !assemble_wave_applicable(ctx))
-      rc = assemble_cyclic_launch(ctx, sig, lam, ctx->K, ld, 1, 0, 512);
-    else if (dense && !use_E_cstr && i_beg == 0 && i_end == M && assemble_strip_applicable(ctx))
-      rc = assemble_strip_launch(ctx, sig, ctx->K, ld, lower_A ? 1 : 0, lam);
-    else if (assemble_wave_applicable(ctx))
-      rc = assemble_wave_launch(ctx, sig, use_E_cstr, d_jlist, d_colmap, j0, n_j, ctx->K, ld, i_beg, i_end,
-                                lower_A ? 1 : 0, lam);
-    else
-      rc = assemble_perm_launch(ctx, sig, use_E_cstr, d_jlist, d_colmap, j0, n_j, 0, ctx->K, ld, i_beg, i_end, 0, 0.0, 0, 0, 0,
-                                dense ? nullptr : colmap.data());
-  }
+  int rc = assemble_dispatch(ctx, job);
   if (rc == GDML_OK && !e_pts.empty()) {
     if (i_end > i_beg) rc = ecol_launch(ctx, sig, d_ep, d_ec, (int64_t)e_pts.size(), ctx->K, ld, 0, 0.0, i_beg, i_end);
   }

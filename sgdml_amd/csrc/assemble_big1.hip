@@ -21,7 +21,7 @@
 //            forms its column's three entries (one per row of the atom) from u_a, w_b (LDS) and the pair's Jacobian entries:
 //            every store instruction writes 512 contiguous bytes of one matrix row.
 // lower != 0: A = -K + lam I for the analytic solve, blocks j <= i only (gdml_assemble_A).
-#include "common.h"
+#include "assemble.h"
 
 namespace {
 
@@ -212,21 +212,22 @@ __global__ void __launch_bounds__(256) assemble_big1_kernel(Big1Args A) {
 
 }  // namespace
 
-bool assemble_big1_applicable(const gdml_ctx* ctx) {
+// P = 1, 22 <= N <= 256: dense column ranges, any rows, no E rows, plain layout; the lower form over the full range
+bool assemble_big1_accepts(const gdml_ctx* ctx, const AsmJob& job) {
   const TrainSet& ts = ctx->ts;
+  if (asm_has_lists(job) || job.use_E || !asm_plain_rows(job) || (job.lower && !asm_full_dense(ctx, job))) return false;
   return ctx_opt_i(ctx, "asm.big1", 1) != 0 && ts.P == 1 && ts.N >= 22 && ts.N <= 256;
 }
 
-// Column points [j0, j0 + n_j) written at col0 + 3N v, row points [i_beg, i_end); lower: A = -K + lam I, blocks j <= i of
+// Column points [j0, j0 + n_j) written at 3N v, row points [i_beg, i_end); lower: A = -K + lam I, blocks j <= i of
 // the whole matrix (j0 = i_beg = 0, n_j = i_end = M).
-int assemble_big1_launch(gdml_ctx* ctx, double sig, int64_t j0, int64_t n_j, int64_t col0, double* K, int64_t ld, int64_t i_beg,
-                         int64_t i_end, int lower, double lam) {
+int assemble_big1_launch(gdml_ctx* ctx, const AsmJob& job) {
   TrainSet& ts = ctx->ts;
-  if (n_j <= 0 || i_end <= i_beg) return GDML_OK;
+  const int lower = job.lower ? 1 : 0;
+  const int64_t n_j = job.n_j, n_i = job.i_end - job.i_beg;
   Big1Args A;
-  A.x = ts.x; A.g = ts.g; A.M = ts.M; A.N = ts.N; A.D = ts.D; A.sig = sig; A.lam = lam;
-  A.j0 = j0; A.n_j = n_j; A.col0 = col0; A.i_beg = i_beg; A.i_end = i_end; A.lower = lower; A.K = K; A.ld = ld;
-  const int64_t n_i = i_end - i_beg;
+  A.x = ts.x; A.g = ts.g; A.M = ts.M; A.N = ts.N; A.D = ts.D; A.sig = job.sig; A.lam = job.lam;
+  A.j0 = job.j0; A.n_j = n_j; A.col0 = 0; A.i_beg = job.i_beg; A.i_end = job.i_end; A.lower = lower; A.K = job.K; A.ld = job.ld;
   int64_t blocks = 0;
   if (lower) {
     for (int64_t r = 0; r < n_i; ++r) blocks += (r + 1 + BIG1_J - 1) / BIG1_J;
@@ -243,7 +244,7 @@ int assemble_big1_launch(gdml_ctx* ctx, double sig, int64_t j0, int64_t n_j, int
     (void)hipFuncSetAttribute((const void*)assemble_big1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int slot = ktime_begin(ctx);
   hipLaunchKernelGGL(assemble_big1_kernel, dim3((unsigned)blocks), dim3(256), lds, ctx->stream, A);
-  ktime_end(ctx, slot, "assemble", 8.0 * (lower ? 0.5 * (double)n_i * (double)(n_i + 1) : (double)n_i * (double)n_j) * 9.0 * ts.N * ts.N);
+  ktime_end(ctx, slot, "assemble", asm_bytes(ts.N, lower, n_i, n_j));
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
   return GDML_OK;

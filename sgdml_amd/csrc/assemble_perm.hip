@@ -27,7 +27,7 @@
 // table (GJS), its x_j tables (JX) -- otherwise through L1/L2 from the dense tables (any N up to GDML_MAX_ATOMS;
 // more than 8 NA row atoms take several rounds).  Permutation rows are held one entry per lane and read with
 // v_readlane (wave-uniform index), so no inner loop has an index load in its dependency chain.
-#include "common.h"
+#include "assemble.h"
 #include <type_traits>
 
 struct PermArgs {
@@ -727,8 +727,6 @@ __global__ void __launch_bounds__(64 * W, 2) assemble_perm_kernel(PermArgs A) {
   }
 }
 
-int build_dense_tables(gdml_ctx* ctx);
-
 // LDS layout for one choice of what is resident; returns the byte size
 static size_t perm_layout(int N, int P, int W, int NA, int n_img, bool gjs, bool jx, int PG, PermArgs* A, int nq = 0) {
   const int NN = N * N;
@@ -766,48 +764,32 @@ static void perm_launch_t(gdml_ctx* ctx, const PermArgs& A, dim3 grid, size_t ld
   hipLaunchKernelGGL((assemble_perm_kernel<W, NA, IMG, GJS, JX, BIG>), grid, dim3(64 * W), lds, ctx->stream, A);
 }
 
+// The general kernel: any group, any N, any column selection, any rows, E rows, both forms, both layouts.
+bool assemble_perm_accepts(const gdml_ctx*, const AsmJob&) { return true; }
+
 // Launch over the column points [0, n_j) of (jlist | j0 + v) and the row points [i_beg, i_end).
-int assemble_perm_launch(gdml_ctx* ctx, double sig, int use_E, const int32_t* d_jlist, const int32_t* d_colmap, int64_t j0,
-                         int64_t n_j, int64_t col0, double* K, int64_t ld, int64_t i_beg, int64_t i_end, int lower, double lam,
-                         int cyc_W, int cyc_rank, int cyc_nb, const int32_t* h_colmap) {
+int assemble_perm_launch(gdml_ctx* ctx, const AsmJob& job) {
   TrainSet& ts = ctx->ts;
-  if (n_j <= 0 || i_end <= i_beg) return GDML_OK;
-  // small molecules, whole column points, plain row layout: the producer / consumer kernel of assemble_pts.hip
-  if (!d_jlist && !d_colmap && col0 == 0 && cyc_W == 0 && assemble_pts_applicable(ctx)) {
-    const int rc = assemble_pts_launch(ctx, sig, use_E, j0, n_j, K, ld, i_beg, i_end, lower, lam);
-    if (rc != GDML_ERR_UNSUPPORTED) return rc;  // no LDS layout for this (N, P): the general kernel below
-  }
-  GDML_TRY(build_dense_tables(ctx));
+  const int use_E = job.use_E, lower = job.lower;
+  const int32_t *d_jlist = job.d_jlist, *d_colmap = job.d_colmap, *h_colmap = job.h_colmap;
+  const int64_t n_j = job.n_j, i_beg = job.i_beg, i_end = job.i_end;
+  const int cyc_W = asm_plain_rows(job) ? 0 : job.W;  // one rank: the plain instantiation
   const int N = ts.N, P = ts.P;
-  if ((lower || cyc_W > 0) && (d_jlist || d_colmap || use_E || j0 != 0 || i_beg != 0 || n_j != ts.M || i_end != ts.M))
+  if ((lower || cyc_W > 0) && !asm_full_dense(ctx, job))
     return gdml_fail(ctx, GDML_ERR_INVALID, "assemble_perm: the lower form needs the dense full column range");
-  if (cyc_W > 0 && 3 * N > cyc_nb)
-    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "assemble_perm: row-cyclic layout needs 3N <= %d", cyc_nb);
-  // no permutation group, more than 21 atoms, dense column range, plain layout: the direct P = 1 kernel of assemble_big1.hip
-  if (!d_jlist && !d_colmap && !use_E && cyc_W == 0 && assemble_big1_applicable(ctx))
-    return assemble_big1_launch(ctx, sig, j0, n_j, col0, K, ld, i_beg, i_end, lower ? 1 : 0, lam);
-  // 25 ... 42 atoms, plain layout: the MFMA / fixed-atom-split kernel of assemble_perm2.hip -- dense column ranges, and
-  // (round 6) index lists that request WHOLE column points in list order (every column of each listed point, output column
-  // 3N v + c: what the iterative solver's K_nm is, iterative.py:229-247 -- configs[3] spent 0.69 s per build on the general
-  // kernel for it)
-  bool whole_points = d_jlist != nullptr && d_colmap != nullptr && h_colmap != nullptr && col0 == 0 && !lower;
-  if (whole_points)
-    for (int64_t e = 0; e < n_j * 3 * N && whole_points; ++e) whole_points = h_colmap[e] == (int32_t)e;
-  if (((!d_jlist && !d_colmap) || whole_points) && !use_E && cyc_W == 0 && assemble_perm2_applicable(ctx)) {
-    const int rc = assemble_perm2_launch(ctx, sig, j0, n_j, col0, K, ld, i_beg, i_end, lower ? 1 : 0, lam, whole_points ? d_jlist : nullptr);
-    if (rc != GDML_ERR_UNSUPPORTED) return rc;
-  }
+  if (cyc_W > 0 && 3 * N > job.nb)
+    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "assemble_perm: row-cyclic layout needs 3N <= %d", job.nb);
   PermArgs A;
   memset(&A, 0, sizeof(A));
   A.XF = ts.XF; A.GD = ts.GD; A.perm = ts.perm; A.pinv = ts.pinv;
-  A.M = ts.M; A.N = N; A.P = P; A.sig = sig; A.use_E = use_E;
-  A.e_row0 = (i_beg == 0 && i_end == ts.M) ? ts.M * 3 * (int64_t)N : (i_end - i_beg) * 3 * (int64_t)N - i_beg;
-  A.jlist = d_jlist; A.colmap = d_colmap; A.j0 = j0; A.n_j = n_j; A.col0 = col0;
-  A.i_beg = i_beg; A.i_end = i_end; A.lower = (lower || cyc_W > 0) ? 1 : 0; A.lam = lam;
-  A.cyc_W = cyc_W; A.cyc_rank = cyc_rank; A.cyc_nb = cyc_nb;
-  A.K = K; A.ld = ld;
+  A.M = ts.M; A.N = N; A.P = P; A.sig = job.sig; A.use_E = use_E;
+  A.e_row0 = asm_e_row0(ts.M, N, i_beg, i_end);
+  A.jlist = d_jlist; A.colmap = d_colmap; A.j0 = job.j0; A.n_j = n_j; A.col0 = 0;
+  A.i_beg = i_beg; A.i_end = i_end; A.lower = (lower || cyc_W > 0) ? 1 : 0; A.lam = job.lam;
+  A.cyc_W = cyc_W; A.cyc_rank = job.rank; A.cyc_nb = job.nb;
+  A.K = job.K; A.ld = job.ld;
   A.dbg = ctx_opt_i(ctx, "asm.perm_debug", 0);
-  A.fast_store = (!d_colmap && cyc_W == 0 && (col0 % 16) == 0 && ctx_opt_i(ctx, "asm.perm_fast_store", 1)) ? 1 : 0;
+  A.fast_store = (!d_colmap && cyc_W == 0 && ctx_opt_i(ctx, "asm.perm_fast_store", 1)) ? 1 : 0;
 
   // ---- shape: wavefronts and row atoms per wavefront, what lives in LDS, permutations per group.  Registers allow two
   // wavefronts per SIMD: either one workgroup of 8 wavefronts per CU with the whole LDS, or (N <= 24) two independent
@@ -940,8 +922,7 @@ int assemble_perm_launch(gdml_ctx* ctx, double sig, int use_E, const int32_t* d_
   else if (NA == 3) PERM_GO(8, 3);
   else PERM_GO(8, 6);
 #undef PERM_GO
-  const double blocks = A.lower ? 0.5 * (double)n_i * (double)(n_i + 1) : (double)n_i * (double)n_j;
-  ktime_end(ctx, slot, "assemble", 8.0 * blocks * 9.0 * N * N);
+  ktime_end(ctx, slot, "assemble", asm_bytes(N, A.lower, n_i, n_j));
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
   if (d_ca) GDML_TRY(ctx_free(ctx, d_ca));

@@ -22,7 +22,7 @@
 //     row (DIRECT; the variant that stages them through LDS for full-row stores is kept as the A/B: 6 % slower, seven more barriers).
 // Everything else (index lists, energy-constraint rows, block-cyclic layouts, other sizes) stays on assemble_perm_kernel.
 // Arithmetic pinned on the CPU: tools/perm2_emulate.py (run by the CPU test suite).
-#include "common.h"
+#include "assemble.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -880,8 +880,6 @@ __global__ void __launch_bounds__(P2_T) assemble_perm2_kernel(Perm2Args A) {
   }
 }
 
-int build_dense_tables(gdml_ctx* ctx);
-
 // TP[pt][e] = (x, G) of the dense tables' entry src[e]: the per-point tables in internal numbering, one 32-byte entry per ordered pair
 __global__ void __launch_bounds__(256) perm2_pack_kernel(const double* __restrict__ XF, const double* __restrict__ GD,
                                                          const int32_t* __restrict__ src, int64_t M, int NN, double* __restrict__ TP) {
@@ -898,15 +896,24 @@ __global__ void __launch_bounds__(256) perm2_pack_kernel(const double* __restric
   *reinterpret_cast<d4*>(TP + t * 4) = v;
 }
 
-bool assemble_perm2_applicable(const gdml_ctx* ctx) {
+// Large groups on 36 ... 42 atoms (below): dense column ranges, or an index list that requests WHOLE column points in list
+// order (every column of each listed point, output column 3N v + c: what the iterative solver's K_nm is, iterative.py:229-247);
+// any rows, no E rows, plain layout; the lower form over the full range
+bool assemble_perm2_accepts(const gdml_ctx* ctx, const AsmJob& job) {
   const TrainSet& ts = ctx->ts;
+  if (job.use_E || !asm_plain_rows(job) || (job.lower && !asm_full_dense(ctx, job))) return false;
+  if (asm_has_lists(job) && !(job.d_jlist && job.d_colmap && job.h_colmap && !job.lower)) return false;
   if (!ctx_opt_i(ctx, "asm.perm2", 1)) return false;
   // Measured (profiles/r05_assemble_perm2.txt): the per-block cost of this kernel is nearly independent of N and P (17 barriers
   // and a dozen short dependent LDS chains per block and group with one workgroup of 9 wavefronts per CU), so it only wins where
   // assemble_perm_kernel's N^2 P work is largest: N = 42, P = 27 1.8x; N = 36, P = 27 1.17x; N = 42, P = 6 1.15x; N = 30, P = 6 0.72x.
   const int min_n = ctx_opt_i(ctx, "asm.perm2_min_n", 36), min_p = ctx_opt_i(ctx, "asm.perm2_min_p", 6);
   if (ts.P < min_p || ts.N < min_n || ts.N > P2_MAXN) return false;
-  return ts.P >= 16 || ts.N >= min_n + 4 || min_n < 36;  // small groups only pay on the largest molecules
+  if (!(ts.P >= 16 || ts.N >= min_n + 4 || min_n < 36)) return false;  // small groups only pay on the largest molecules
+  if (asm_has_lists(job))
+    for (int64_t e = 0; e < job.n_j * 3 * ts.N; ++e)
+      if (job.h_colmap[e] != (int32_t)e) return false;
+  return true;
 }
 
 // Plan of the group: internal numbering (fixed atoms first), permutations in it, V-phase tasks.  Built once per training set.
@@ -1080,12 +1087,12 @@ static int perm2_plan(gdml_ctx* ctx) {
   return GDML_OK;
 }
 
-// Column points [j0, j0 + n_j) written at col0 + 3N v, row points [i_beg, i_end); lower: A = -K + lam I, blocks j <= i.
-int assemble_perm2_launch(gdml_ctx* ctx, double sig, int64_t j0, int64_t n_j, int64_t col0, double* K, int64_t ld, int64_t i_beg,
-                          int64_t i_end, int lower, double lam, const int32_t* d_jlist) {
+// Column points [j0, j0 + n_j), or the listed ones, written at 3N v, row points [i_beg, i_end); lower: A = -K + lam I,
+// blocks j <= i.
+int assemble_perm2_launch(gdml_ctx* ctx, const AsmJob& job) {
   TrainSet& ts = ctx->ts;
-  if (n_j <= 0 || i_end <= i_beg) return GDML_OK;
-  GDML_TRY(build_dense_tables(ctx));
+  const int lower = job.lower ? 1 : 0;
+  const int64_t n_j = job.n_j, i_beg = job.i_beg, i_end = job.i_end;
   GDML_TRY(perm2_plan(ctx));
   const int N = ts.N, P = ts.P;
   Perm2Args A;
@@ -1093,10 +1100,10 @@ int assemble_perm2_launch(gdml_ctx* ctx, double sig, int64_t j0, int64_t n_j, in
   A.TP = ts.p2_TP; A.blob = ts.p2;
   A.o_src = ts.p2_o[0]; A.o_sigma = ts.p2_o[1]; A.o_tasks = ts.p2_o[2];
   A.n_tasks = ts.p2_ntasks;
-  A.M = ts.M; A.N = N; A.P = P; A.nF = ts.p2_nF; A.nFb = ts.p2_nFb; A.sig = sig;
-  A.j0 = j0; A.n_j = n_j; A.col0 = col0; A.i_beg = i_beg; A.i_end = i_end;
-  A.jlist = d_jlist;
-  A.lower = lower; A.lam = lam; A.K = K; A.ld = ld;
+  A.M = ts.M; A.N = N; A.P = P; A.nF = ts.p2_nF; A.nFb = ts.p2_nFb; A.sig = job.sig;
+  A.j0 = job.j0; A.n_j = n_j; A.col0 = 0; A.i_beg = i_beg; A.i_end = i_end;
+  A.jlist = job.d_jlist;
+  A.lower = lower; A.lam = job.lam; A.K = job.K; A.ld = job.ld;
   A.dbg = ctx_opt_i(ctx, "asm.perm2_debug", 0);
   // small LDS items into the two free regions: the unused rows of B0 (16 doubles per moved atom) and the tail behind the byte
   // permutation tables
@@ -1166,8 +1173,7 @@ int assemble_perm2_launch(gdml_ctx* ctx, double sig, int64_t j0, int64_t n_j, in
     }
     GDML_TRY(ctx_free(ctx, d_trace));
   }
-  const double blocks = lower ? 0.5 * (double)n_i * (double)(n_i + 1) : (double)n_i * (double)n_j;
-  ktime_end(ctx, slot, "assemble", 8.0 * blocks * 9.0 * N * N);
+  ktime_end(ctx, slot, "assemble", asm_bytes(N, lower, n_i, n_j));
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
   return GDML_OK;

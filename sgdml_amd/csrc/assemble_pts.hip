@@ -27,7 +27,7 @@
 // 1.5 KB per-wavefront LDS buffer so that a store instruction writes 64 consecutive doubles.
 #include <type_traits>
 
-#include "common.h"
+#include "assemble.h"
 
 struct PtsArgs {
   const double* XF;     // (M,N,N)    XF[x][m][b] = x[pair(b,m)]
@@ -472,10 +472,11 @@ __global__ void __launch_bounds__(768) assemble_pts_kernel(PtsArgs A) {
   }
 }
 
-int build_dense_tables(gdml_ctx* ctx);
-
-bool assemble_pts_applicable(const gdml_ctx* ctx) {
+// 8 <= N <= 24 with a permutation group: dense column ranges, any rows, E rows, plain layout; the lower form over the full
+// range (anything else in the lower form is refused by the launch)
+bool assemble_pts_accepts(const gdml_ctx* ctx, const AsmJob& job) {
   const TrainSet& ts = ctx->ts;
+  if (asm_has_lists(job) || !asm_plain_rows(job)) return false;
   // measured (profiles/r03_assemble_pts.txt): 1.3-1.5x over assemble_perm.hip for permutation groups; for P = 1 (N = 22-24,
   // the register-resident kernels cover N <= 21) the general kernel is as fast, so it keeps that case (asm.pts = 2 forces)
   const int opt = ctx_opt_i(ctx, "asm.pts", 1);
@@ -499,21 +500,20 @@ static void pts_launch_t(gdml_ctx* ctx, PtsArgs& A, dim3 grid, size_t* lds_out =
 }
 
 // Column points [j0, j0 + n_j) (output columns from 0), row points [i_beg, i_end) (rows relative to i_beg).
-int assemble_pts_launch(gdml_ctx* ctx, double sig, int use_E, int64_t j0, int64_t n_j, double* K, int64_t ld, int64_t i_beg,
-                        int64_t i_end, int lower, double lam) {
+int assemble_pts_launch(gdml_ctx* ctx, const AsmJob& job) {
   TrainSet& ts = ctx->ts;
-  if (n_j <= 0 || i_end <= i_beg) return GDML_OK;
-  GDML_TRY(build_dense_tables(ctx));
+  const int use_E = job.use_E, lower = job.lower;
+  const int64_t n_j = job.n_j, i_beg = job.i_beg, i_end = job.i_end;
   const int N = ts.N, P = ts.P;
-  if (lower && (use_E || j0 != 0 || i_beg != 0 || n_j != ts.M || i_end != ts.M))
+  if (lower && !asm_full_dense(ctx, job))
     return gdml_fail(ctx, GDML_ERR_INVALID, "assemble_pts: the lower form needs the dense full column range");
   if ((int64_t)P * N > 4096) return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "assemble_pts: permutation tables of %d x %d entries", P, N);
   PtsArgs A;
   memset(&A, 0, sizeof(A));
   A.XF = ts.XF; A.GD = ts.GD; A.perm = ts.perm; A.pinv = ts.pinv;
-  A.M = ts.M; A.N = N; A.P = P; A.sig = sig; A.lam = lam; A.use_E = use_E; A.lower = lower ? 1 : 0;
-  A.j0 = j0; A.n_j = n_j; A.i_beg = i_beg; A.i_end = i_end;
-  A.K = K; A.ld = ld;
+  A.M = ts.M; A.N = N; A.P = P; A.sig = job.sig; A.lam = job.lam; A.use_E = use_E; A.lower = lower ? 1 : 0;
+  A.j0 = job.j0; A.n_j = n_j; A.i_beg = i_beg; A.i_end = i_end;
+  A.K = job.K; A.ld = job.ld;
   A.dbg = ctx_opt_i(ctx, "asm.pts_debug", 0);
   A.nt_store = ctx_opt_i(ctx, "asm.pts_nt", 1);
   A.PPS = 64 / N;
@@ -552,8 +552,7 @@ int assemble_pts_launch(gdml_ctx* ctx, double sig, int use_E, int64_t j0, int64_
   dim3 grid((unsigned)((n_strips + 7) / 8 * 8), (unsigned)((n_i + i_chunk - 1) / i_chunk));
   const int slot = ktime_begin(ctx);
   dispatch(grid, nullptr);
-  const double blocks = A.lower ? 0.5 * (double)n_i * (double)(n_i + 1) : (double)n_i * (double)n_j;
-  ktime_end(ctx, slot, "assemble", 8.0 * blocks * 9.0 * N * N);
+  ktime_end(ctx, slot, "assemble", asm_bytes(N, A.lower, n_i, n_j));
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
   return GDML_OK;

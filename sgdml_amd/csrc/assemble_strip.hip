@@ -20,7 +20,7 @@
 // Ordering inside an iteration: loads of point i+1 are issued first, consumed (written to the other LDS buffer) after the
 // scalar phase and BEFORE the 63 stores of point i, so the only vmcnt wait of the loop covers the stores of point i-1,
 // which had the whole scalar phase to drain.
-#include "common.h"
+#include "assemble.h"
 
 struct StripArgs {
   const double* XF;  // (M,N,N)   x[pair(b,m)], m-major
@@ -226,11 +226,13 @@ __global__ void __launch_bounds__(64 * STRIP_W, 2) assemble_strip_kernel(StripAr
   }
 }
 
-int build_dense_tables(gdml_ctx* ctx);
-
-bool assemble_strip_applicable(const gdml_ctx* ctx) {
+// assemble_wave's shapes from 11 atoms on, and nothing but the whole matrix: every column of every row point, no E rows,
+// plain layout (W = 0: the local matrix of the distributed solve, on one rank too, is assemble_wave's), either form
+bool assemble_strip_accepts(const gdml_ctx* ctx, const AsmJob& job) {
   const TrainSet& ts = ctx->ts;
-  return assemble_wave_applicable(ctx) && ts.N >= 11 && ts.N <= 21 && ctx_opt_i(ctx, "asm.strip", 1) != 0;
+  if (asm_has_lists(job) || job.use_E || job.W != 0) return false;
+  if (job.j0 != 0 || job.n_j != ts.M || job.i_beg != 0 || job.i_end != ts.M) return false;
+  return assemble_wave_accepts(ctx, job) && ts.N >= 11 && ts.N <= 21 && ctx_opt_i(ctx, "asm.strip", 1) != 0;
 }
 
 template <int N>
@@ -250,21 +252,18 @@ static int strip_launch_n(gdml_ctx* ctx, StripArgs& A) {
   dim3 grid((unsigned)n_wg, (unsigned)((ts.M + A.i_chunk - 1) / A.i_chunk));
   const int slot = ktime_begin(ctx);
   hipLaunchKernelGGL(assemble_strip_kernel<N>, grid, dim3(64 * STRIP_W), 0, ctx->stream, A);
-  const double M = (double)ts.M;
-  const double blocks = A.lower ? 0.5 * M * (M + 1.0) : M * M;
-  ktime_end(ctx, slot, "assemble", 8.0 * blocks * 9.0 * ts.N * ts.N);
+  ktime_end(ctx, slot, "assemble", asm_bytes(ts.N, A.lower, ts.M, ts.M));
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
   return GDML_OK;
 }
 
 // All columns of all row points: the full un-negated K (lower = 0) or A = -K + lam I, lower blocks (lower = 1).
-int assemble_strip_launch(gdml_ctx* ctx, double sig, double* K, int64_t ld, int lower, double lam) {
+int assemble_strip_launch(gdml_ctx* ctx, const AsmJob& job) {
   TrainSet& ts = ctx->ts;
-  GDML_TRY(build_dense_tables(ctx));
   StripArgs A;
-  A.XF = ts.XF; A.GD = ts.GD; A.x = ts.x; A.TS = nullptr; A.M = ts.M; A.n = ts.M * 3 * (int64_t)ts.N; A.sig = sig;
-  A.lower = lower; A.lam = lam; A.K = K; A.ld = ld; A.i_chunk = 32;
+  A.XF = ts.XF; A.GD = ts.GD; A.x = ts.x; A.TS = nullptr; A.M = ts.M; A.n = ts.M * 3 * (int64_t)ts.N; A.sig = job.sig;
+  A.lower = job.lower; A.lam = job.lam; A.K = job.K; A.ld = job.ld; A.i_chunk = 32;
   switch (ts.N) {
 #define SC(v) case v: return strip_launch_n<v>(ctx, A);
     SC(11) SC(12) SC(13) SC(14) SC(15) SC(16) SC(17) SC(18) SC(19) SC(20) SC(21)

@@ -17,7 +17,7 @@
 // 63x63 block against 31.7 KB written: the kernel is bound by the HBM write stream, and because a
 // wave writes the 504-byte row segments of consecutive j back to back the partially covered cache
 // lines merge in the XCD's L2.
-#include "common.h"
+#include "assemble.h"
 
 // dense tables: XF[i][m][b] = x_i[pair(b,m)] (0 if m == b), GD[i][m][b][al] = G_i(b,m)[al]
 __global__ void __launch_bounds__(256) dense_tables_kernel(const double* __restrict__ x,
@@ -215,7 +215,8 @@ int build_dense_tables(gdml_ctx* ctx) {
   return GDML_OK;
 }
 
-bool assemble_wave_applicable(const gdml_ctx* ctx) {
+// P = 1 with the identity permutation, N <= 21: any column selection, any rows, E rows, both forms, both layouts
+bool assemble_wave_accepts(const gdml_ctx* ctx, const AsmJob&) {
   const TrainSet& ts = ctx->ts;
   if (!ctx_opt_i(ctx, "asm.wave", 1)) return false;
   if (ts.P != 1 || ts.N > 21 || ts.N < 2) return false;
@@ -224,24 +225,21 @@ bool assemble_wave_applicable(const gdml_ctx* ctx) {
   return true;
 }
 
-int assemble_wave_launch(gdml_ctx* ctx, double sig, int use_E, const int32_t* d_jlist,
-                         const int32_t* d_colmap, int64_t j0, int64_t n_j, double* K, int64_t ld,
-                         int64_t i_beg, int64_t i_end, int lower, double lam, int cyc_W, int cyc_rank, int cyc_nb) {
+int assemble_wave_launch(gdml_ctx* ctx, const AsmJob& job) {
   TrainSet& ts = ctx->ts;
-  GDML_TRY(build_dense_tables(ctx));
+  const int lower = job.lower;
+  const int64_t n_j = job.n_j, n_i = job.i_end - job.i_beg;
   WaveArgs A;
-  A.XF = ts.XF; A.GD = ts.GD; A.M = ts.M; A.N = ts.N; A.sig = sig; A.use_E = use_E;
-  A.e_row0 = (i_beg == 0 && i_end == ts.M) ? ts.M * 3 * (int64_t)ts.N : (i_end - i_beg) * 3 * (int64_t)ts.N - i_beg;
-  A.jlist = d_jlist; A.colmap = d_colmap; A.j0 = j0; A.n_j = n_j; A.K = K; A.ld = ld;
-  A.i_beg = i_beg;
+  A.XF = ts.XF; A.GD = ts.GD; A.M = ts.M; A.N = ts.N; A.sig = job.sig; A.use_E = job.use_E;
+  A.e_row0 = asm_e_row0(ts.M, ts.N, job.i_beg, job.i_end);
+  A.jlist = job.d_jlist; A.colmap = job.d_colmap; A.j0 = job.j0; A.n_j = n_j; A.K = job.K; A.ld = job.ld;
+  A.i_beg = job.i_beg;
   A.lower = lower;
-  A.lam = lam;
-  A.cyc_W = cyc_W; A.cyc_rank = cyc_rank; A.cyc_nb = cyc_nb;
-  if (cyc_W > 0 && !lower) return gdml_fail(ctx, GDML_ERR_INVALID, "assemble_wave: the row-cyclic layout is only built in the lower form");
-  if (lower && (d_jlist || d_colmap || use_E || j0 != 0 || i_beg != 0))
+  A.lam = job.lam;
+  A.cyc_W = job.W; A.cyc_rank = job.rank; A.cyc_nb = job.nb;
+  if (job.W > 0 && !lower) return gdml_fail(ctx, GDML_ERR_INVALID, "assemble_wave: the row-cyclic layout is only built in the lower form");
+  if (lower && !asm_full_dense(ctx, job))
     return gdml_fail(ctx, GDML_ERR_INVALID, "assemble_wave: lower form needs the dense full column range");
-  const int64_t n_i = i_end - i_beg;
-  if (n_i <= 0) return GDML_OK;
   // column points walked by one wavefront: 64 for full rows; 32 in the lower form (measured 3.90 vs 4.06-4.22 ms at the
   // benchmark size, tools/asm_lower_probe.py: shorter walks balance the triangular rows better)
   int j_chunk = ctx_opt_i(ctx, "asm.j_chunk", lower ? 32 : 64);
@@ -252,7 +250,7 @@ int assemble_wave_launch(gdml_ctx* ctx, double sig, int use_E, const int32_t* d_
   switch (ts.N) {
 #define WC(v)                                                                                          \
   case v:                                                                                              \
-    if (cyc_W > 0) hipLaunchKernelGGL((assemble_wave_kernel<v, true>), grid, dim3(64), 0, ctx->stream, A); \
+    if (job.W > 0) hipLaunchKernelGGL((assemble_wave_kernel<v, true>), grid, dim3(64), 0, ctx->stream, A); \
     else hipLaunchKernelGGL((assemble_wave_kernel<v, false>), grid, dim3(64), 0, ctx->stream, A);          \
     break;
     WC(2) WC(3) WC(4) WC(5) WC(6) WC(7) WC(8) WC(9) WC(10) WC(11) WC(12) WC(13) WC(14) WC(15) WC(16)
@@ -260,9 +258,7 @@ int assemble_wave_launch(gdml_ctx* ctx, double sig, int use_E, const int32_t* d_
 #undef WC
     default: return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "assemble_wave: N out of range");
   }
-  // algorithmic bytes: every requested element written once (lower form: the n_i (n_i + 1) / 2 blocks with j <= i)
-  const double blocks = lower ? 0.5 * (double)n_i * (double)(n_i + 1) : (double)n_i * (double)n_j;
-  ktime_end(ctx, slot, "assemble", 8.0 * blocks * 9.0 * ts.N * ts.N);
+  ktime_end(ctx, slot, "assemble", asm_bytes(ts.N, lower, n_i, n_j));
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
   return GDML_OK;

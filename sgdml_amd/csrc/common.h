@@ -225,8 +225,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // internal cross-TU entry points
-int assemble_launch(gdml_ctx* ctx, double sig, int use_E_cstr, const int32_t* d_jlist,
-                    int64_t n_j, const int32_t* d_colmap, int64_t col0_all);
 int desc_device(gdml_ctx* ctx, const double* d_R, int64_t M, int N, const double* lat,
                 const double* lat_inv, double* d_x, double* d_g);
 int predict_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B, double* d_E,
@@ -302,26 +300,3 @@ int comm_ensure_second(gdml_ctx* ctx);
 // operations end with an error), and this context refuses further collectives.
 void comm_abort(gdml_ctx* ctx);
 static inline bool comm_active(const gdml_ctx* ctx) { return (ctx->comm || ctx->host_allreduce) && !ctx->virtual_rank; }
-bool assemble_wave_applicable(const gdml_ctx* ctx);
-bool assemble_strip_applicable(const gdml_ctx* ctx);
-int assemble_strip_launch(gdml_ctx* ctx, double sig, double* K, int64_t ld, int lower, double lam);
-int assemble_erows_cyclic_launch(gdml_ctx* ctx, double sig, double lam, double* K, int64_t ld, int cyc_W, int cyc_rank,
-                                 int cyc_nb);
-int assemble_cyclic_launch(gdml_ctx* ctx, double sig, double lam, double* K, int64_t ld, int cyc_W, int cyc_rank,
-                           int cyc_nb);
-bool assemble_perm2_applicable(const gdml_ctx* ctx);
-bool assemble_big1_applicable(const gdml_ctx* ctx);  // assemble_big1.hip: P = 1, 22 <= N <= 256, dense column ranges
-int assemble_big1_launch(gdml_ctx* ctx, double sig, int64_t j0, int64_t n_j, int64_t col0, double* K, int64_t ld, int64_t i_beg,
-                         int64_t i_end, int lower, double lam);
-int assemble_perm2_launch(gdml_ctx* ctx, double sig, int64_t j0, int64_t n_j, int64_t col0, double* K, int64_t ld, int64_t i_beg,
-                          int64_t i_end, int lower, double lam, const int32_t* d_jlist = nullptr);
-int assemble_perm_launch(gdml_ctx* ctx, double sig, int use_E, const int32_t* d_jlist, const int32_t* d_colmap, int64_t j0,
-                         int64_t n_j, int64_t col0, double* K, int64_t ld, int64_t i_beg, int64_t i_end, int lower, double lam,
-                         int cyc_W, int cyc_rank, int cyc_nb, const int32_t* h_colmap = nullptr);
-bool assemble_pts_applicable(const gdml_ctx* ctx);
-int assemble_pts_launch(gdml_ctx* ctx, double sig, int use_E, int64_t j0, int64_t n_j, double* K, int64_t ld, int64_t i_beg,
-                        int64_t i_end, int lower, double lam);
-int assemble_wave_launch(gdml_ctx* ctx, double sig, int use_E, const int32_t* d_jlist,
-                         const int32_t* d_colmap, int64_t j0, int64_t n_j, double* K, int64_t ld,
-                         int64_t i_beg, int64_t i_end, int lower = 0, double lam = 0.0, int cyc_W = 0,
-                         int cyc_rank = 0, int cyc_nb = 0);

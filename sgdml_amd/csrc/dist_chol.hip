@@ -35,7 +35,7 @@
 // keeps an accumulator and one 512-double all-reduce per step collects it.
 // Collective volume per rank: sum_k (n - k0) 512 * 8 B = 4 n^2 B (16 GB at n = 63 000) gathered over the whole
 // factorisation, against n^3 / (3 W) flops: at 8 GPUs ~0.1 s of xGMI time for ~0.2 s of MFMA time.
-#include "common.h"
+#include "assemble.h"
 
 namespace {
 
@@ -184,7 +184,12 @@ extern "C" int gdml_dist_chol_solve(gdml_ctx* ctx, double sig, double lam, const
   auto body = [&]() -> int {
     // ---- assembly of my rows (lower blocks of A = -K + lam I) and the right-hand side
     phase_begin(ctx);
-    GDML_TRY(assemble_cyclic_launch(ctx, sig, lam, A, ld, c.W, c.rank, (int)nb));
+    AsmJob job;  // every force block j <= i of the rows this rank owns
+    job.sig = sig; job.n_j = ts.M; job.i_end = ts.M;
+    job.K = A; job.ld = ld;
+    job.lower = 1; job.lam = lam;
+    job.W = c.W; job.rank = c.rank; job.nb = (int)nb;
+    GDML_TRY(assemble_dispatch(ctx, job));
     if (use_E) GDML_TRY(assemble_erows_cyclic_launch(ctx, sig, lam, A, ld, c.W, c.rank, (int)nb));
     GDML_TRY(phase_end(ctx, "assemble"));
     HIP_CHECK(ctx, hipMemcpyAsync(A + Lr * ld, y, n * 8, hipMemcpyHostToDevice, st));

@@ -387,6 +387,28 @@ def test_direct_kernel_for_large_molecules_without_a_group(ctx, N, M):
     assert np.linalg.norm(Am @ (-a) - y) <= 1e-10 * np.linalg.norm(y)
 
 
+@pytest.mark.parametrize('N,M', [(11, 14), (21, 12)])
+def test_point_range_on_the_strip_shapes(ctx, N, M):
+    """A dense point range without energy constraints on the shapes assemble_strip serves (P = 1, 11 <= N <= 21).  The strip
+    kernel builds nothing but the whole matrix -- it writes all 3N M columns -- so a range must go to assemble_wave
+    (assemble_strip_accepts, csrc/assemble_strip.hip); routed to the strip kernel it wrote past the rows of the n_j-point buffer.
+    Against the oracle at 1e-12 max|K| (the tolerance of every assembly parity test here), with extra rows allocated behind the
+    matrix, and the whole matrix again afterwards through the strip kernel."""
+    ds = orc.synth_dataset(N, M, seed=N, jitter=0.3)
+    xd, gd = orc.desc_from_R(ds['R'].reshape(M, -1))
+    tp = orc.tril_perms_from_atom_perms(np.arange(N)[None])
+    sig = 20.0
+    Ko = orc.assemble_K(xd, gd, orc.tril_perms_lin_from_tril_perms(tp), sig)
+    scale = np.abs(Ko).max()
+    ctx.train_upload(xd, gd, tp)
+    for lo, hi in ((0, 3), (2, M - 1), (M - 1, M)):
+        Ks = ctx.assemble_K(sig, False, points=(lo, hi), alloc_extra_rows=2, to_host=True)
+        assert Ks.shape == (3 * N * M + 2, 3 * N * (hi - lo))
+        assert np.abs(Ks[:3 * N * M] - Ko[:, 3 * N * lo:3 * N * hi]).max() <= 1e-12 * scale, (lo, hi)
+    K = ctx.assemble_K(sig, False, to_host=True)
+    assert np.abs(K - Ko).max() <= 1e-12 * scale
+
+
 def _matching_cases():
     g = np.load(os.path.join(ROOT, 'tests', 'golden', 'perm_c3.npz'))
     lat = g['lat']

@@ -303,7 +303,7 @@ def test_descriptors_are_reused_across_a_sigma_sweep(trainer):
 
 def test_bench_labels_follow_the_library_dispatch_of_the_perm2_kernel():
     """bench.py names the assembly kernel of a configuration in its `roofline_assemble` entries; the dispatch itself is C++
-    (csrc/assemble_perm2.hip assemble_perm2_applicable: N <= 42, P >= asm.perm2_min_p, N >= asm.perm2_min_n, groups below 16
+    (csrc/assemble_perm2.hip assemble_perm2_accepts: N <= 42, P >= asm.perm2_min_p, N >= asm.perm2_min_n, groups below 16
     elements four atoms later).  Both are read here so that one cannot move without the other."""
     import re
     import sys
