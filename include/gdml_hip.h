@@ -79,7 +79,7 @@ int gdml_mem_info(gdml_ctx* ctx, int64_t* held, int64_t* free_b, int64_t* total_
 int gdml_mem_reserve(gdml_ctx* ctx, int64_t bytes, int64_t* reserved_out);
 
 /* Elapsed milliseconds (HIP events on the compute stream) of the most recent call of the
- * named phase: "desc", "assemble", "factor", "solve", "predict", "matvec", "precon".
+ * named phase: "desc", "assemble", "factor", "solve", "predict", "matvec", "precon", "uncert", "loo".
  * Also returns how many kernel launches the phase issued. */
 int gdml_phase_ms(gdml_ctx* ctx, const char* phase, double* ms_out, int64_t* launches_out);
 
@@ -169,6 +169,8 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *   predict.cov_chunk (64)     geometries per pass of gdml_predict_cov / gdml_uncert_cross (their rows of the cross-kernel are 3N n
  *                         doubles each; fewer when free memory is short)
  *   predict.cov_global (0)    1: the cross-kernel keeps its per-permutation vectors in global memory (the path of N > 374; tests)
+ *   chol.loo_chunk (64)            training points per pass of gdml_loo (their rows of L^-T are 3N n doubles each; fewer when free
+ *                         memory is short).  The results do not depend on it
  *   pcg.f32_min_pivot (1e-7)  fp32 form: smallest squared Cholesky pivot of the rounded factor's Gram matrix below which the
  *                         reference's fp64 form is kept (gdml_get_option("pcg.f32_last_min_pivot") reads the last value seen)
  * Unknown keys return GDML_ERR_INVALID. */
@@ -335,6 +337,29 @@ int gdml_predict_cov(gdml_ctx* ctx, const double* R, int64_t B, const double* la
                      double* cov_out);
 int gdml_predict_cov_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat, const double* lat_inv,
                          int full, double* cov_dev);
+
+/* Leave-one-out force errors, their predictive covariances and log det A from the resident Cholesky factor: what M
+ * retrainings on M - 1 points each would give, in one pass (Rasmussen & Williams, Gaussian Processes for Machine Learning,
+ * 5.4.2, in block form).  The reference has no counterpart (it holds back a validation split).  In the library's conventions --
+ * A = -K + lam I = L L^T, labels y normalised by std, alphas = -A^-1 y as gdml_chol_solve returns them -- and with a = -alphas,
+ * a_j the 3N entries of training point j and G_j the 3N x 3N diagonal block j of A^-1:
+ *   r_j = G_j^-1 a_j = y_j - (prediction at x_j of the model trained without point j)      resid_out (M,3N)
+ *   C_j = G_j^-1     = predictive covariance of the left-out label, noise lam included      cov_out
+ *   log det A = 2 sum_i log L_ii                                                             *logdet_out
+ * The caller multiplies r by std and C by std^2.  cov_mode 0: cov_out is not written (may be NULL); 1: (M,3N) diagonals of C_j;
+ * 2: (M,3N,3N), both triangles.  alphas (n = 3N M) are host coefficients that belong to the resident factor's matrix: for
+ * coefficients from another solver (PCG to 1e-4) solve y through the factor first (gdml_chol_solve).
+ * Needs a factor WITHOUT energy-constraint rows resident for the training set of gdml_train_upload: after gdml_uncert_prepare,
+ * or after gdml_chol_factor / gdml_chol_solve in training (the right-hand-side row behind the factor is not touched).  The
+ * factor is only read: a prepared factor stays prepared, gdml_predict_cov gives the same bits before and after.
+ * fp64 throughout (G_j on the MFMA pipe), no atomics, every sum in a fixed order: repeated calls give identical bits, the
+ * diagonal of cov_mode 2 and resid_out equal those of cov_mode 1 bit for bit, and nothing depends on option chol.loo_chunk.
+ * GDML_ERR_STATE without a factor or with one that does not belong to the training set, GDML_ERR_UNSUPPORTED for a factor
+ * with energy-constraint rows or a multi-rank context, GDML_ERR_INVALID for NULL arguments / a wrong n / cov_mode,
+ * GDML_ERR_NOT_PD with *info = j + 1 when G_j of training point j has a non-positive pivot (the outputs are then undefined).
+ * Not offered: leave-one-out energies (the integration constant is refitted per fold) and systems with energy constraints. */
+int gdml_loo(gdml_ctx* ctx, const double* alphas, int64_t n, int cov_mode, double* resid_out, double* cov_out,
+             double* logdet_out, int* info);
 
 /* Test / validation error sums evaluated on the device (replaces the body of the reference's
  * cli.test loop, sgdml/cli.py:1564-1605 with _online_err :1170): predicts B host geometries R,

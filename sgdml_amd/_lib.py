@@ -54,6 +54,7 @@ SIGNATURES = {
     'gdml_uncert_cross': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     'gdml_predict_cov': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
     'gdml_predict_cov_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
+    'gdml_loo': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     'gdml_kernel_matvec': (C.c_int, [_vp, C.c_double, C.c_int, _vp, C.c_int64, _vp]),
     'gdml_predict_errors': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     'gdml_nystroem_factor': (C.c_int, [_vp, C.c_double, _vp, C.c_int64, _vp, _vp, C.POINTER(C.c_int)]),
@@ -612,6 +613,24 @@ class Context(object):
             lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
         self._check(self._lib.gdml_predict_cov_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), int(bool(full)),
                                                    cov_dev))
+
+    def loo(self, alphas, cov=None):
+        """Leave-one-out pass over the resident Cholesky factor (gdml_loo), in normalised units: (resid (M,3N), cov, logdet) with
+        cov None, the (M,3N) diagonals ('diag') or the (M,3N,3N) covariances ('full') of the left-out labels, logdet = log det A.
+        alphas: the library's coefficients -A^-1 y of this factor.  Raises numpy.linalg.LinAlgError when a diagonal block of
+        A^-1 is not positive definite."""
+        if cov not in (None, 'diag', 'full'):
+            raise ValueError("cov must be None, 'diag' or 'full'")
+        if not hasattr(self, 'n_atoms'):
+            raise GDMLHipError('loo: no training set resident (train_upload)')
+        alphas = f64(alphas).ravel()
+        M, n3 = self.n_train, 3 * self.n_atoms
+        resid = np.empty((M, n3))
+        c = None if cov is None else np.empty((M, n3) if cov == 'diag' else (M, n3, n3))
+        logdet, info = C.c_double(0.0), C.c_int(0)
+        self._check(self._lib.gdml_loo(self._h, _ptr(alphas), alphas.size, {None: 0, 'diag': 1, 'full': 2}[cov], _ptr(resid),
+                                       _ptr(c), C.byref(logdet), C.byref(info)))
+        return resid, c, logdet.value
 
     def predict_errors(self, R, F_ref, E_ref=None, std=1.0, c=0.0, lat_and_inv=None):
         """Eight error sums of a labelled batch, evaluated on the GPU (see gdml_predict_errors)."""

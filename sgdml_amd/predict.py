@@ -286,6 +286,54 @@ class GDMLPredict(object):
         cov *= self.std * self.std * self.uncertainty_scale
         return E, F, cov
 
+    # ---- leave-one-out errors and model evidence (csrc/loo.hip)
+
+    def loo_errors(self, F_train=None, cov=None):
+        """Leave-one-out force errors of the training set from the factor of prepare_uncertainty(), in one pass instead of M
+        retrainings: for every training point j the error F_j - F_hat_j of the model trained WITHOUT point j (same sig, lam
+        and permutations), exact up to rounding (Rasmussen & Williams 5.4.2).
+
+        The coefficients are model['alphas_F'].  With F_train (M,3N), the labels the model was trained on, they are solved
+        through the resident factor instead -- exact for this factor, and the right choice for models the iterative solver
+        trained to a tolerance.  cov: None, 'diag' or 'full' -- the predictive (co)variances of the left-out labels.
+
+        Returns a dict: 'F_resid' (M,3N) the errors in the units of F; 'F_loo' = F_train - F_resid, the left-out predictions
+        (only with F_train); 'f_mae', 'f_rmse' over all M 3N components (the definitions of test_errors()['force']); 'cov'
+        (M,3N) or (M,3N,3N) in units of F squared (std^2 times `uncertainty_scale`) when requested; 'log_det_A'; and
+        'log_marginal_likelihood' of the normalised labels at signal variance s^2 = `uncertainty_scale`:
+            -1/2 y^T A^-1 y / s^2 - 1/2 (log det A + n log s^2) - n/2 log 2 pi,    y^T A^-1 y = -y . alphas
+        (with F_train; without it y is not known and the key is left out).  Leave-one-out energies are not offered: the
+        integration constant is refitted per fold."""
+        if self._use_E_cstr:
+            raise NotImplementedError('leave-one-out errors of models with energy constraints are not supported')
+        if cov not in (None, 'diag', 'full'):
+            raise ValueError("cov must be None, 'diag' or 'full'")
+        n = 3 * self.n_atoms * self.n_train
+        y = None
+        if F_train is not None:
+            F_train = np.asarray(F_train, dtype=np.float64).reshape(self.n_train, -1)
+            if F_train.size != n:
+                raise ValueError('F_train holds {} values, the model has {} coefficients'.format(F_train.size, n))
+            y = F_train.ravel() / self.std
+            alphas = self._ctx.chol_solve(y)
+        else:
+            if self._alphas_F is None:
+                raise ValueError("leave-one-out errors need the model's 'alphas_F' or F_train")
+            alphas = self._alphas_F
+        resid, c, logdet = self._ctx.loo(alphas, cov)
+        resid *= self.std
+        out = {'F_resid': resid, 'f_mae': float(np.abs(resid).sum() / n), 'f_rmse': float(np.sqrt((resid * resid).sum() / n)),
+               'log_det_A': logdet}
+        if c is not None:
+            c *= self.std * self.std * self.uncertainty_scale
+            out['cov'] = c
+        if y is not None:
+            s2 = self.uncertainty_scale
+            out['F_loo'] = F_train - resid
+            out['log_marginal_likelihood'] = float(-0.5 * (-np.dot(y, alphas)) / s2 - 0.5 * (logdet + n * np.log(s2))
+                                                   - 0.5 * n * np.log(2.0 * np.pi))
+        return out
+
     def predict(self, R=None, return_E=True):
         """Energies (B,) and forces (B,3N) for geometries R (B,3N); R=None -> training-set mode."""
         if R is not None:

@@ -22,15 +22,20 @@ class Analytic(object):
         self.callback = callback
         self.n_refine = 0  # iterative-refinement steps (0 = LAPACK cho_solve semantics)
         self.used_lu = False  # set when the last solve went through the LU branch (analytic.py:101-114)
+        self.loo_result = None  # (resid, None, log det A) of Context.loo in normalised units when gdml_train.loo is set
 
     def solve(self, task, R_desc, R_d_desc, tril_perms_lin, y):
         sig, lam, use_E_cstr = task['sig'], task['lam'], task['use_E_cstr']
         n_train, dim_d = R_d_desc.shape[:2]
+        want_loo = bool(getattr(self.gdml_train, 'loo', False))
+        self.loo_result = None
 
         ctx = self.gdml_train._context()
         ctx.train_upload(R_desc, R_d_desc, _lib.tril_perms_from_lin(tril_perms_lin, dim_d))
 
         if ctx.comm_info()[1] > 1:
+            if want_loo:
+                self.log.info('Leave-one-out errors skipped: the factor of a multi-rank solve is distributed')
             # GDMLTrain.init_distributed: the system matrix is partitioned block-row-cyclic over the ranks and
             # factored by the distributed Cholesky (csrc/dist_chol.hip); every rank gets the coefficients.  With energy
             # constraints y carries the M energy labels and the library appends the M energy rows (train.py:235-300)
@@ -85,20 +90,29 @@ class Analytic(object):
             cb(NOT_DONE)
 
         start = timeit.default_timer()
+        have_factor = False
         try:
             # A = -K + lam I, A = L L^T (analytic.py:65,82,94)
             ctx.chol_factor(lam)
             alphas = ctx.chol_solve(None, n_refine=self.n_refine)  # backward substitution; = -A^-1 y (analytic.py:97-99)
+            have_factor = True
         except np.linalg.LinAlgError:  # "Try a solver that makes less assumptions" (analytic.py:101-114)
             if self.callback is not None:
                 cb = partial(self.callback, disp_str='Solving linear system (LU factorization)      ')  # Keep whitespaces!
                 cb(NOT_DONE)
             self.used_lu = True
+            if want_loo:
+                self.log.info('Leave-one-out errors skipped: the LU branch leaves no Cholesky factor')
             # the failed Cholesky consumed the matrix (the reference keeps a second copy, overwrite_a=False): the
             # LU needs both triangles, so the full K is assembled again (milliseconds) and factored with partial
             # pivoting on the device
             ctx.assemble_K(sig, use_E_cstr)
             alphas = ctx.lu_solve(lam, y)
+
+        if want_loo and use_E_cstr:
+            self.log.info('Leave-one-out errors skipped: not offered for systems with energy constraints')
+        elif want_loo and have_factor:  # the factor is still resident
+            self.loo_result = ctx.loo(alphas)
 
         if self.callback is not None:
             dur_s = timeit.default_timer() - start

@@ -29,7 +29,7 @@ def _errors_into_model(model, errs, n_pts, is_test, md5=None):
 
 def sigma_sweep(gdml_train, dataset, n_train, n_valid, n_test, sigs=None, valid_dataset=None, test_dataset=None,
                 lam=1e-10, perms=None, use_sym=True, use_E=True, use_E_cstr=False, early_stop=True, callback=None,
-                emulate_cli_rng=False):
+                emulate_cli_rng=False, select='valid'):
     """Train one model per sigma on a shared task, validate each, select the best, test it.
 
     Returns (best_model, table, timings): `table` rows are (sig, e_mae, e_rmse, f_mae, f_rmse) of the validated
@@ -40,7 +40,15 @@ def sigma_sweep(gdml_train, dataset, n_train, n_valid, n_test, sigs=None, valid_
     additionally consumes what a freshly installed reference CLI draws between them for its CPU worker benchmark (one
     rand(min(1000, n_valid), 3N) per validation until its cache holds three runs: cli.py:1513-1518 -> predict.py:833-858,
     :1087-1090), so that a seed reproduces the reference's test sample too (tests/test_hip_r3.py).
+
+    select='loo' chooses by the leave-one-out force RMSE of the TRAINING set instead (GDMLTrain.loo, csrc/loo.hip: one pass
+    over each model's resident Cholesky factor, exact up to rounding): no validation predictions are made, the force columns
+    of `table` hold the leave-one-out errors (the energy columns 0), and the early-stop rule and the final choice apply to
+    them.  The NumPy draws of the validation loop are kept, so the test sample is the one select='valid' draws.  Needs the
+    analytic solver on a single GPU without energy constraints (RuntimeError otherwise).
     """
+    if select not in ('valid', 'loo'):
+        raise ValueError("select must be 'valid' or 'loo'")
     if sigs is None:
         sigs = list(range(10, 100, 10))  # cli.py:806: default grid '10:10:100'
     valid_dataset = dataset if valid_dataset is None else valid_dataset
@@ -62,11 +70,23 @@ def sigma_sweep(gdml_train, dataset, n_train, n_valid, n_test, sigs=None, valid_
     for sig in sigs:
         task = dict(task0, sig=sig)
         t0 = timeit.default_timer()
-        model = gdml_train.train(task, callback=callback)
-        t1 = timeit.default_timer()
-        pred = GDMLPredict(model, _borrow_ctx=gdml_train._context())  # short-lived: the trainer's context serves it
-        errs = pred.test_errors(R_valid, F_valid, E_valid)
-        del pred
+        if select == 'loo':
+            loo_was = gdml_train.loo
+            gdml_train.loo = True
+            try:
+                model = gdml_train.train(task, callback=callback)
+            finally:
+                gdml_train.loo = loo_was
+            if 'loo_f_rmse' not in model:
+                raise RuntimeError("select='loo' needs the analytic solver's Cholesky factor (single GPU, no energy constraints)")
+            t1 = timeit.default_timer()
+            errs = {'force': (model['loo_f_mae'], model['loo_f_rmse'])}
+        else:
+            model = gdml_train.train(task, callback=callback)
+            t1 = timeit.default_timer()
+            pred = GDMLPredict(model, _borrow_ctx=gdml_train._context())  # short-lived: the trainer's context serves it
+            errs = pred.test_errors(R_valid, F_valid, E_valid)
+            del pred
         # the reference shuffles the validation indices of every model before its online error loop (cli.py:1487-1488);
         # the device reduction does not care about the order, but the draw keeps the global NumPy stream -- which picks
         # the test sample below -- where the reference's is
@@ -76,7 +96,8 @@ def sigma_sweep(gdml_train, dataset, n_train, n_valid, n_test, sigs=None, valid_
         t2 = timeit.default_timer()
         t_train += t1 - t0
         t_valid += t2 - t1
-        _errors_into_model(model, errs, len(iv), is_test=False)
+        if select == 'valid':
+            _errors_into_model(model, errs, len(iv), is_test=False)
         models.append(model)
         e = errs.get('energy', (0.0, 0.0))
         table.append((sig, float(e[0]), float(e[1]), float(errs['force'][0]), float(errs['force'][1])))

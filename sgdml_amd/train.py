@@ -45,6 +45,11 @@ class GDMLTrain(object):
         # inducing columns of a freshly installed reference's NumPy path.  Off by default: the caller's global stream is
         # left alone, like the reference's own torch path does (README, "Things a user of the reference should know").
         self.emulate_reference_rng = False
+        # Public switch: leave-one-out force errors and log det A from the analytic solver's factor while it is still resident
+        # (csrc/loo.hip): train() then stores 'loo_f_mae', 'loo_f_rmse' (units of F) and 'log_det_A' in the model.  Single GPU,
+        # no energy constraints, Cholesky branch only; otherwise the reason is logged and the keys are left out.  Off by
+        # default: a default run does exactly what it did before.
+        self.loo = False
         self._emulate_ref_rng = False  # rounds 3-4 name of the same switch (tests)
 
     def __del__(self):
@@ -375,10 +380,17 @@ class GDMLTrain(object):
             self.log.info('Using analytic solver (expected device memory use: ~{:.1f} GB)'.format(est_analytic / 2**30))
             analytic = Analytic(self, desc, callback=callback)
             alphas = analytic.solve(task, R_desc, R_d_desc, tril_perms_lin, y)
+            if analytic.loo_result is not None:
+                resid, _, logdet = analytic.loo_result
+                solver_keys['loo_f_mae'] = float(np.abs(resid).mean() * y_std)
+                solver_keys['loo_f_rmse'] = float(np.sqrt((resid * resid).mean()) * y_std)
+                solver_keys['log_det_A'] = float(logdet)
         else:
             from .solvers.iterative import Iterative
 
             self.log.info('Using iterative solver')
+            if self.loo:
+                self.log.info('Leave-one-out errors skipped: the iterative solver leaves no Cholesky factor')
             iterative = Iterative(self, desc, self._max_memory, self._max_processes, self._use_torch,
                                   callback=callback)
             (
