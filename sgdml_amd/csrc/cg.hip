@@ -868,7 +868,7 @@ static int build_f32_form(gdml_ctx* ctx, double lam, double* X, const double* S,
     double fits = rc_a == GDML_OK ? 1.0 : 0.0;
     if (comm_active(ctx)) {
       double* d_flag;
-      GDML_TRY(ctx_slot(ctx, 10, 64, &d_flag));
+      GDML_TRY(ctx_slot(ctx, SLOT_PRECON_MF, 64, &d_flag));
       HIP_CHECK(ctx, hipMemcpyAsync(d_flag, &fits, 8, hipMemcpyHostToDevice, st));
       GDML_TRY(comm_allreduce_sum(ctx, d_flag, 1));
       HIP_CHECK(ctx, hipMemcpyAsync(&fits, d_flag, 8, hipMemcpyDeviceToHost, st));
@@ -911,7 +911,7 @@ static int build_f32_form(gdml_ctx* ctx, double lam, double* X, const double* S,
       chunk = chunk < 256 ? 256 : chunk / 16 * 16;
       if (chunk > n_loc) chunk = n_loc > 0 ? n_loc : 1;
       double* D;
-      GDML_TRY(ctx_slot(ctx, 11, chunk * ld * 8, &D));
+      GDML_TRY(ctx_slot(ctx, SLOT_F32_GRAM_ROWS, chunk * ld * 8, &D));
       HIP_CHECK(ctx, hipMemsetAsync(G, 0, 2 * m * ld * 8, st));  // G and Gc (upper tiles are never written again)
       for (int64_t r0 = 0; r0 < n_loc; r0 += chunk) {
         const int64_t rows = (n_loc - r0 < chunk) ? n_loc - r0 : chunk;
@@ -984,7 +984,7 @@ static int lev_scores_to_host(gdml_ctx* ctx, const ShardGeo& sg, double* lev_sco
     ctx->precon_stage = 2;
   }
   double* d_lev;
-  GDML_TRY(ctx_slot(ctx, 2, sg.n_pad * 8, &d_lev));
+  GDML_TRY(ctx_slot(ctx, SLOT_LEV_SCORES, sg.n_pad * 8, &d_lev));
   if (n_loc > 0)
     hipLaunchKernelGGL(row_sqnorm_kernel, dim3(ceil_div(n_loc, 4)), dim3(256), 0, ctx->stream, X, ld, n_loc, m,
                        d_lev + sg.row0);
@@ -1211,7 +1211,7 @@ static int precon_apply_mf(gdml_ctx* ctx, double lam, const double* d_v, double*
   const int rows_per = 512;
   const int nparts = (int)((m + rows_per - 1) / rows_per);
   double* buf;
-  GDML_TRY(ctx_slot(ctx, 10, (2 * n_pad + 2 * m_pad + (int64_t)nparts * m_pad) * 8, &buf));
+  GDML_TRY(ctx_slot(ctx, SLOT_PRECON_MF, (2 * n_pad + 2 * m_pad + (int64_t)nparts * m_pad) * 8, &buf));
   double* s = buf;            // K v, later K e
   double* e = s + n_pad;      // scattered m-vector
   double* t1 = e + n_pad;
@@ -1251,7 +1251,7 @@ static int precon_apply_device(gdml_ctx* ctx, double lam, const double* d_v, dou
     int nparts = (int)((n_loc + rows_per - 1) / rows_per);
     if (nparts < 1) nparts = 1;
     double* buf;
-    GDML_TRY(ctx_slot(ctx, 3, ((int64_t)nparts * m + 2 * ld + 4) * 8, &buf));
+    GDML_TRY(ctx_slot(ctx, SLOT_PRECON_GEMV, ((int64_t)nparts * m + 2 * ld + 4) * 8, &buf));
     double* part = buf;
     double* t = buf + (((int64_t)nparts * m + 1) & ~(int64_t)1);
     double* u = t + ld;
@@ -1296,7 +1296,7 @@ static int precon_apply_device(gdml_ctx* ctx, double lam, const double* d_v, dou
   int nparts = (int)((n_loc + rows_per - 1) / rows_per);
   if (nparts < 1) nparts = 1;
   double* buf;
-  GDML_TRY(ctx_slot(ctx, 3, ((int64_t)nparts * m + m + 2) * 8, &buf));
+  GDML_TRY(ctx_slot(ctx, SLOT_PRECON_GEMV, ((int64_t)nparts * m + m + 2) * 8, &buf));
   double* part = buf;
   double* t = buf + (((int64_t)nparts * m + 1) & ~(int64_t)1);  // 16-byte aligned: read in pairs
   const int kslot = ktime_begin(ctx);

@@ -1154,7 +1154,7 @@ int launch_panel_trsm(gdml_ctx* ctx, hipStream_t st, const double* L, double* X,
   const int dbg = ctx_opt_i(ctx, "trsm.debug", 0);  // timing-only ablation bits: 1 no substitution, 2 no MFMA update,
                                                     // 4 no L_jj staging, 8 no strip load, 16 no stores
   double* Tb = nullptr;
-  GDML_TRY(ctx_slot(ctx, 8, (int64_t)8 * PT_TB * 8, &Tb));
+  GDML_TRY(ctx_slot(ctx, SLOT_PANEL_TRSM, (int64_t)8 * PT_TB * 8, &Tb));
   const int slot = (st == (ctx->kt_stream ? ctx->kt_stream : ctx->stream)) ? ktime_begin(ctx) : -1;
   hipLaunchKernelGGL(panel_trsm_prep_kernel, dim3((unsigned)(nb / 64)), dim3(256), 0, st, L, ldl > 0 ? ldl : ld, Tb);
   if (dbg)
@@ -1275,7 +1275,7 @@ static int panel_factor(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int
 int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int64_t ld, int64_t k0,
                        int64_t nb) {
   double* save = nullptr;  // two 64 x 64 slots for the deferred write-back of the diagonal blocks
-  GDML_TRY(ctx_slot(ctx, 5, 2 * 4096 * 8, &save));
+  GDML_TRY(ctx_slot(ctx, SLOT_PANEL_SAVE, 2 * 4096 * 8, &save));
   const double* Lprev = nullptr;
   double* Aprev = nullptr;
   int wprev = 0, flip = 0;

@@ -72,6 +72,36 @@ struct Model {
   bool has_aE = false;
 };
 
+// Cached work buffers of ctx_slot.  A buffer belongs to its requester from the ctx_slot call to the end of that library call:
+// everything that touches it is ordered on the context's streams inside the call, nothing is carried over to the next call,
+// and a request that has to grow the buffer waits for ctx->stream before the old one is freed.  Requesters may therefore
+// share a slot exactly when none of them runs, or is called, while another's pointer is still in use:
+//   SLOT_PREDICT_WS   predict_fused, the three paths of predict_device and hess_device are alternatives of one call each;
+//                     none calls another (matvec_device -> predict_device holds SLOT_MATVEC_OUT / _VREF, not this one)
+//   SLOT_PRECON_GEMV  the fp32 form (precon_form 3) and the fp64 form are two branches of precon_apply_device
+//   SLOT_PRECON_MF    build_f32_form reads its flag back and synchronises before it goes on, and applies no preconditioner;
+//                     precon_apply_mf calls matvec_device, which requests other slots only
+//   SLOT_GRAM_WS/ROWS gdml_uncert_cross, gdml_predict_cov and gdml_loo each carve them anew (gram_workspace) and call none of
+//                     the others; tall_trsm in between requests SLOT_PANEL_TRSM only
+enum CtxSlot {
+  SLOT_PREDICT_WS = 0,      // row-split partials of F_x and E (predict_device, predict_fused); workspace of hess_device
+  SLOT_MATVEC_OUT = 1,      // forces and energies of this rank's query points (matvec_device)
+  SLOT_LEV_SCORES = 2,      // replicated leverage scores (lev_scores_to_host: gdml_nystroem_lev_scores, gdml_nystroem_factor)
+  SLOT_PRECON_GEMV = 3,     // row-split partials and m-vectors of one preconditioner application (precon_apply_device)
+  SLOT_PREDICT_STATS = 4,   // row statistics of the table for predict_mfma_kernel (predict_device)
+  SLOT_PANEL_SAVE = 5,      // deferred write-back of two 64 x 64 diagonal blocks (panel_factor_steps)
+  SLOT_LU_UT = 6,           // transposed panel of U (lu_factor_device)
+  SLOT_WIDE_WS = 7,         // pair scalars, row statistics, padded tables and queries (predict_wide_device)
+  SLOT_PANEL_TRSM = 8,      // prepared diagonal blocks of a panel (launch_panel_trsm)
+  SLOT_WIDE_PARTS = 9,      // k-split partials of the F_x contraction (predict_wide_device)
+  SLOT_PRECON_MF = 10,      // vectors of the matrix-free preconditioner (precon_apply_mf); "fits on every rank" flag (build_f32_form)
+  SLOT_F32_GRAM_ROWS = 11,  // widened row chunk of the rounded factor (build_f32_form)
+  SLOT_MATVEC_VREF = 12,    // coefficients back in the reference order (matvec_device, sharded with energy constraints)
+  SLOT_GRAM_WS = 13,        // queries / coefficients, partial Gram tiles, staged output (gram_workspace: uncert.hip, loo.hip)
+  SLOT_GRAM_ROWS = 14,      // the (3N x chunk, padded to 128 rows) x K_ld row buffer (gram_workspace: uncert.hip, loo.hip)
+  SLOT_COUNT
+};
+
 struct gdml_ctx {
   int device = 0;
   int num_cus = 256;  // compute units of the device (grid sizing)
@@ -143,8 +173,8 @@ struct gdml_ctx {
   // scratch
   double* scratch = nullptr;
   int64_t scratch_bytes = 0;
-  double* slot[15] = {};  // cached work buffers (ctx_slot)
-  int64_t slot_bytes[15] = {};
+  double* slot[SLOT_COUNT] = {};  // cached work buffers (ctx_slot, CtxSlot)
+  int64_t slot_bytes[SLOT_COUNT] = {};
   int* d_info = nullptr;
 
   // comm
@@ -260,6 +290,24 @@ int chol_bwd_device(gdml_ctx* ctx, const double* L, int64_t n, int64_t ld, doubl
 // X[:, 0:m] <- X L^-T for the n rows of X (cg.hip).  look: 1 left-looking, 0 right-looking, -1 = option nys.trsm_left
 int tall_trsm(gdml_ctx* ctx, const double* L, double* X, int64_t n, int64_t m, int64_t ld, int look = -1);
 int ctx_slot(gdml_ctx* ctx, int slot, int64_t bytes, double** out);
+int ctx_slot_release(gdml_ctx* ctx, int slot);
+// ---- block Gram of tall row blocks (block_gram.hip; uncert.hip, loo.hip)
+struct GramSplit {
+  int n3, nblk, npairs, S;  // rows of an item, its 64-row blocks and lower block pairs, k splits
+  int64_t n, ld, L;         // columns, pitch (n rounded up to 16), split length
+};
+GramSplit gram_split(int64_t n, int n3);
+// The solve runs on whole 128-row tiles (zero rows behind the last item): an interior tile of the trailing update and an
+// edge tile round differently (chol.hip: acc = -C first vs C - acc last), and which of the two an item's rows meet must not
+// depend on how the items were cut into chunks.
+static inline int64_t pad_rows128(int64_t rows) { return (rows + 127) / 128 * 128; }
+// chunk length (option chunk_opt, default 64, less when free memory is short), row buffer and workspace of ws_fixed +
+// chunk * ws_per_item doubles
+int gram_workspace(gdml_ctx* ctx, const GramSplit& g, const char* chunk_opt, int64_t items, int64_t ws_per_item, int64_t ws_fixed,
+                   int64_t* chunk, double** rows, double** ws);
+// partial tiles of Z_i Z_i^T for `items` row blocks; item i is zero left of column first0 + i first_stride.  One launch, not timed
+void block_gram_launch(gdml_ctx* ctx, const GramSplit& g, const double* Z, double* part, int64_t items, bool diag, int64_t first0,
+                       int64_t first_stride);
 void shard_points(const gdml_ctx* ctx, int64_t M, int64_t* p0, int64_t* p1, int64_t* pts_per);
 // Layout of the replicated device vectors of the sharded solvers (Nystroem factor rows, PCG vectors, mat-vec in / out).
 //   no communicator (world <= 1): the reference order, n entries, no padding;

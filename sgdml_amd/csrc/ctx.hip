@@ -371,12 +371,17 @@ int ctx_scratch(gdml_ctx* ctx, int64_t bytes, double** out) {
   return GDML_OK;
 }
 
+int ctx_slot_release(gdml_ctx* ctx, int slot) {
+  if (ctx->slot[slot]) GDML_TRY(ctx_free(ctx, ctx->slot[slot]));
+  ctx->slot[slot] = nullptr;
+  ctx->slot_bytes[slot] = 0;
+  return GDML_OK;
+}
+
 // Cached work buffer that only grows (avoids hipMalloc/hipFree in hot paths).
 int ctx_slot(gdml_ctx* ctx, int slot, int64_t bytes, double** out) {
   if (bytes > ctx->slot_bytes[slot]) {
-    if (ctx->slot[slot]) GDML_TRY(ctx_free(ctx, ctx->slot[slot]));
-    ctx->slot[slot] = nullptr;
-    ctx->slot_bytes[slot] = 0;
+    GDML_TRY(ctx_slot_release(ctx, slot));
     int64_t want = bytes + bytes / 8;
     GDML_TRY(ctx_alloc(ctx, (void**)&ctx->slot[slot], want));
     ctx->slot_bytes[slot] = want;

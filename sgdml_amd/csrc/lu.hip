@@ -228,7 +228,7 @@ int lu_factor_device(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int64_t* d
   hipStream_t st = ctx->stream;
   HIP_CHECK(ctx, hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
   double* UT = nullptr;
-  GDML_TRY(ctx_slot(ctx, 6, n * LU_NB * 8, &UT));
+  GDML_TRY(ctx_slot(ctx, SLOT_LU_UT, n * LU_NB * 8, &UT));
   for (int64_t k0 = 0; k0 < n; k0 += LU_NB) {
     const int nb = (int)((n - k0 < LU_NB) ? n - k0 : LU_NB);
     for (int j = 0; j < nb; ++j) {

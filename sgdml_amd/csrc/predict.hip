@@ -850,7 +850,7 @@ int predict_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_
                                (wide_opt == 2 || (wide_opt == 1 && (double)MP * (double)B * (double)D >= 1.0e9)));
   if (wide) {  // large molecules: the contractions as tiled fp64-MFMA GEMMs (predict_wide.hip)
     double* part;
-    GDML_TRY(ctx_slot(ctx, 0, (B * (int64_t)D + B) * 8, &part));
+    GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, (B * (int64_t)D + B) * 8, &part));
     const int slot = ktime_begin(ctx);
     GDML_TRY(predict_wide_device(ctx, d_xq, B, part, part + B * (int64_t)D));
     ktime_end(ctx, slot, "predict", 10.0 * (double)D * (double)B * (double)MP);
@@ -907,7 +907,7 @@ int predict_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_
 
   int64_t need = (JS * B * (int64_t)D + JS * B) * 8;
   double* part;
-  GDML_TRY(ctx_slot(ctx, 0, need, &part));
+  GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, need, &part));
 
   PredArgs A;
   A.xq = d_xq; A.xp = md.xp; A.jap = md.jap; A.aE = md.has_aE ? md.aE : nullptr;
@@ -916,7 +916,7 @@ int predict_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_
   const int slot = ktime_begin(ctx);
   if (mfma) {
     double* stats;
-    GDML_TRY(ctx_slot(ctx, 4, 2 * MP * 8, &stats));
+    GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_STATS, 2 * MP * 8, &stats));
     hipLaunchKernelGGL(row_stats_kernel, dim3(ceil_div(MP, 4)), dim3(256), 0, ctx->stream, md.xp, md.jap, MP,
                        D, stats, stats + MP);
     dim3 grid((unsigned)n_qt, (unsigned)JS);
@@ -1316,7 +1316,7 @@ static int predict_fused(gdml_ctx* ctx, const double* R, int64_t B, const double
   const int64_t n_waves = (MP + rows - 1) / rows;
   const int n_wg = (int)((n_waves + 3) / 4);
   double* part;
-  GDML_TRY(ctx_slot(ctx, 0, (int64_t)n_wg * B * (D + 1) * 8, &part));
+  GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, (int64_t)n_wg * B * (D + 1) * 8, &part));
   FusedArgs A;
   A.xp = md.xp; A.jap = md.jap; A.aE = md.has_aE ? md.aE : nullptr;
   A.MP = MP; A.D = D; A.N = N; A.B = (int)B; A.want_E = E_out != nullptr;
@@ -1606,7 +1606,7 @@ int matvec_device(gdml_ctx* ctx, double lam, int use_E_cstr, const double* d_v, 
   const VecLayout L = vec_layout(ctx, use_E_cstr);
   if (L.two_seg) {
     double* vref;
-    GDML_TRY(ctx_slot(ctx, 12, n * 8, &vref));
+    GDML_TRY(ctx_slot(ctx, SLOT_MATVEC_VREF, n * 8, &vref));
     hipLaunchKernelGGL(vec_to_ref_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_v, L, vref);
     GDML_TRY(set_alphas_device(ctx, vref, vref + nF));
   } else {
@@ -1616,7 +1616,7 @@ int matvec_device(gdml_ctx* ctx, double lam, int use_E_cstr, const double* d_v, 
   if (ctx->world > 1) shard_points(ctx, M, &p0, &p1, &per);
   const int64_t B = p1 - p0;
   double* dF;
-  GDML_TRY(ctx_slot(ctx, 1, (B * N3 + B + 8) * 8, &dF));
+  GDML_TRY(ctx_slot(ctx, SLOT_MATVEC_OUT, (B * N3 + B + 8) * 8, &dF));
   double* dE = dF + B * N3;
   if (B > 0) {
     GDML_TRY(predict_device(ctx, ts.x + p0 * ts.D, ts.g + p0 * ts.D * 3, B, use_E_cstr ? dE : nullptr, dF));

@@ -511,7 +511,7 @@ int hess_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B
   const int64_t nU = Bs * nr_cap * ld, nCS = Bs * nr_cap * 2, nPF = G * Bs * D, nPE = G * Bs * 2,
                 nHp = JS * Bs * (int64_t)ld * ld, nFX = Bs * (int64_t)D;
   double* ws;
-  GDML_TRY(ctx_slot(ctx, 0, (2 * nU + nCS + nPF + nPE + nHp + nFX + Bs) * 8, &ws));
+  GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, (2 * nU + nCS + nPF + nPE + nHp + nFX + Bs) * 8, &ws));
   double* U = ws;
   double* W = U + nU;
   double* cs = W + nU;

@@ -312,7 +312,7 @@ int predict_wide_device(gdml_ctx* ctx, const double* d_xq, int64_t B, double* pa
   const int nparts = (int)((MP + rows_per - 1) / rows_per);
   const int Dp = (D + 15) / 16 * 16;
   double* w;
-  GDML_TRY(ctx_slot(ctx, 7, (2 * MPp * Bc + 2 * MP + Bc + 2 * (int64_t)nparts * Bc + (2 * MPp + Bc) * (int64_t)Dp) * 8, &w));
+  GDML_TRY(ctx_slot(ctx, SLOT_WIDE_WS, (2 * MPp * Bc + 2 * MP + Bc + 2 * (int64_t)nparts * Bc + (2 * MPp + Bc) * (int64_t)Dp) * 8, &w));
   double* S = w;
   double* T = S + MPp * Bc;
   double* nX = T + MPp * Bc;
@@ -370,7 +370,7 @@ int predict_wide_device(gdml_ctx* ctx, const double* d_xq, int64_t B, double* pa
         nz = best;
       }
       double* Pp;
-      GDML_TRY(ctx_slot(ctx, 9, (int64_t)nz * bc * D * 8, &Pp));
+      GDML_TRY(ctx_slot(ctx, SLOT_WIDE_PARTS, (int64_t)nz * bc * D * 8, &Pp));
       dim3 grid((unsigned)ceil_div(D, WT), (unsigned)ceil_div(bc, WT), (unsigned)nz);
       // unchecked loads wherever memory exists: S / T have Bc columns (a multiple of 128 when padded: zeros past bc), and a
       // table row's columns past Dp are the next row's (the last row's: the query block behind the tables) -- they only feed

@@ -6,7 +6,7 @@
 //   Kx_q  (3N x n)   cross-kernel rows: block j = the 3N x 3N block of train.py:97-232 for row point q (un-permuted) and
 //                    column point j (permuted);  k_qq (3N x 3N) the same with i = j = q
 //   Z_q   = (-Kx_q) L^-T                                   (tall_trsm of cg.hip, right-looking: few rows, long factor)
-//   Sig_q = (-k_qq) - Z_q Z_q^T                            (cov_gram_kernel + cov_reduce_kernel)
+//   Sig_q = (-k_qq) - Z_q Z_q^T                            (block_gram.hip + cov_reduce_kernel)
 // in the units of the normalised labels; the host multiplies by std^2 (and its calibration factor).
 //
 // cross_rows_kernel, with x, g the descriptor / compressed Jacobian of q and X, G those of column point j, pi = pi_p,
@@ -21,10 +21,6 @@
 // the pair sums of |d|^2 per atom), every output element is summed over a group in registers by the one thread that owns it.
 #include "common.h"
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-#define UC_SLOT_WS 13    // queries, descriptors, -k_qq, partial Gram tiles, staged output
-#define UC_SLOT_ROWS 14  // (3N B) x K_ld row buffer
 #define UC_LDS_DOUBLES 6000  // per workgroup of the cross kernel (48 KB: two workgroups per CU keep their LDS)
 
 struct CrossArgs {
@@ -186,89 +182,9 @@ static int cross_launch(gdml_ctx* ctx, const double* xq, const double* gq, int b
 }
 
 // ---- Gram step ---------------------------------------------------------------------------------------------------------
-// Sig_q = (-k_qq) - Z_q Z_q^T on the fp64 MFMA pipe.  The 3N x 3N output is cut into 64 x 64 blocks (4 x 4 MFMA tiles of
-// v_mfma_f64_16x16x4_f64); one WAVEFRONT owns (query, lower block pair (I, J), k split s): both operands are rows of Z_q and
-// come straight from global memory as 32-byte runs (lane group g = lane >> 4 feeds k = 4 g + step into MFMA step `step`, the
-// same bijection on both sides -- as in the panel solve of chol.hip), rows past 3N re-read row 3N - 1 and are never stored.
-// The pad columns [n, ld) of Z are zero, so the k loop needs no edge.  The S partial tiles of a block go to a scratch slot
-// and cov_reduce_kernel sums them in the order s = 0 .. S - 1: no atomics, bit-reproducible.  S and the split length
-// depend on n alone, and the diag_only form runs the SAME MFMA sequence for the diagonal tiles (it only leaves the others
-// out), so the marginal variances equal the diagonal of the full covariance bit for bit.
-struct GramArgs {
-  const double* Z;
-  double* part;  // full: [q][pair][s][64 x 64]; diag_only: [q][block][s][64]
-  int64_t ld, L, units;
-  int n3, nblk, npairs, S;
-};
-
-template <bool DIAG>
-__global__ void __launch_bounds__(256) cov_gram_kernel(GramArgs g) {
-  const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
-  const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (unit >= g.units) return;
-  const int s = (int)(unit % g.S);
-  const int64_t up = unit / g.S;
-  const int pr = (int)(up % g.npairs);
-  const int64_t q = up / g.npairs;
-  int I, J;
-  if (DIAG) {
-    I = J = pr;
-  } else {
-    I = (int)((sqrt(8.0 * (double)pr + 1.0) - 1.0) * 0.5);
-    while (I * (I + 1) / 2 > pr) --I;
-    while ((I + 1) * (I + 2) / 2 <= pr) ++I;
-    J = pr - I * (I + 1) / 2;
-  }
-  const int64_t k_beg = (int64_t)s * g.L;
-  const int64_t k_end = k_beg + g.L < g.ld ? k_beg + g.L : g.ld;
-  const double* pa[4];
-  const double* pb[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int ra = I * 64 + 16 * i + li, rb = J * 64 + 16 * i + li;
-    ra = ra < g.n3 ? ra : g.n3 - 1;
-    rb = rb < g.n3 ? rb : g.n3 - 1;
-    pa[i] = g.Z + (q * g.n3 + ra) * g.ld + 4 * lk;
-    pb[i] = g.Z + (q * g.n3 + rb) * g.ld + 4 * lk;
-  }
-  d4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (d4){0.0, 0.0, 0.0, 0.0};
-  for (int64_t k0 = k_beg; k0 < k_end; k0 += 16) {
-    d4 av[4], bv[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) av[i] = *reinterpret_cast<const d4*>(pa[i] + k0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) bv[i] = DIAG ? av[i] : *reinterpret_cast<const d4*>(pb[i] + k0);
-#pragma unroll
-    for (int st = 0; st < 4; ++st)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (!DIAG || i == j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i][st], bv[j][st], acc[i][j], 0, 0, 0);
-  }
-  // f64 MFMA C/D layout: col = lane & 15, row = (lane >> 4) + 4 r
-  if (DIAG) {
-    double* o = g.part + ((q * g.nblk + I) * g.S + s) * 64;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (li == lk + 4 * r) o[16 * i + li] = acc[i][i][r];
-  } else {
-    double* o = g.part + ((q * g.npairs + pr) * g.S + s) * 4096;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[(16 * i + lk + 4 * r) * 64 + 16 * j + li] = acc[i][j][r];
-  }
-}
-
+// Sig_q = (-k_qq) - Z_q Z_q^T: the partial tiles of Z_q Z_q^T come from block_gram_launch (block_gram.hip; a query's rows have
+// no zero prefix, so first = 0), cov_reduce_kernel sums them in the order s = 0 .. S - 1.  The diag_only form runs the same
+// MFMA sequence for the diagonal tiles, so the marginal variances equal the diagonal of the full covariance bit for bit.
 // out = sym(-k_qq) - sum_s partial_s (fixed order).  Full form: both triangles from the lower block pairs; diag_only: (B,3N).
 __global__ void __launch_bounds__(256) cov_reduce_kernel(const double* __restrict__ part, const double* __restrict__ nkqq,
                                                          double* __restrict__ out, int n3, int nblk, int npairs, int S,
@@ -307,45 +223,23 @@ static int uncert_check_queries(gdml_ctx* ctx, const char* who, const double* R,
   return GDML_OK;
 }
 
-// Work buffers of one batch chunk.  The Gram split (S, L) depends on n alone.
+// Work buffers of one batch chunk (the chunk length: option predict.cov_chunk).
 struct UncertPlan {
-  int N, n3, D, nblk, npairs, S;
-  int64_t n, ld, L, per_query, bc;
+  GramSplit g;
+  int N, D;
+  int64_t bc;
   double *R, *xq, *gq, *nkqq, *part, *out, *rows;
 };
 
-// The solve runs on whole 128-row tiles (zero rows behind the last query): an interior tile of the trailing update and an
-// edge tile round differently (chol.hip: acc = -C first vs C - acc last), and which of the two a query's rows meet must not
-// depend on how the batch was cut into chunks.
-static inline int64_t uc_pad_rows(int64_t rows) { return (rows + 127) / 128 * 128; }
-
 static int uncert_plan(gdml_ctx* ctx, int64_t B, bool need_gram, UncertPlan* p) {
   const TrainSet& ts = ctx->ts;
-  p->N = ts.N; p->n3 = 3 * ts.N; p->D = ts.D;
-  p->n = ts.M * p->n3;
-  p->ld = (p->n + 15) / 16 * 16;
-  p->nblk = (p->n3 + 63) / 64;
-  p->npairs = p->nblk * (p->nblk + 1) / 2;
-  p->S = (int)((p->n + 1023) / 1024);
-  if (p->S > 32) p->S = 32;
-  if (p->S < 1) p->S = 1;
-  p->L = ((p->ld + p->S - 1) / p->S + 15) / 16 * 16;
-  p->S = (int)((p->ld + p->L - 1) / p->L);  // no empty split
-  const int64_t n3 = p->n3;
-  const int64_t small = n3 + 4 * (int64_t)p->D + 2 * n3 * n3 + (need_gram ? (int64_t)p->npairs * p->S * 4096 : 0);
-  p->per_query = (n3 * p->ld + small) * 8;
-  // chunk of the batch: the option's cap (default 64 geometries -- 2 GB of rows at n = 63 000), less when free memory is short
-  int64_t bc = ctx_opt_i(ctx, "predict.cov_chunk", 64);
-  if (bc < 1) bc = 1;
-  if (bc > B) bc = B;
-  size_t f = 0, t = 0;
-  HIP_CHECK(ctx, hipMemGetInfo(&f, &t));
-  const int64_t have = (int64_t)f + ctx->slot_bytes[UC_SLOT_WS] + ctx->slot_bytes[UC_SLOT_ROWS];
-  while (bc > 1 && bc * p->per_query + 127 * p->ld * 8 > have / 10 * 9) bc = (bc + 1) / 2;
-  p->bc = bc;
+  p->N = ts.N; p->D = ts.D;
+  p->g = gram_split(ts.M * 3 * ts.N, 3 * ts.N);
+  const int64_t n3 = p->g.n3;
+  const int64_t small = n3 + 4 * (int64_t)p->D + 2 * n3 * n3 + (need_gram ? (int64_t)p->g.npairs * p->g.S * 4096 : 0);
   double* ws;
-  GDML_TRY(ctx_slot(ctx, UC_SLOT_ROWS, uc_pad_rows(bc * n3) * p->ld * 8, &p->rows));
-  GDML_TRY(ctx_slot(ctx, UC_SLOT_WS, bc * small * 8, &ws));
+  GDML_TRY(gram_workspace(ctx, p->g, "predict.cov_chunk", B, small, 0, &p->bc, &p->rows, &ws));
+  const int64_t bc = p->bc;
   p->R = ws;
   p->xq = p->R + bc * n3;
   p->gq = p->xq + bc * p->D;
@@ -372,11 +266,8 @@ extern "C" int gdml_uncert_release(gdml_ctx* ctx) {
   if (!ctx) return GDML_ERR_INVALID;
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->uncert_ready = false;
-  for (int s : {UC_SLOT_WS, UC_SLOT_ROWS}) {
-    if (ctx->slot[s]) GDML_TRY(ctx_free(ctx, ctx->slot[s]));
-    ctx->slot[s] = nullptr;
-    ctx->slot_bytes[s] = 0;
-  }
+  GDML_TRY(ctx_slot_release(ctx, SLOT_GRAM_WS));
+  GDML_TRY(ctx_slot_release(ctx, SLOT_GRAM_ROWS));
   if (ctx->K) {
     GDML_TRY(ctx_free(ctx, ctx->K));
     ctx->K = nullptr;
@@ -401,14 +292,14 @@ extern "C" int gdml_uncert_cross(gdml_ctx* ctx, const double* R, int64_t B, cons
   const double sig = ctx->uncert_ready || ctx->K_sig > 0 ? ctx->K_sig : ctx->model.sig;
   UncertPlan p;
   GDML_TRY(uncert_plan(ctx, B, false, &p));
-  const int64_t n3 = p.n3;
+  const int64_t n3 = p.g.n3, n = p.g.n, ld = p.g.ld;
   for (int64_t b0 = 0; b0 < B; b0 += p.bc) {
     const int bc = (int)(B - b0 < p.bc ? B - b0 : p.bc);
     HIP_CHECK(ctx, hipMemcpyAsync(p.R, R + b0 * n3, bc * n3 * 8, hipMemcpyHostToDevice, ctx->stream));
     GDML_TRY(desc_device(ctx, p.R, bc, p.N, lat, lat_inv, p.xq, p.gq));
-    GDML_TRY(cross_launch(ctx, p.xq, p.gq, bc, p.rows, p.ld, p.nkqq, 1.0, sig));
+    GDML_TRY(cross_launch(ctx, p.xq, p.gq, bc, p.rows, ld, p.nkqq, 1.0, sig));
     if (Kx_out)
-      HIP_CHECK(ctx, hipMemcpy2DAsync(Kx_out + b0 * n3 * p.n, p.n * 8, p.rows, p.ld * 8, p.n * 8, bc * n3,
+      HIP_CHECK(ctx, hipMemcpy2DAsync(Kx_out + b0 * n3 * n, n * 8, p.rows, ld * 8, n * 8, bc * n3,
                                       hipMemcpyDeviceToHost, ctx->stream));
     if (kqq_out)
       HIP_CHECK(ctx, hipMemcpyAsync(kqq_out + b0 * n3 * n3, p.nkqq, bc * n3 * n3 * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -429,9 +320,10 @@ static int cov_common(gdml_ctx* ctx, const double* R, bool on_device, int64_t B,
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
   UncertPlan p;
   GDML_TRY(uncert_plan(ctx, B, true, &p));
-  if (ctx->K_rows != p.n || ctx->K_ld != p.ld)
+  const GramSplit& g = p.g;
+  if (ctx->K_rows != g.n || ctx->K_ld != g.ld)
     return gdml_fail(ctx, GDML_ERR_STATE, "gdml_predict_cov: the resident factor does not belong to the resident training set");
-  const int64_t n3 = p.n3, per_out = full ? n3 * n3 : n3;
+  const int64_t n3 = g.n3, per_out = full ? n3 * n3 : n3;
   phase_begin(ctx);
   for (int64_t b0 = 0; b0 < B; b0 += p.bc) {
     const int bc = (int)(B - b0 < p.bc ? B - b0 : p.bc);
@@ -441,31 +333,24 @@ static int cov_common(gdml_ctx* ctx, const double* R, bool on_device, int64_t B,
       d_R = p.R;
     }
     GDML_TRY(desc_device(ctx, d_R, bc, p.N, lat, lat_inv, p.xq, p.gq));
-    GDML_TRY(cross_launch(ctx, p.xq, p.gq, bc, p.rows, p.ld, p.nkqq, -1.0, ctx->K_sig));
+    GDML_TRY(cross_launch(ctx, p.xq, p.gq, bc, p.rows, g.ld, p.nkqq, -1.0, ctx->K_sig));
     // Z = (-Kx) L^-T.  Right-looking: the rows are few and the factor is long, so every 512-column step updates the whole
     // remaining width in one launch that fills the chip (the left-looking form of the Nystroem build would run 4 tiles deep
     // products per 128 rows)
-    const int64_t rows = (int64_t)bc * n3, rows_pad = uc_pad_rows(rows);
+    const int64_t rows = (int64_t)bc * n3, rows_pad = pad_rows128(rows);
     if (rows_pad > rows)
-      HIP_CHECK(ctx, hipMemsetAsync(p.rows + rows * p.ld, 0, (rows_pad - rows) * p.ld * 8, ctx->stream));
+      HIP_CHECK(ctx, hipMemsetAsync(p.rows + rows * g.ld, 0, (rows_pad - rows) * g.ld * 8, ctx->stream));
     int slot = ktime_begin(ctx);
-    GDML_TRY(tall_trsm(ctx, ctx->K, p.rows, rows_pad, p.n, p.ld, 0));
-    ktime_end(ctx, slot, "uncert_solve", (double)p.n * (double)p.n * (double)n3 * bc);
-    GramArgs g;
-    g.Z = p.rows; g.part = p.part; g.ld = p.ld; g.L = p.L; g.n3 = p.n3; g.nblk = p.nblk; g.S = p.S;
-    g.npairs = full ? p.npairs : p.nblk;
-    g.units = (int64_t)bc * g.npairs * g.S;
+    GDML_TRY(tall_trsm(ctx, ctx->K, p.rows, rows_pad, g.n, g.ld, 0));
+    ktime_end(ctx, slot, "uncert_solve", (double)g.n * (double)g.n * (double)n3 * bc);
     slot = ktime_begin(ctx);
-    if (full)
-      hipLaunchKernelGGL(cov_gram_kernel<false>, dim3((unsigned)ceil_div(g.units, 4)), dim3(256), 0, ctx->stream, g);
-    else
-      hipLaunchKernelGGL(cov_gram_kernel<true>, dim3((unsigned)ceil_div(g.units, 4)), dim3(256), 0, ctx->stream, g);
+    block_gram_launch(ctx, g, p.rows, p.part, bc, !full, 0, 0);
     double* d_out = on_device ? cov_out + b0 * per_out : p.out;
     const int64_t total = bc * per_out;
     hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, p.part, p.nkqq, d_out,
-                       p.n3, p.nblk, p.npairs, p.S, full, total);
-    ctx->launch_counter += 2;
-    ktime_end(ctx, slot, "uncert_gram", 2.0 * (double)p.ld * (full ? (double)n3 * n3 : (double)n3) * bc);
+                       g.n3, g.nblk, g.npairs, g.S, full, total);
+    ctx->launch_counter++;
+    ktime_end(ctx, slot, "uncert_gram", 2.0 * (double)g.ld * (full ? (double)n3 * n3 : (double)n3) * bc);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return gdml_fail(ctx, GDML_ERR_HIP, "cov_gram launch: %s", hipGetErrorString(e));
     if (!on_device) {

@@ -180,3 +180,19 @@ def test_perm2_kernel_keeps_scratch_out_of_its_store_passes_and_inner_loops():
             worst = max(worst, run)
             n_reads = 0
     assert worst < 3, worst
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')
+def test_block_gram_kernel_keeps_the_registers_of_the_kernels_it_replaced():
+    """block_gram_kernel (csrc/block_gram.hip) serves the posterior covariance and the leave-one-out pass, which each had a copy
+    of it (cov_gram_kernel<DIAG>, loo_gram_kernel).  Its speed is its MFMA count per 16 columns and its occupancy -- the 4 x 4
+    accumulator tiles in AGPRs, two (full) / four (diagonal) waves per SIMD, nothing in scratch; the figures are those of
+    the copies it replaced, so that the `first` column rule or a later edit cannot cost either caller anything unnoticed."""
+    text = _assembly('block_gram')
+    for sym, mfma, vgpr, agpr, occupancy in (('_Z17block_gram_kernelILb0EEv13BlockGramArgs', 64, 100, 128, 2),
+                                             ('_Z17block_gram_kernelILb1EEv13BlockGramArgs', 16, 96, 32, 4)):
+        start = text.index('\n' + sym + ':')
+        end = text.index('.Lfunc_end', start)
+        assert sum(1 for l in text[start:end].split('\n') if l.strip().startswith('v_mfma_f64_16x16x4')) == mfma, sym
+        usage = dict(re.findall(r'^; (NumVgprs|NumAgprs|ScratchSize|Occupancy): (\d+)$', text[end:text.index('; COMPUTE_PGM_RSRC2', end)], flags=re.M))
+        assert usage == {'NumVgprs': str(vgpr), 'NumAgprs': str(agpr), 'ScratchSize': '0', 'Occupancy': str(occupancy)}, (sym, usage)
