@@ -171,6 +171,8 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *   predict.cov_global (0)    1: the cross-kernel keeps its per-permutation vectors in global memory (the path of N > 374; tests)
  *   chol.loo_chunk (64)            training points per pass of gdml_loo (their rows of L^-T are 3N n doubles each; fewer when free
  *                         memory is short).  The results do not depend on it
+ *   chol.extend_chunk (64)         points per pass of gdml_factor_extend (their 3N rows are assembled, solved and factored together;
+ *                         fewer when free memory is short).  Different values agree to rounding, not bit for bit
  *   pcg.f32_min_pivot (1e-7)  fp32 form: smallest squared Cholesky pivot of the rounded factor's Gram matrix below which the
  *                         reference's fp64 form is kept (gdml_get_option("pcg.f32_last_min_pivot") reads the last value seen)
  * Unknown keys return GDML_ERR_INVALID. */
@@ -360,6 +362,29 @@ int gdml_predict_cov_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const do
  * Not offered: leave-one-out energies (the integration constant is refitted per fold) and systems with energy constraints. */
 int gdml_loo(gdml_ctx* ctx, const double* alphas, int64_t n, int cov_mode, double* resid_out, double* cov_out,
              double* logdet_out, int* info);
+
+/* Appending b training points to the factor of gdml_uncert_prepare without factoring again (on-the-fly learning: label the
+ * geometries gdml_predict_cov flags, add them, go on).  The reference has no counterpart (it retrains from nothing).  With
+ * A = -K + lam I = L L^T resident (n = 3N M) and m = 3N b new rows the factor is bordered,
+ *   A' = | A  C^T |    L' = | L  0   |    C = -Kx of the new points against the old ones,  W = C L^-T,
+ *        | C  D   |         | W  L_S |    S = D - W W^T = L_S L_S^T,
+ * at n^2 m flops instead of n'^3 / 3: the cross-kernel rows of gdml_predict_cov, its right-looking triangular solve, a split-k
+ * Gram product on the fp64 MFMA pipe and the blocked Cholesky on the m x m Schur complement, in chunks of at most
+ * chol.extend_chunk points (a chunk's rows are part of the factor the next chunk solves against).
+ * R_desc_new (b,D), R_d_desc_new (b,D,3): host descriptors and compressed Jacobians of the new points (gdml_desc_from_R);
+ * they are appended to the resident training set, the new factor (n' = n + m rows, pitch n' rounded up to 16) replaces the
+ * old one and stays prepared: gdml_chol_solve, gdml_predict_cov and gdml_loo work on the enlarged system at once; sig and
+ * lam are those of gdml_uncert_prepare.  The new rows are built in a second buffer, so both matrices are resident for the
+ * duration of the call, and the context changes only after the last chunk has been factored: on ANY error the old factor,
+ * the old training set and the prepared mark are exactly as before.  b = 0 is a no-op.
+ * fp64 throughout, no atomics, every sum in a fixed order: the same sequence of calls on the same context state gives
+ * identical bits (different chunkings of the same points agree to rounding only).
+ * GDML_ERR_STATE without a prepared factor of the resident training set, GDML_ERR_UNSUPPORTED for a factor with
+ * energy-constraint rows or a multi-rank context, GDML_ERR_INVALID for b < 0 or NULL tables, GDML_ERR_OOM when the second
+ * buffer does not fit, GDML_ERR_NOT_PD with *info = order of the failing leading minor of A' (1-based) when a pivot of S is
+ * not positive.  Phase "extend"; kernel timers extend_copy, extend_cross, extend_solve, extend_schur, extend_chol.
+ * Not offered: removing points, systems with energy constraints, a reserved pitch that would avoid the copy. */
+int gdml_factor_extend(gdml_ctx* ctx, const double* R_desc_new, const double* R_d_desc_new, int64_t b, int* info);
 
 /* Test / validation error sums evaluated on the device (replaces the body of the reference's
  * cli.test loop, sgdml/cli.py:1564-1605 with _online_err :1170): predicts B host geometries R,

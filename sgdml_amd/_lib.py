@@ -55,6 +55,7 @@ SIGNATURES = {
     'gdml_predict_cov': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
     'gdml_predict_cov_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
     'gdml_loo': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    'gdml_factor_extend': (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int)]),
     'gdml_kernel_matvec': (C.c_int, [_vp, C.c_double, C.c_int, _vp, C.c_int64, _vp]),
     'gdml_predict_errors': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     'gdml_nystroem_factor': (C.c_int, [_vp, C.c_double, _vp, C.c_int64, _vp, _vp, C.POINTER(C.c_int)]),
@@ -631,6 +632,25 @@ class Context(object):
         self._check(self._lib.gdml_loo(self._h, _ptr(alphas), alphas.size, {None: 0, 'diag': 1, 'full': 2}[cov], _ptr(resid),
                                        _ptr(c), C.byref(logdet), C.byref(info)))
         return resid, c, logdet.value
+
+    def factor_extend(self, R_desc_new, R_d_desc_new):
+        """Append training points (descriptors (b,D), compressed Jacobians (b,D,3)) to the training set and to the factor of
+        uncert_prepare without factoring again (gdml_factor_extend).  Raises numpy.linalg.LinAlgError when the enlarged matrix
+        is not positive definite and MemoryError when the second matrix buffer does not fit; the context is then unchanged."""
+        if not hasattr(self, 'n_atoms'):
+            raise GDMLHipError('factor_extend: no training set resident (train_upload, uncert_prepare)')
+        D = self.n_atoms * (self.n_atoms - 1) // 2
+        R_desc_new = f64(R_desc_new).reshape(-1, D)
+        b = R_desc_new.shape[0]
+        R_d_desc_new = f64(R_d_desc_new)
+        if R_d_desc_new.shape != (b, D, 3):
+            raise ValueError('R_d_desc_new must be the compressed (b,D,3) Jacobian')
+        info = C.c_int(0)
+        self._check(self._lib.gdml_factor_extend(self._h, _ptr(R_desc_new), _ptr(R_d_desc_new), b, C.byref(info)))
+        if b:
+            self._train_fp = None  # the resident set is no longer the one train_upload fingerprinted
+            self.n_train += b
+        return info.value
 
     def predict_errors(self, R, F_ref, E_ref=None, std=1.0, c=0.0, lat_and_inv=None):
         """Eight error sums of a labelled batch, evaluated on the GPU (see gdml_predict_errors)."""

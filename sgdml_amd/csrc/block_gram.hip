@@ -45,10 +45,11 @@ int gram_workspace(gdml_ctx* ctx, const GramSplit& g, const char* chunk_opt, int
 // no atomics, bit-reproducible.  DIAG runs the SAME MFMA sequence for the diagonal tiles (it only leaves the others out).
 // An item whose rows are zero left of column `first` skips the splits wholly left of it (the tile is not written: the caller
 // does not read it) and starts the first split it keeps at `first` rounded down to 16; first = 0 changes nothing.
+// The rows may lie in a wider buffer (pitch > ld: extend.hip sums over the first ld columns of rows of the factor).
 struct BlockGramArgs {
   const double* Z;
   double* part;  // full: [item][pair][s][64 x 64]; DIAG: [item][block][s][64]
-  int64_t ld, L, units, first0, first_stride;
+  int64_t ld, pitch, L, units, first0, first_stride;
   int n3, nblk, npairs, S;
 };
 
@@ -82,8 +83,8 @@ __global__ void __launch_bounds__(256) block_gram_kernel(BlockGramArgs g) {
     int ra = I * 64 + 16 * i + li, rb = J * 64 + 16 * i + li;
     ra = ra < g.n3 ? ra : g.n3 - 1;
     rb = rb < g.n3 ? rb : g.n3 - 1;
-    pa[i] = g.Z + (q * g.n3 + ra) * g.ld + 4 * lk;
-    pb[i] = g.Z + (q * g.n3 + rb) * g.ld + 4 * lk;
+    pa[i] = g.Z + (q * g.n3 + ra) * g.pitch + 4 * lk;
+    pb[i] = g.Z + (q * g.n3 + rb) * g.pitch + 4 * lk;
   }
   d4 acc[4][4];
 #pragma unroll
@@ -124,9 +125,9 @@ __global__ void __launch_bounds__(256) block_gram_kernel(BlockGramArgs g) {
 }
 
 void block_gram_launch(gdml_ctx* ctx, const GramSplit& s, const double* Z, double* part, int64_t items, bool diag, int64_t first0,
-                       int64_t first_stride) {
+                       int64_t first_stride, int64_t pitch) {
   BlockGramArgs g;
-  g.Z = Z; g.part = part; g.ld = s.ld; g.L = s.L; g.first0 = first0; g.first_stride = first_stride;
+  g.Z = Z; g.part = part; g.ld = s.ld; g.pitch = pitch > 0 ? pitch : s.ld; g.L = s.L; g.first0 = first0; g.first_stride = first_stride;
   g.n3 = s.n3; g.nblk = s.nblk; g.S = s.S;
   g.npairs = diag ? s.nblk : s.npairs;
   g.units = items * g.npairs * g.S;

@@ -305,9 +305,13 @@ static inline int64_t pad_rows128(int64_t rows) { return (rows + 127) / 128 * 12
 // chunk * ws_per_item doubles
 int gram_workspace(gdml_ctx* ctx, const GramSplit& g, const char* chunk_opt, int64_t items, int64_t ws_per_item, int64_t ws_fixed,
                    int64_t* chunk, double** rows, double** ws);
-// partial tiles of Z_i Z_i^T for `items` row blocks; item i is zero left of column first0 + i first_stride.  One launch, not timed
+// partial tiles of Z_i Z_i^T for `items` row blocks; item i is zero left of column first0 + i first_stride.  One launch, not timed.
+// pitch: row pitch of Z when it is not g.ld (0 = g.ld)
 void block_gram_launch(gdml_ctx* ctx, const GramSplit& g, const double* Z, double* part, int64_t items, bool diag, int64_t first0,
-                       int64_t first_stride);
+                       int64_t first_stride, int64_t pitch = 0);
+// sgn * (cross-kernel rows) of bc device-resident queries against M column points (uncert.hip; extend.hip)
+int cross_rows_launch(gdml_ctx* ctx, const double* xt, const double* gt, int64_t M, const double* xq, const double* gq, int bc,
+                      double* rows, int64_t ld, double* kqq, double sgn, double sig, const char* tname);
 void shard_points(const gdml_ctx* ctx, int64_t M, int64_t* p0, int64_t* p1, int64_t* pts_per);
 // Layout of the replicated device vectors of the sharded solvers (Nystroem factor rows, PCG vectors, mat-vec in / out).
 //   no communicator (world <= 1): the reference order, n entries, no padding;

@@ -1,0 +1,246 @@
+// Appending training points to the resident Cholesky factor without factoring again (no counterpart in the reference, which
+// retrains from nothing).
+//
+// Conventions: A = -K + lam I = L L^T resident in ctx->K (lower triangle, row-major, pitch K_ld = n rounded up
+// to 16), n = 3N M.  Appending b points (m = 3N b rows) borders the matrix and its factor:
+//   A' = | A  C^T |     L' = | L  0   |     C   = -Kx of the new points against the old ones  (cross_rows_kernel of uncert.hip)
+//        | C  D   |          | W  L_S |     W   = C L^-T                                       (tall_trsm of cg.hip, right-looking)
+//                                           S   = D - W W^T = L_S L_S^T                        (block_gram.hip + schur_reduce_kernel,
+//                                                                                               chol_factor_device)
+// The points go through in chunks (option chol.extend_chunk); a chunk's rows are rows of L' once it is through, and the next chunk
+// solves against them as well.  The rows are built in place in a NEW buffer of pitch n' rounded up to 16 (the invariant
+// K_ld == round16(K_rows) the other users of the factor rely on), into which the lower triangle of L is copied first; the old
+// buffer, the old training-set tables and every flag of the context are replaced only after the last chunk has been factored,
+// so a failure (no memory, a non-positive pivot) leaves the context as it was.
+// The Schur complement of a chunk is factored in a work buffer of its own and stored back: its place in the factor starts at
+// column n, which need not be a multiple of 4, and the panel solves of chol_factor_device want 32-byte aligned rows.
+#include "common.h"
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+// Lower triangle of src (pitch lds, n rows) into dst (pitch ldd >= lds): row r, columns 0 .. r rounded up to the 64-column
+// grid of the diagonal blocks (what the old buffer held there: the solves load whole diagonal blocks), as 32-byte groups; the
+// rest of the row up to the 512-column panel grid is zeroed, beyond it nothing reads.  Both pitches are multiples of 16.
+// A workgroup takes rows r and n - 1 - r together: every workgroup moves about the same number of bytes.
+__global__ void __launch_bounds__(256) extend_copy_lower_kernel(const double* __restrict__ src, int64_t lds, double* __restrict__ dst,
+                                                                int64_t ldd, int64_t n) {
+  const int64_t half = (n + 1) / 2;
+  for (int64_t i = blockIdx.x; i < half; i += gridDim.x) {
+    for (int k = 0; k < 2; ++k) {
+      const int64_t r = k == 0 ? i : n - 1 - i;
+      if (k == 1 && r == i) break;
+      const d4* __restrict__ s = reinterpret_cast<const d4*>(src + r * lds);
+      d4* __restrict__ d = reinterpret_cast<d4*>(dst + r * ldd);
+      int64_t c_copy = (r / 64 + 1) * 64, c_zero = (r / 512 + 1) * 512;
+      if (c_copy > lds) c_copy = lds;
+      if (c_zero > ldd) c_zero = ldd;
+      for (int64_t v = threadIdx.x; v < c_copy / 4; v += 256) d[v] = s[v];
+      for (int64_t v = c_copy / 4 + threadIdx.x; v < c_zero / 4; v += 256) d[v] = (d4){0.0, 0.0, 0.0, 0.0};
+    }
+  }
+}
+
+// S = (D + lam I) - W W^T on the lower triangle of a chunk of mc rows: W W^T over the columns [0, n16) comes as the partial
+// tiles of block_gram_kernel (one item; summed here in the order s = 0 .. S - 1), the columns [n16, ncur) that do not fill a
+// group of 16 are added behind them in index order, one fused multiply-add each.  One workgroup per lower 64 x 64 block pair;
+// every element has one owner.  W: the chunk's rows in the factor buffer (pitch ld), D their columns from ncur on.
+struct SchurArgs {
+  const double* part;  // [pair][s][64 x 64]
+  const double* W;
+  double* S;           // mc x mc, pitch lds
+  int64_t ld, lds, n16, ncur;
+  int mc, nsplit;
+  double lam;
+};
+
+__global__ void __launch_bounds__(256) schur_reduce_kernel(SchurArgs a) {
+  const int pr = blockIdx.x;
+  int I = (int)((sqrt(8.0 * (double)pr + 1.0) - 1.0) * 0.5);
+  while (I * (I + 1) / 2 > pr) --I;
+  while ((I + 1) * (I + 2) / 2 <= pr) ++I;
+  const int J = pr - I * (I + 1) / 2;
+  const double* __restrict__ p = a.part + (int64_t)pr * a.nsplit * 4096;
+  for (int e = threadIdx.x; e < 4096; e += 256) {
+    const int r = I * 64 + (e >> 6), c = J * 64 + (e & 63);
+    if (r >= a.mc || c > r) continue;
+    double acc = 0.0;
+    for (int s = 0; s < a.nsplit; ++s) acc += p[(int64_t)s * 4096 + e];
+    const double* __restrict__ wr = a.W + (int64_t)r * a.ld;
+    const double* __restrict__ wc = a.W + (int64_t)c * a.ld;
+    for (int64_t k = a.n16; k < a.ncur; ++k) acc = __builtin_fma(wr[k], wc[k], acc);
+    const double d = wr[a.ncur + c] + (r == c ? a.lam : 0.0);
+    a.S[(int64_t)r * a.lds + c] = d - acc;
+  }
+}
+
+// the factored chunk back into its place: row r of the chunk, columns ncur .. ncur + r of the factor
+__global__ void __launch_bounds__(256) extend_store_lower_kernel(const double* __restrict__ S, int64_t lds, double* __restrict__ dst,
+                                                                 int64_t ld) {
+  const int64_t r = blockIdx.x;
+  for (int64_t c = threadIdx.x; c <= r; c += 256) dst[r * ld + c] = S[r * lds + c];
+}
+
+static int64_t extend_ws_doubles(int64_t n1, int64_t bc, int64_t n3) {
+  const int64_t mc = bc * n3, nblk = (mc + 63) / 64, npairs = nblk * (nblk + 1) / 2;
+  int64_t S = (n1 + 1023) / 1024;  // gram_split never plans more splits for n <= n1
+  if (S > 32) S = 32;
+  return bc * n3 * n3 + npairs * S * 4096 + mc * ((mc + 15) / 16 * 16);
+}
+
+extern "C" int gdml_factor_extend(gdml_ctx* ctx, const double* R_desc_new, const double* R_d_desc_new, int64_t b, int* info) {
+  if (!ctx) return GDML_ERR_INVALID;
+  if (info) *info = 0;
+  if (b < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_factor_extend: b < 0");
+  if (b > 0 && (!R_desc_new || !R_d_desc_new))
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_factor_extend: R_desc_new or R_d_desc_new is NULL");
+  if (comm_active(ctx) && ctx->world > 1)
+    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_factor_extend: the factor of a multi-rank context is distributed");
+  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_factor_extend: call gdml_train_upload first");
+  if (ctx->K && ctx->K_factored && ctx->K_use_E)
+    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_factor_extend: the resident factor carries energy-constraint rows");
+  if (!ctx->uncert_ready || !ctx->K || !ctx->K_factored)
+    return gdml_fail(ctx, GDML_ERR_STATE,
+                     "gdml_factor_extend: no factor prepared (gdml_uncert_prepare; an assembly since then overwrote it)");
+  TrainSet& ts = ctx->ts;
+  const int64_t M0 = ts.M, n3 = 3 * (int64_t)ts.N, D = ts.D;
+  const int64_t n0 = M0 * n3, ld0 = (n0 + 15) / 16 * 16;
+  if (ctx->K_rows != n0 || ctx->K_cols != n0 || ctx->K_ld != ld0 || ctx->K_sharded)
+    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_factor_extend: the resident factor does not belong to the resident training set");
+  if (b == 0) return GDML_OK;
+  const int64_t n1 = n0 + b * n3, ld1 = (n1 + 15) / 16 * 16;
+  if (n1 > INT32_MAX) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_factor_extend: %lld rows exceed the factorisation's range", (long long)n1);
+  HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // the Gram work buffers of gdml_predict_cov / gdml_loo were sized for n: they are carved anew at the next call
+  GDML_TRY(ctx_slot_release(ctx, SLOT_GRAM_WS));
+  GDML_TRY(ctx_slot_release(ctx, SLOT_GRAM_ROWS));
+
+  // everything new lives in buffers of its own until the commit
+  double *Kn = nullptr, *x1 = nullptr, *g1 = nullptr, *ws = nullptr;
+  auto drop = [&](int rc) {
+    (void)hipStreamSynchronize(st);
+    if (ws) (void)ctx_free(ctx, ws);
+    if (g1) (void)ctx_free(ctx, g1);
+    if (x1) (void)ctx_free(ctx, x1);
+    if (Kn) (void)ctx_free(ctx, Kn);
+    return rc;
+  };
+#define EXT_TRY(expr)                         \
+  do {                                        \
+    const int rc_e = (expr);                  \
+    if (rc_e != GDML_OK) return drop(rc_e);   \
+  } while (0)
+#define EXT_HIP(call)                                                                                               \
+  do {                                                                                                              \
+    const hipError_t e_e = (call);                                                                                  \
+    if (e_e != hipSuccess)                                                                                          \
+      return drop(gdml_fail(ctx, e_e == hipErrorOutOfMemory ? GDML_ERR_OOM : GDML_ERR_HIP, "%s failed: %s (%s:%d)", \
+                            #call, hipGetErrorString(e_e), __FILE__, __LINE__));                                    \
+  } while (0)
+
+  // the matrix with up to 127 pad rows behind it: the solve runs on whole 128-row tiles (pad_rows128)
+  const int64_t Kn_bytes = (n1 + 127) * ld1 * 8;
+  EXT_TRY(ctx_alloc(ctx, (void**)&Kn, Kn_bytes));
+  EXT_TRY(ctx_alloc(ctx, (void**)&x1, (M0 + b) * D * 8));
+  EXT_TRY(ctx_alloc(ctx, (void**)&g1, (M0 + b) * D * 24));
+  // chunk length: the option's cap, the point count, then halved while the work buffers exceed 90 % of free memory
+  int64_t bc = ctx_opt_i(ctx, "chol.extend_chunk", 64);
+  if (bc < 1) bc = 1;
+  if (bc > b) bc = b;
+  size_t mem_free = 0, mem_total = 0;
+  EXT_HIP(hipMemGetInfo(&mem_free, &mem_total));
+  while (bc > 1 && extend_ws_doubles(n1, bc, n3) * 8 > (int64_t)mem_free / 10 * 9) bc = (bc + 1) / 2;
+  EXT_TRY(ctx_alloc(ctx, (void**)&ws, extend_ws_doubles(n1, bc, n3) * 8));
+  const int64_t mc_max = bc * n3, lds = (mc_max + 15) / 16 * 16;
+  double* const Sb = ws;                      // Schur complement of a chunk, pitch lds (32-byte aligned rows: first)
+  double* const kqq = Sb + mc_max * lds;      // the cross-kernel's k_qq output (the same blocks arrive as columns of D)
+  double* const part = kqq + bc * n3 * n3;
+
+  phase_begin(ctx);
+  EXT_HIP(hipMemcpyAsync(x1, ts.x, M0 * D * 8, hipMemcpyDeviceToDevice, st));
+  EXT_HIP(hipMemcpyAsync(g1, ts.g, M0 * D * 24, hipMemcpyDeviceToDevice, st));
+  EXT_HIP(hipMemcpyAsync(x1 + M0 * D, R_desc_new, b * D * 8, hipMemcpyHostToDevice, st));
+  EXT_HIP(hipMemcpyAsync(g1 + M0 * D * 3, R_d_desc_new, b * D * 24, hipMemcpyHostToDevice, st));
+  int slot = ktime_begin(ctx);
+  {
+    int64_t grid = (n0 + 1) / 2;
+    if (grid > 64 * (int64_t)ctx->num_cus) grid = 64 * (int64_t)ctx->num_cus;
+    hipLaunchKernelGGL(extend_copy_lower_kernel, dim3((unsigned)grid), dim3(256), 0, st, ctx->K, ld0, Kn, ld1, n0);
+    ctx->launch_counter++;
+  }
+  ktime_end(ctx, slot, "extend_copy", (double)n0 * (double)(n0 + 1) * 8.0);  // bytes read + written
+
+  int64_t n_cur = n0, M_cur = M0;
+  for (int64_t p0 = 0; p0 < b; p0 += bc) {
+    const int64_t c = b - p0 < bc ? b - p0 : bc, mc = c * n3, rows_pad = pad_rows128(mc);
+    double* const rows = Kn + n_cur * ld1;
+    if (rows_pad > mc) EXT_HIP(hipMemsetAsync(rows + mc * ld1, 0, (rows_pad - mc) * ld1 * 8, st));
+    // [C | D] = -Kx of the chunk's points against the old points, the earlier chunks and the chunk itself
+    EXT_TRY(cross_rows_launch(ctx, x1, g1, M_cur + c, x1 + M_cur * D, g1 + M_cur * D * 3, (int)c, rows, ld1, kqq, -1.0, ctx->K_sig,
+                              "extend_cross"));
+    // W = C L'^-T over the n_cur finished rows, right-looking (few rows, long factor: uncert.hip)
+    slot = ktime_begin(ctx);
+    EXT_TRY(tall_trsm(ctx, Kn, rows, rows_pad, n_cur, ld1, 0));
+    ktime_end(ctx, slot, "extend_solve", (double)n_cur * (double)n_cur * (double)mc);
+    // S = D + lam I - W W^T
+    slot = ktime_begin(ctx);
+    SchurArgs a;
+    a.part = part; a.W = rows; a.S = Sb; a.ld = ld1; a.lds = lds; a.n16 = n_cur / 16 * 16; a.ncur = n_cur;
+    a.mc = (int)mc; a.nsplit = 0; a.lam = ctx->K_lam;
+    EXT_HIP(hipMemsetAsync(Sb, 0, mc * lds * 8, st));  // (the factorisation loads whole diagonal blocks: no stale upper triangle)
+    const int nblk = (int)((mc + 63) / 64), npairs = nblk * (nblk + 1) / 2;
+    if (a.n16 > 0) {
+      const GramSplit g = gram_split(a.n16, (int)mc);
+      a.nsplit = g.S;
+      block_gram_launch(ctx, g, rows, part, 1, false, 0, 0, ld1);
+    }
+    hipLaunchKernelGGL(schur_reduce_kernel, dim3((unsigned)npairs), dim3(256), 0, st, a);
+    ctx->launch_counter++;
+    ktime_end(ctx, slot, "extend_schur", (double)mc * (double)mc * (double)n_cur);
+    EXT_HIP(hipGetLastError());
+    slot = ktime_begin(ctx);
+    int inf = 0;
+    EXT_TRY(chol_factor_device(ctx, Sb, mc, lds, &inf));
+    if (inf != 0) {
+      if (info) *info = (int)(n_cur + inf);
+      return drop(gdml_fail(ctx, GDML_ERR_NOT_PD, "gdml_factor_extend: %lld-th leading minor of the extended matrix is not positive definite",
+                            (long long)(n_cur + inf)));
+    }
+    hipLaunchKernelGGL(extend_store_lower_kernel, dim3((unsigned)mc), dim3(256), 0, st, Sb, lds, rows + n_cur, ld1);
+    ctx->launch_counter++;
+    ktime_end(ctx, slot, "extend_chol", (double)mc * (double)mc * (double)mc / 3.0);
+    EXT_HIP(hipGetLastError());
+    n_cur += mc;
+    M_cur += c;
+  }
+  EXT_TRY(phase_end(ctx, "extend"));
+  EXT_HIP(hipStreamSynchronize(st));
+#undef EXT_TRY
+#undef EXT_HIP
+
+  // ---- commit: nothing below fails half way (ctx_free of a tracked pointer on an idle stream)
+  (void)ctx_free(ctx, ws);
+  (void)ctx_free(ctx, ctx->K);
+  ctx->K = Kn;
+  ctx->K_bytes = Kn_bytes;
+  ctx->K_rows = ctx->K_cols = ctx->K_rows_global = n1;
+  ctx->K_ld = ld1;
+  ctx->K_extra = 0;
+  ctx->K_rhs_row = false;
+  ctx->K_factored = true;
+  ctx->precon = nullptr;
+  // the training set: the dense tables derived from the old one are built again when an assembly next asks for them
+  (void)ctx_free(ctx, ts.x);
+  (void)ctx_free(ctx, ts.g);
+  (void)ctx_free(ctx, ts.XF);
+  (void)ctx_free(ctx, ts.GD);
+  (void)ctx_free(ctx, ts.TS);
+  (void)ctx_free(ctx, ts.p2);
+  (void)ctx_free(ctx, ts.p2_TP);
+  ts.XF = ts.GD = ts.TS = ts.p2_TP = nullptr;
+  ts.p2 = nullptr;
+  ts.x = x1;
+  ts.g = g1;
+  ts.M = M0 + b;
+  return GDML_OK;
+}

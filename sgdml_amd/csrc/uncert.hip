@@ -142,14 +142,15 @@ __global__ void __launch_bounds__(256) cross_rows_kernel(CrossArgs a) {
   }
 }
 
-// sgn * Kx of bc device-resident queries into `rows` (pitch ld) and sgn * k_qq into `kqq`
-static int cross_launch(gdml_ctx* ctx, const double* xq, const double* gq, int bc, double* rows, int64_t ld, double* kqq,
-                        double sgn, double sig) {
+// sgn * Kx of bc device-resident queries against the M column points (xt, gt) into `rows` (pitch ld) and sgn * k_qq into
+// `kqq`; permutations and molecule size are those of the resident training set, the launch is timed as `tname`
+int cross_rows_launch(gdml_ctx* ctx, const double* xt, const double* gt, int64_t M, const double* xq, const double* gq, int bc,
+                      double* rows, int64_t ld, double* kqq, double sgn, double sig, const char* tname) {
   const TrainSet& ts = ctx->ts;
   CrossArgs a;
-  a.xq = xq; a.gq = gq; a.xt = ts.x; a.gt = ts.g; a.perm = ts.perm; a.pinv = ts.pinv;
+  a.xq = xq; a.gq = gq; a.xt = xt; a.gt = gt; a.perm = ts.perm; a.pinv = ts.pinv;
   a.rows = rows; a.kqq = kqq; a.gws = nullptr;
-  a.ld = ld; a.M = ts.M; a.items = (int64_t)bc * (ts.M + 1);
+  a.ld = ld; a.M = M; a.items = (int64_t)bc * (M + 1);
   a.B = bc; a.N = ts.N; a.D = ts.D; a.P = ts.P;
   a.WS = 16 * ts.N + 2;
   a.sig = sig; a.sgn = sgn;
@@ -171,7 +172,7 @@ static int cross_launch(gdml_ctx* ctx, const double* xq, const double* gq, int b
   hipLaunchKernelGGL(cross_rows_kernel, dim3((unsigned)grid), dim3(256), lds, ctx->stream, a);
   ctx->launch_counter++;
   // algorithmic work: bytes written
-  ktime_end(ctx, slot, "uncert_cross", (double)a.items * 9.0 * ts.N * (double)ts.N * 8.0);
+  ktime_end(ctx, slot, tname, (double)a.items * 9.0 * ts.N * (double)ts.N * 8.0);
   hipError_t e = hipGetLastError();
   int rc = e == hipSuccess ? GDML_OK : gdml_fail(ctx, GDML_ERR_HIP, "cross_rows launch: %s", hipGetErrorString(e));
   if (a.gws) {
@@ -179,6 +180,12 @@ static int cross_launch(gdml_ctx* ctx, const double* xq, const double* gq, int b
     if (rc == GDML_OK) rc = rc2;
   }
   return rc;
+}
+
+// the same against the resident training set
+static int cross_launch(gdml_ctx* ctx, const double* xq, const double* gq, int bc, double* rows, int64_t ld, double* kqq,
+                        double sgn, double sig) {
+  return cross_rows_launch(ctx, ctx->ts.x, ctx->ts.g, ctx->ts.M, xq, gq, bc, rows, ld, kqq, sgn, sig, "uncert_cross");
 }
 
 // ---- Gram step ---------------------------------------------------------------------------------------------------------

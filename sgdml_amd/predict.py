@@ -5,11 +5,18 @@ mode (``predict()`` with cached descriptors, predict.py:1221-1233) follow the re
 """
 import logging
 import sys
+import timeit
 
 import numpy as np
 
 from . import _lib
 from .utils.desc import Desc
+
+
+def integration_constant(E_ref, E_pred):
+    """The reference's rule for the energy offset c (train.py:1090-1258): the mean of E_ref - E_pred, E_pred predicted at c = 0.
+    Shared by GDMLTrain._recov_int_const and GDMLPredict.add_training_points."""
+    return np.sum(E_ref - E_pred) / E_ref.shape[0]
 
 
 class GDMLPredict(object):
@@ -93,6 +100,12 @@ class GDMLPredict(object):
         self._use_E_cstr = bool(model['use_E_cstr']) if 'use_E_cstr' in model else 'alphas_E' in model
         self._alphas_F = np.asarray(model['alphas_F'], dtype=np.float64).ravel() if 'alphas_F' in model else None
         self.uncertainty_scale = 1.0
+        # add_training_points / export_model: the model's other keys, J alpha, and what prepare_uncertainty(R, F) leaves behind
+        # (Cartesian geometries, compressed Jacobians and normalised labels of the training set)
+        self._model = dict(model)
+        self._R_d_desc_alpha = np.asarray(model['R_d_desc_alpha'], dtype=np.float64)
+        self._unc_R = self._unc_gd = self._unc_y = None
+        self._n_added = 0
 
     def __del__(self):
         for ctx in getattr(self, '_replicas', []):
@@ -256,6 +269,7 @@ class GDMLPredict(object):
         if not np.allclose(xd, self._R_desc_train, rtol=1e-10, atol=0.0):
             raise ValueError("R_train does not reproduce the model's training descriptors (wrong geometries or order)")
         scale = 1.0
+        y = None
         if F_train is not None:
             if self._alphas_F is None:
                 raise ValueError("calibration needs the model's 'alphas_F'")
@@ -267,6 +281,7 @@ class GDMLPredict(object):
         self._train_resident = False  # the training-set mode uploads its own descriptors again when it is used next
         self._ctx.uncert_prepare(self.sig, self._lam)
         self.uncertainty_scale = scale
+        self._unc_R, self._unc_gd, self._unc_y = (R_train.copy(), gd, y) if y is not None else (None, None, None)
 
     def release_uncertainty(self):
         """Free the resident factor of prepare_uncertainty()."""
@@ -333,6 +348,98 @@ class GDMLPredict(object):
             out['log_marginal_likelihood'] = float(-0.5 * (-np.dot(y, alphas)) / s2 - 0.5 * (logdet + n * np.log(s2))
                                                    - 0.5 * n * np.log(2.0 * np.pi))
         return out
+
+    # ---- growing the training set through the resident factor (csrc/extend.hip)
+
+    def add_training_points(self, R_new, F_new, E=None):
+        """Add labelled geometries R_new (b,3N), F_new (b,3N) to the model WITHOUT retraining: the factor of
+        prepare_uncertainty(R_train, F_train) -- which must have been called with F_train -- is bordered by the new points'
+        rows on the first GPU (n^2 3N b flops instead of n'^3 / 3), the coefficients of the enlarged system are solved through it
+        and every table the predictor holds is refreshed, on all replicas.  The labels are normalised with the model's
+        EXISTING std: predictions do not depend on it (alphas = -A^-1 F / std, F_hat = std (... alphas)), so the result is the
+        model a retraining on the enlarged set gives.  predict(), predict_uncertainty() and loo_errors() then work on M + b
+        points; `uncertainty_scale` is recalibrated on the enlarged set.
+
+        E: energies of ALL M + b training points in model order; the integration constant c is then recomputed by the
+        trainer's rule (mean of E - E_pred at c = 0).  Without E, c is kept.
+
+        Raises ValueError without the labelled prepare_uncertainty, NotImplementedError for models with energy constraints,
+        numpy.linalg.LinAlgError when the enlarged matrix is not positive definite (a duplicate geometry at tiny lam) and
+        MemoryError when old and new factor do not fit side by side; the model is unchanged after any of them.
+        Returns {'n_train', 'c_updated', 'phase_ms': {'extend', 'solve'} device times, 'host_ms': {...} wall times of the
+        steps, 'kernel_ms': per-phase kernel times when the context is profiling}."""
+        if self._use_E_cstr:
+            raise NotImplementedError('adding training points to models with energy constraints is not supported')
+        if self._unc_y is None:
+            raise ValueError('add_training_points needs prepare_uncertainty(R_train, F_train) with the training labels first')
+        n3 = 3 * self.n_atoms
+        R_new = np.asarray(R_new, dtype=np.float64)
+        if R_new.size % n3:
+            raise ValueError('R_new holds {} values, not a multiple of 3N = {}'.format(R_new.size, n3))
+        R_new = R_new.reshape(-1, n3)
+        b = R_new.shape[0]
+        F_new = np.asarray(F_new, dtype=np.float64)
+        if F_new.size != b * n3:
+            raise ValueError('F_new holds {} values for {} geometries of {} atoms'.format(F_new.size, b, self.n_atoms))
+        if E is not None:
+            E = np.asarray(E, dtype=np.float64).ravel()
+            if E.size != self.n_train + b:
+                raise ValueError('E holds {} energies, the enlarged training set has {} points'.format(E.size, self.n_train + b))
+        ctx = self._ctx
+        t = [timeit.default_timer()]
+        xd, gd = ctx.desc_from_R(R_new, self.n_atoms, self.lat_and_inv)
+        t.append(timeit.default_timer())
+        ctx.factor_extend(xd, gd)  # raises with the context untouched
+        t.append(timeit.default_timer())
+        y = np.concatenate([self._unc_y, F_new.ravel() / self.std])
+        alphas = ctx.chol_solve(y)
+        t.append(timeit.default_timer())
+        self._unc_y = y
+        self._unc_R = np.concatenate([self._unc_R, R_new])
+        self._unc_gd = np.concatenate([self._unc_gd, gd])
+        self._R_desc_train = np.ascontiguousarray(np.concatenate([self._R_desc_train, xd]))
+        self._alphas_F = alphas
+        self._R_d_desc_alpha = self.desc.d_desc_dot_vec(self._unc_gd, alphas.reshape(-1, n3))
+        self.n_train += b
+        self.chunk_size = self.n_train
+        self._n_added += b
+        for c_ in [ctx] + self._replicas:
+            c_.predict_upload_model(self._R_desc_train, self._R_d_desc_alpha, self._tril_perms, self.sig, None)
+        self._replicas_stale = False
+        self._train_resident = False
+        self.uncertainty_scale = float(-np.dot(y, alphas) / y.size)
+        if E is not None:
+            self.c = 0.0
+            self.c = float(integration_constant(E, self.predict(self._unc_R)[0]))
+        t.append(timeit.default_timer())
+        out = {'n_train': self.n_train, 'c_updated': E is not None,
+               'phase_ms': {'extend': ctx.phase_ms('extend')[0] if b else 0.0, 'solve': ctx.phase_ms('solve')[0]},
+               'host_ms': dict(zip(('desc', 'extend', 'solve', 'model'), [1e3 * (t[i + 1] - t[i]) for i in range(4)]))}
+        kern = {k: ctx.kernel_stat(k)[0] for k in ('extend_copy', 'extend_cross', 'extend_solve', 'extend_schur', 'extend_chol')}
+        if any(kern.values()):
+            out['kernel_ms'] = kern
+        return out
+
+    def export_model(self):
+        """The current model as a dict in the reference's schema (what GDMLPredict and the model files take): the keys the
+        constructor was given, with R_desc, R_d_desc_alpha, alphas_F, c and std as they are now.  After add_training_points
+        idxs_train carries -1 for every added point (they come from no dataset index) and the stored validation errors are
+        reset to NaN, as the trainer sets them for a model that has not been validated."""
+        m = dict(self._model)
+        m['R_desc'] = np.ascontiguousarray(self._R_desc_train.T)
+        m['R_d_desc_alpha'] = self._R_d_desc_alpha
+        if self._alphas_F is not None:
+            m['alphas_F'] = self._alphas_F
+        m['c'] = self.c
+        m['std'] = self.std
+        if self._n_added:
+            if 'idxs_train' in m:
+                m['idxs_train'] = np.concatenate([np.asarray(m['idxs_train']).astype(np.int64),
+                                                  -np.ones(self._n_added, dtype=np.int64)])
+            m['f_err'] = {'mae': np.nan, 'rmse': np.nan}
+            if 'e_err' in m:
+                m['e_err'] = {'mae': np.nan, 'rmse': np.nan}
+        return m
 
     def predict(self, R=None, return_E=True):
         """Energies (B,) and forces (B,3N) for geometries R (B,3N); R=None -> training-set mode."""

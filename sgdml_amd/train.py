@@ -12,7 +12,7 @@ import numpy as np
 
 from . import __version__, DONE, NOT_DONE
 from . import _lib
-from .predict import GDMLPredict
+from .predict import GDMLPredict, integration_constant
 from .solvers.analytic import Analytic
 from .utils import io
 from .utils.desc import Desc
@@ -454,7 +454,7 @@ class GDMLTrain(object):
             self.log.warning(
                 'Potentially inconsistent scales in energy vs. force labels detected! (factor ~{:.2f})'.format(e_fact)
             )
-        return np.sum(E_ref - E_pred) / E_ref.shape[0]
+        return integration_constant(E_ref, E_pred)
 
     # ------------------------------------------------------------------ kernel matrix (semi-public)
 
