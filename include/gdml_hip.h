@@ -173,6 +173,8 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *                         memory is short).  The results do not depend on it
  *   chol.extend_chunk (64)         points per pass of gdml_factor_extend (their 3N rows are assembled, solved and factored together;
  *                         fewer when free memory is short).  Different values agree to rounding, not bit for bit
+ *   chol.remove_chunk (64)         removed points per sweep of gdml_factor_remove; a sweep never takes more than 128 columns
+ *                         of L[kept, removed] (the LDS of its kernels).  Different values agree to rounding, not bit for bit
  *   pcg.f32_min_pivot (1e-7)  fp32 form: smallest squared Cholesky pivot of the rounded factor's Gram matrix below which the
  *                         reference's fp64 form is kept (gdml_get_option("pcg.f32_last_min_pivot") reads the last value seen)
  * Unknown keys return GDML_ERR_INVALID. */
@@ -383,8 +385,35 @@ int gdml_loo(gdml_ctx* ctx, const double* alphas, int64_t n, int cov_mode, doubl
  * energy-constraint rows or a multi-rank context, GDML_ERR_INVALID for b < 0 or NULL tables, GDML_ERR_OOM when the second
  * buffer does not fit, GDML_ERR_NOT_PD with *info = order of the failing leading minor of A' (1-based) when a pivot of S is
  * not positive.  Phase "extend"; kernel timers extend_copy, extend_cross, extend_solve, extend_schur, extend_chol.
- * Not offered: removing points, systems with energy constraints, a reserved pitch that would avoid the copy. */
+ * Not offered: systems with energy constraints, a reserved pitch that would avoid the copy (removing points:
+ * gdml_factor_remove). */
 int gdml_factor_extend(gdml_ctx* ctx, const double* R_desc_new, const double* R_d_desc_new, int64_t b, int* info);
+
+/* Removing b training points from the factor of gdml_uncert_prepare without factoring again (a label that turned out wrong
+ * under gdml_loo, a window of fixed size over a trajectory).  The reference has no counterpart.  idx: b distinct host indices
+ * of training points in the resident order; the kept points keep their relative order.  With L_c = L[kept, kept] and
+ * V = L[kept, removed] (m = 3N b columns)
+ *   A_kept = L_c L_c^T + V V^T = L' L'^T,   [L_c V] Q = [L' 0]  with Q orthogonal:
+ * a rank-m positive update of the rows behind the first removed point, at O(m n^2) flops and one read and write of the
+ * factor instead of n'^3 / 3.  L_c and V are gathered into a second buffer (n' = n - m rows, pitch n' rounded up to 16) and
+ * a side buffer; then, 64 columns at a time, a Householder LQ of [L_kk V_k] in one workgroup (reflectors e_i + [0; v_i],
+ * kept as a WY pair) and its application to the rows below on the fp64 MFMA pipe.  V goes through in slices of at most
+ * chol.remove_chunk points and 128 columns, highest columns first; a slice's sweep leaves the other slices' columns alone.
+ * Removing only the LAST points is a truncation: no sweep runs.  A diagonal entry that comes out negative has its column
+ * negated (gdml_loo sums logs of positive entries).
+ * The resident training set loses the points, the new factor replaces the old one and stays prepared: gdml_chol_solve,
+ * gdml_predict_cov, gdml_loo and gdml_factor_extend work on the reduced system at once.  Both matrices are resident for the
+ * duration of the call, and the context changes only after the last sweep: on ANY error the old factor, the old training
+ * set and the prepared mark are exactly as before.  b = 0 is a no-op.
+ * fp64 throughout, no atomics, every sum in a fixed order: the same sequence of calls on the same context state gives
+ * identical bits (different values of chol.remove_chunk agree to rounding only).
+ * GDML_ERR_STATE without a prepared factor of the resident training set, GDML_ERR_UNSUPPORTED for a factor with
+ * energy-constraint rows or a multi-rank context, GDML_ERR_INVALID for b < 0, NULL idx with b > 0, an index outside
+ * [0, M), a duplicate or b = M (nothing left), GDML_ERR_OOM when the second buffer does not fit, GDML_ERR_NOT_PD with
+ * *info = column of the reduced system (1-based) whose new diagonal entry is not positive and finite.
+ * Phase "remove"; kernel timers remove_compact, remove_panel, remove_apply.
+ * Not offered: systems with energy constraints, replacing a point in place, a reserved pitch that would avoid the copy. */
+int gdml_factor_remove(gdml_ctx* ctx, const int64_t* idx, int64_t b, int* info);
 
 /* Test / validation error sums evaluated on the device (replaces the body of the reference's
  * cli.test loop, sgdml/cli.py:1564-1605 with _online_err :1170): predicts B host geometries R,

@@ -56,6 +56,7 @@ SIGNATURES = {
     'gdml_predict_cov_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
     'gdml_loo': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     'gdml_factor_extend': (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int)]),
+    'gdml_factor_remove': (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(C.c_int)]),
     'gdml_kernel_matvec': (C.c_int, [_vp, C.c_double, C.c_int, _vp, C.c_int64, _vp]),
     'gdml_predict_errors': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     'gdml_nystroem_factor': (C.c_int, [_vp, C.c_double, _vp, C.c_int64, _vp, _vp, C.POINTER(C.c_int)]),
@@ -650,6 +651,22 @@ class Context(object):
         if b:
             self._train_fp = None  # the resident set is no longer the one train_upload fingerprinted
             self.n_train += b
+        return info.value
+
+    def factor_remove(self, idx):
+        """Remove the training points idx (distinct indices in the resident order) from the training set and from the factor
+        of uncert_prepare without factoring again (gdml_factor_remove); the kept points keep their order.  Raises
+        numpy.linalg.LinAlgError when a diagonal entry of the reduced factor is not positive and MemoryError when the second
+        matrix buffer does not fit; the context is then unchanged."""
+        if not hasattr(self, 'n_atoms'):
+            raise GDMLHipError('factor_remove: no training set resident (train_upload, uncert_prepare)')
+        idx = i64(idx).ravel()
+        b = idx.size
+        info = C.c_int(0)
+        self._check(self._lib.gdml_factor_remove(self._h, _ptr(idx), b, C.byref(info)))
+        if b:
+            self._train_fp = None  # the resident set is no longer the one train_upload fingerprinted
+            self.n_train -= b
         return info.value
 
     def predict_errors(self, R, F_ref, E_ref=None, std=1.0, c=0.0, lat_and_inv=None):

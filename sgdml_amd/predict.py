@@ -105,7 +105,9 @@ class GDMLPredict(object):
         self._model = dict(model)
         self._R_d_desc_alpha = np.asarray(model['R_d_desc_alpha'], dtype=np.float64)
         self._unc_R = self._unc_gd = self._unc_y = None
-        self._n_added = 0
+        # idxs_train as export_model writes it once the training set was edited (-1 for added points, removed entries dropped)
+        self._idxs_train = np.asarray(model['idxs_train']).astype(np.int64) if 'idxs_train' in model else None
+        self._edited = False
 
     def __del__(self):
         for ctx in getattr(self, '_replicas', []):
@@ -402,7 +404,10 @@ class GDMLPredict(object):
         self._R_d_desc_alpha = self.desc.d_desc_dot_vec(self._unc_gd, alphas.reshape(-1, n3))
         self.n_train += b
         self.chunk_size = self.n_train
-        self._n_added += b
+        if b:
+            self._edited = True
+            if self._idxs_train is not None:
+                self._idxs_train = np.concatenate([self._idxs_train, -np.ones(b, dtype=np.int64)])
         for c_ in [ctx] + self._replicas:
             c_.predict_upload_model(self._R_desc_train, self._R_d_desc_alpha, self._tril_perms, self.sig, None)
         self._replicas_stale = False
@@ -420,11 +425,90 @@ class GDMLPredict(object):
             out['kernel_ms'] = kern
         return out
 
+    # ---- shrinking the training set through the resident factor (csrc/remove.hip)
+
+    def remove_training_points(self, idx, E=None):
+        """Remove the training points idx (distinct integer indices in the model's current order) from the model WITHOUT
+        retraining: their rows and columns leave the factor of prepare_uncertainty(R_train, F_train) -- which must have been
+        called with F_train -- by a positive rank-3N b update of the rows behind them on the first GPU (O(3N b n^2) flops
+        instead of n'^3 / 3), the coefficients of the reduced system are solved through it at the model's existing std and
+        every table the predictor holds is refreshed, on all replicas.  The kept points keep their order; the result is the
+        model a retraining on the kept points gives.  predict(), predict_uncertainty(), loo_errors() and
+        add_training_points() then work on M - b points; `uncertainty_scale` is recalibrated on them.
+
+        E: energies of the M - b KEPT points in their new order; the integration constant c is then recomputed by the
+        trainer's rule (mean of E - E_pred at c = 0).  Without E, c is kept.
+
+        Raises ValueError without the labelled prepare_uncertainty or for indices that are not distinct integers in
+        [0, n_train) or that leave no point, NotImplementedError for models with energy constraints,
+        numpy.linalg.LinAlgError when the reduced factor loses positivity and MemoryError when old and new factor do not fit
+        side by side; the model is unchanged after any of them.
+        Returns {'n_train', 'c_updated', 'phase_ms': {'remove', 'solve'} device times, 'host_ms': {...} wall times of the
+        steps, 'kernel_ms': per-phase kernel times when the context is profiling}."""
+        if self._use_E_cstr:
+            raise NotImplementedError('removing training points from models with energy constraints is not supported')
+        if self._unc_y is None:
+            raise ValueError('remove_training_points needs prepare_uncertainty(R_train, F_train) with the training labels first')
+        n3 = 3 * self.n_atoms
+        raw = np.asarray(idx)
+        if raw.size and raw.dtype.kind not in 'iu':
+            raise ValueError('idx must hold integer indices of training points')
+        idx = raw.astype(np.int64).ravel()
+        b = idx.size
+        if b and (idx.min() < 0 or idx.max() >= self.n_train):
+            raise ValueError('idx must lie in [0, {})'.format(self.n_train))
+        if np.unique(idx).size != b:
+            raise ValueError('idx holds an index twice')
+        if b >= self.n_train:
+            raise ValueError('removing {} of {} training points leaves none'.format(b, self.n_train))
+        if E is not None:
+            E = np.asarray(E, dtype=np.float64).ravel()
+            if E.size != self.n_train - b:
+                raise ValueError('E holds {} energies, the reduced training set has {} points'.format(E.size, self.n_train - b))
+        keep = np.ones(self.n_train, dtype=bool)
+        keep[idx] = False
+        ctx = self._ctx
+        t = [timeit.default_timer()]
+        ctx.factor_remove(idx)  # raises with the context untouched
+        t.append(timeit.default_timer())
+        y = np.ascontiguousarray(self._unc_y.reshape(self.n_train, n3)[keep]).ravel()
+        alphas = ctx.chol_solve(y)
+        t.append(timeit.default_timer())
+        self._unc_y = y
+        self._unc_R = np.ascontiguousarray(self._unc_R[keep])
+        self._unc_gd = np.ascontiguousarray(self._unc_gd[keep])
+        self._R_desc_train = np.ascontiguousarray(self._R_desc_train[keep])
+        self._alphas_F = alphas
+        self._R_d_desc_alpha = self.desc.d_desc_dot_vec(self._unc_gd, alphas.reshape(-1, n3))
+        self.n_train -= b
+        self.chunk_size = self.n_train
+        if b:
+            self._edited = True
+            if self._idxs_train is not None:
+                self._idxs_train = self._idxs_train[keep]
+        for c_ in [ctx] + self._replicas:
+            c_.predict_upload_model(self._R_desc_train, self._R_d_desc_alpha, self._tril_perms, self.sig, None)
+        self._replicas_stale = False
+        self._train_resident = False
+        self.uncertainty_scale = float(-np.dot(y, alphas) / y.size)
+        if E is not None:
+            self.c = 0.0
+            self.c = float(integration_constant(E, self.predict(self._unc_R)[0]))
+        t.append(timeit.default_timer())
+        out = {'n_train': self.n_train, 'c_updated': E is not None,
+               'phase_ms': {'remove': ctx.phase_ms('remove')[0] if b else 0.0, 'solve': ctx.phase_ms('solve')[0]},
+               'host_ms': dict(zip(('remove', 'solve', 'model'), [1e3 * (t[i + 1] - t[i]) for i in range(3)]))}
+        kern = {k: ctx.kernel_stat(k)[0] for k in ('remove_compact', 'remove_panel', 'remove_apply')}
+        if any(kern.values()):
+            out['kernel_ms'] = kern
+        return out
+
     def export_model(self):
         """The current model as a dict in the reference's schema (what GDMLPredict and the model files take): the keys the
         constructor was given, with R_desc, R_d_desc_alpha, alphas_F, c and std as they are now.  After add_training_points
-        idxs_train carries -1 for every added point (they come from no dataset index) and the stored validation errors are
-        reset to NaN, as the trainer sets them for a model that has not been validated."""
+        idxs_train carries -1 for every added point (they come from no dataset index), after remove_training_points it has
+        lost the removed entries, and the stored validation errors are reset to NaN, as the trainer sets them for a model that
+        has not been validated."""
         m = dict(self._model)
         m['R_desc'] = np.ascontiguousarray(self._R_desc_train.T)
         m['R_d_desc_alpha'] = self._R_d_desc_alpha
@@ -432,10 +516,9 @@ class GDMLPredict(object):
             m['alphas_F'] = self._alphas_F
         m['c'] = self.c
         m['std'] = self.std
-        if self._n_added:
-            if 'idxs_train' in m:
-                m['idxs_train'] = np.concatenate([np.asarray(m['idxs_train']).astype(np.int64),
-                                                  -np.ones(self._n_added, dtype=np.int64)])
+        if self._edited:
+            if self._idxs_train is not None:
+                m['idxs_train'] = self._idxs_train.copy()
             m['f_err'] = {'mae': np.nan, 'rmse': np.nan}
             if 'e_err' in m:
                 m['e_err'] = {'mae': np.nan, 'rmse': np.nan}
