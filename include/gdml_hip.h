@@ -175,6 +175,9 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *                         fewer when free memory is short).  Different values agree to rounding, not bit for bit
  *   chol.remove_chunk (64)         removed points per sweep of gdml_factor_remove; a sweep never takes more than 128 columns
  *                         of L[kept, removed] (the LDS of its kernels).  Different values agree to rounding, not bit for bit
+ *   chol.select_chunk (64)         candidates per pass of gdml_select_points' first stage (their rows of the cross-kernel are 3N n
+ *                         doubles each; fewer when free memory is short).  The results do not depend on it
+ *   chol.select_mem_budget (0)     bytes the retained buffers of gdml_select_points may take; 0 = 90 % of free device memory (tests)
  *   pcg.f32_min_pivot (1e-7)  fp32 form: smallest squared Cholesky pivot of the rounded factor's Gram matrix below which the
  *                         reference's fp64 form is kept (gdml_get_option("pcg.f32_last_min_pivot") reads the last value seen)
  * Unknown keys return GDML_ERR_INVALID. */
@@ -414,6 +417,40 @@ int gdml_factor_extend(gdml_ctx* ctx, const double* R_desc_new, const double* R_
  * Phase "remove"; kernel timers remove_compact, remove_panel, remove_apply.
  * Not offered: systems with energy constraints, replacing a point in place, a reserved pitch that would avoid the copy. */
 int gdml_factor_remove(gdml_ctx* ctx, const int64_t* idx, int64_t b, int* info);
+
+/* Choosing which n_select of B unlabelled candidate geometries to label next, by the greedy batch rule on the JOINT information
+ * gain (ranking gdml_predict_cov's variances scores every geometry alone: a pool cut from a trajectory is full of near-copies
+ * and the top of that ranking is one geometry several times).  The reference has no counterpart.  With A = -K + lam I = L L^T
+ * resident (n = 3N M, n3 = 3N), T the training set, S_t the candidates picked before step t and, for candidate q,
+ *   W_q = (-Kx_q) L^-T,   Sig_q^(0) = -k_qq - W_q W_q^T            (the covariance gdml_predict_cov returns, bit for bit)
+ *   gain_t(q) = log det(Sig_q^(t) / lam + I) = log det A_{T+S_t+q} - log det A_{T+S_t} - n3 log lam      (nats)
+ * -- twice the mutual information between the model and a noisy label at q given everything known so far; it needs no labels
+ * and does not depend on std -- step t picks q* = argmax gain_t (ties: the LOWEST pool index) and conditions the pool on it:
+ *   C = -k(pool, q*) - W W_q*^T - sum_{s<t} V_s V_s[q*]^T  (n3 B x n3),   V_t = C G^-T  with  G G^T = Sig_q*^(t) + lam I,
+ *   Sig_q^(t+1) = Sig_q^(t) - V_t[q] V_t[q]^T   for every remaining q,
+ * a block-pivoted Cholesky of the pool's joint posterior covariance.  The sweep ends after n_select picks, or before a pick
+ * whose gain is below min_gain (-inf: never).  W W_q*^T runs on the fp64 MFMA pipe and reads all of W ceil(n3 / 64) times per step.
+ * R (B,3N) host geometries; gain0_out (B) the initial gains of ALL candidates; idx_out, gain_out (n_select) the picks in
+ * order and their gains at the time of the pick, of which *n_selected_out are written.  With n_select = 0 only gain0_out is
+ * computed, the candidates stream through in chunks (option chol.select_chunk) and any pool size works; n_select = 1 adds an
+ * argmax to that and retains nothing either; otherwise W (n3 B x n),
+ * the covariances and the block columns V stay on the device for the duration of the call.
+ * The factor and the training set are only read: a prepared factor stays prepared, gdml_predict_cov, gdml_loo and
+ * gdml_chol_solve give the same bits before and after.  fp64 throughout, no atomics, every sum in a fixed order: repeated
+ * calls give identical bits; a candidate's initial gain depends neither on its place in the pool nor on chol.select_chunk (two
+ * identical geometries have identical initial gains), and different values of chol.select_chunk give the same picks.
+ * GDML_ERR_STATE without a prepared factor of the resident training set, GDML_ERR_UNSUPPORTED for a factor with
+ * energy-constraint rows or a multi-rank context, GDML_ERR_INVALID for a NULL R, B < 0, n_select outside [0, B], a lattice
+ * without its inverse, a NULL gain0_out / n_selected_out or (n_select > 0) idx_out / gain_out, GDML_ERR_OOM when the retained
+ * buffers do not fit -- the message ends with "largest pool that fits: K" (0: none of at least n_select candidates) --,
+ * GDML_ERR_NOT_PD with *info = q + 1 when Sig_q + lam I of candidate q has a non-positive pivot.  After any error every work
+ * buffer of the call has been released.  Phase "select"; kernel timers select_cross, select_solve, select_gram, select_score,
+ * select_column, select_update.
+ * Not offered: systems with energy constraints, multi-GPU factors, criteria other than the information gain, removing
+ * candidates from a running sweep, labelling (gdml_factor_extend adds the labelled points). */
+int gdml_select_points(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv, int64_t n_select,
+                       double min_gain, int64_t* idx_out, double* gain_out, double* gain0_out, int64_t* n_selected_out,
+                       int* info);
 
 /* Test / validation error sums evaluated on the device (replaces the body of the reference's
  * cli.test loop, sgdml/cli.py:1564-1605 with _online_err :1170): predicts B host geometries R,

@@ -57,6 +57,8 @@ SIGNATURES = {
     'gdml_loo': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     'gdml_factor_extend': (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int)]),
     'gdml_factor_remove': (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(C.c_int)]),
+    'gdml_select_points': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_double, _vp, _vp, _vp, _ip,
+                                     C.POINTER(C.c_int)]),
     'gdml_kernel_matvec': (C.c_int, [_vp, C.c_double, C.c_int, _vp, C.c_int64, _vp]),
     'gdml_predict_errors': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
     'gdml_nystroem_factor': (C.c_int, [_vp, C.c_double, _vp, C.c_int64, _vp, _vp, C.POINTER(C.c_int)]),
@@ -668,6 +670,29 @@ class Context(object):
             self._train_fp = None  # the resident set is no longer the one train_upload fingerprinted
             self.n_train -= b
         return info.value
+
+    def select_points(self, R, lat_and_inv=None, n_select=0, min_gain=None):
+        """Greedy selection of n_select of the candidate geometries R (B,3N) by joint information gain against the factor of
+        uncert_prepare (gdml_select_points): (idx (k,) pool indices in pick order, gain (k,) their gains when picked,
+        gain_initial (B,)), k <= n_select (fewer when the best remaining gain falls below min_gain).  n_select = 0 computes the
+        initial gains only, streaming the pool.  Raises MemoryError when the retained rows of the pool do not fit (the
+        message names the largest pool that would), numpy.linalg.LinAlgError for a candidate whose covariance is not
+        positive definite."""
+        if not hasattr(self, 'n_atoms'):
+            raise GDMLHipError('select_points: no training set resident (train_upload, uncert_prepare)')
+        n3 = 3 * self.n_atoms
+        R = f64(R).reshape(-1, n3)
+        B = R.shape[0]
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        n_select = int(n_select)
+        idx, gain, gain0 = np.zeros(max(n_select, 0), dtype=np.int64), np.zeros(max(n_select, 0)), np.empty(B)
+        k, info = C.c_int64(0), C.c_int(0)
+        self._check(self._lib.gdml_select_points(self._h, _ptr(R), B, _ptr(lat), _ptr(lat_inv), n_select,
+                                                 -np.inf if min_gain is None else float(min_gain), _ptr(idx), _ptr(gain),
+                                                 _ptr(gain0), C.byref(k), C.byref(info)))
+        return idx[:k.value].copy(), gain[:k.value].copy(), gain0
 
     def predict_errors(self, R, F_ref, E_ref=None, std=1.0, c=0.0, lat_and_inv=None):
         """Eight error sums of a labelled batch, evaluated on the GPU (see gdml_predict_errors)."""

@@ -81,8 +81,8 @@ struct Model {
 //   SLOT_PRECON_GEMV  the fp32 form (precon_form 3) and the fp64 form are two branches of precon_apply_device
 //   SLOT_PRECON_MF    build_f32_form reads its flag back and synchronises before it goes on, and applies no preconditioner;
 //                     precon_apply_mf calls matvec_device, which requests other slots only
-//   SLOT_GRAM_WS/ROWS gdml_uncert_cross, gdml_predict_cov and gdml_loo each carve them anew (gram_workspace) and call none of
-//                     the others; tall_trsm in between requests SLOT_PANEL_TRSM only
+//   SLOT_GRAM_WS/ROWS gdml_uncert_cross, gdml_predict_cov, gdml_loo and gdml_select_points each carve them anew (gram_workspace)
+//                     and call none of the others; tall_trsm in between requests SLOT_PANEL_TRSM only
 enum CtxSlot {
   SLOT_PREDICT_WS = 0,      // row-split partials of F_x and E (predict_device, predict_fused); workspace of hess_device
   SLOT_MATVEC_OUT = 1,      // forces and energies of this rank's query points (matvec_device)
@@ -97,8 +97,8 @@ enum CtxSlot {
   SLOT_PRECON_MF = 10,      // vectors of the matrix-free preconditioner (precon_apply_mf); "fits on every rank" flag (build_f32_form)
   SLOT_F32_GRAM_ROWS = 11,  // widened row chunk of the rounded factor (build_f32_form)
   SLOT_MATVEC_VREF = 12,    // coefficients back in the reference order (matvec_device, sharded with energy constraints)
-  SLOT_GRAM_WS = 13,        // queries / coefficients, partial Gram tiles, staged output (gram_workspace: uncert.hip, loo.hip)
-  SLOT_GRAM_ROWS = 14,      // the (3N x chunk, padded to 128 rows) x K_ld row buffer (gram_workspace: uncert.hip, loo.hip)
+  SLOT_GRAM_WS = 13,        // queries / coefficients, partial Gram tiles, staged output (gram_workspace: uncert.hip, loo.hip, select.hip)
+  SLOT_GRAM_ROWS = 14,      // the (3N x chunk, padded to 128 rows) x K_ld row buffer (gram_workspace: uncert.hip, loo.hip, select.hip)
   SLOT_COUNT
 };
 
@@ -309,9 +309,13 @@ int gram_workspace(gdml_ctx* ctx, const GramSplit& g, const char* chunk_opt, int
 // pitch: row pitch of Z when it is not g.ld (0 = g.ld)
 void block_gram_launch(gdml_ctx* ctx, const GramSplit& g, const double* Z, double* part, int64_t items, bool diag, int64_t first0,
                        int64_t first_stride, int64_t pitch = 0);
-// sgn * (cross-kernel rows) of bc device-resident queries against M column points (uncert.hip; extend.hip)
+// sgn * (cross-kernel rows) of bc device-resident queries against M column points, and sgn * k_qq unless kqq is null
+// (uncert.hip; extend.hip, select.hip)
 int cross_rows_launch(gdml_ctx* ctx, const double* xt, const double* gt, int64_t M, const double* xq, const double* gq, int bc,
                       double* rows, int64_t ld, double* kqq, double sgn, double sig, const char* tname);
+// out = sym(-k_qq) - sum_s partial_s of `items` row blocks whose partial tiles block_gram_launch wrote (uncert.hip; select.hip)
+void cov_reduce_launch(gdml_ctx* ctx, const GramSplit& g, const double* part, const double* nkqq, double* out, int64_t items,
+                       int full);
 void shard_points(const gdml_ctx* ctx, int64_t M, int64_t* p0, int64_t* p1, int64_t* pts_per);
 // Layout of the replicated device vectors of the sharded solvers (Nystroem factor rows, PCG vectors, mat-vec in / out).
 //   no communicator (world <= 1): the reference order, n entries, no padding;

@@ -58,6 +58,7 @@ __global__ void __launch_bounds__(256) cross_rows_kernel(CrossArgs a) {
     if (self) {  // pad columns of this query's rows (the solve and the Gram kernel read whole 16-column groups)
       const int64_t n = a.M * n3, npad = a.ld - n;
       for (int64_t e = tid; e < npad * n3; e += 256) a.rows[((int64_t)q * n3 + e / npad) * a.ld + n + e % npad] = 0.0;
+      if (!a.kqq) continue;  // k_qq not asked for (the same for the whole workgroup)
     }
     for (int p0 = 0; p0 < a.P; p0 += a.PG) {
       const int pg = a.P - p0 < a.PG ? a.P - p0 : a.PG;
@@ -143,7 +144,7 @@ __global__ void __launch_bounds__(256) cross_rows_kernel(CrossArgs a) {
 }
 
 // sgn * Kx of bc device-resident queries against the M column points (xt, gt) into `rows` (pitch ld) and sgn * k_qq into
-// `kqq`; permutations and molecule size are those of the resident training set, the launch is timed as `tname`
+// `kqq` (null: k_qq is not computed, the item only zeroes the pad columns); permutations and molecule size are those of the resident training set, the launch is timed as `tname`
 int cross_rows_launch(gdml_ctx* ctx, const double* xt, const double* gt, int64_t M, const double* xq, const double* gq, int bc,
                       double* rows, int64_t ld, double* kqq, double sgn, double sig, const char* tname) {
   const TrainSet& ts = ctx->ts;
@@ -172,7 +173,7 @@ int cross_rows_launch(gdml_ctx* ctx, const double* xt, const double* gt, int64_t
   hipLaunchKernelGGL(cross_rows_kernel, dim3((unsigned)grid), dim3(256), lds, ctx->stream, a);
   ctx->launch_counter++;
   // algorithmic work: bytes written
-  ktime_end(ctx, slot, tname, (double)a.items * 9.0 * ts.N * (double)ts.N * 8.0);
+  ktime_end(ctx, slot, tname, (double)bc * (double)(M + (kqq ? 1 : 0)) * 9.0 * ts.N * (double)ts.N * 8.0);
   hipError_t e = hipGetLastError();
   int rc = e == hipSuccess ? GDML_OK : gdml_fail(ctx, GDML_ERR_HIP, "cross_rows launch: %s", hipGetErrorString(e));
   if (a.gws) {
@@ -217,6 +218,15 @@ __global__ void __launch_bounds__(256) cov_reduce_kernel(const double* __restric
     const double kd = nkqq[q * n3 * n3 + (int64_t)r * n3 + r];
     out[t] = 0.5 * (kd + kd) - acc;
   }
+}
+
+// the reduce for `items` row blocks (one launch, not timed): out (items,3N,3N) with full, else (items,3N)
+void cov_reduce_launch(gdml_ctx* ctx, const GramSplit& g, const double* part, const double* nkqq, double* out, int64_t items,
+                       int full) {
+  const int64_t total = items * (full ? (int64_t)g.n3 * g.n3 : (int64_t)g.n3);
+  hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, part, nkqq, out, g.n3,
+                     g.nblk, g.npairs, g.S, full, total);
+  ctx->launch_counter++;
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -354,9 +364,7 @@ static int cov_common(gdml_ctx* ctx, const double* R, bool on_device, int64_t B,
     block_gram_launch(ctx, g, p.rows, p.part, bc, !full, 0, 0);
     double* d_out = on_device ? cov_out + b0 * per_out : p.out;
     const int64_t total = bc * per_out;
-    hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, ctx->stream, p.part, p.nkqq, d_out,
-                       g.n3, g.nblk, g.npairs, g.S, full, total);
-    ctx->launch_counter++;
+    cov_reduce_launch(ctx, g, p.part, p.nkqq, d_out, bc, full);
     ktime_end(ctx, slot, "uncert_gram", 2.0 * (double)g.ld * (full ? (double)n3 * n3 : (double)n3) * bc);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return gdml_fail(ctx, GDML_ERR_HIP, "cov_gram launch: %s", hipGetErrorString(e));

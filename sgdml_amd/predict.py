@@ -4,6 +4,7 @@ the HIP prediction kernels (csrc/predict.hip).  Outputs, scaling (std, c) and th
 mode (``predict()`` with cached descriptors, predict.py:1221-1233) follow the reference.
 """
 import logging
+import re
 import sys
 import timeit
 
@@ -499,6 +500,99 @@ class GDMLPredict(object):
                'phase_ms': {'remove': ctx.phase_ms('remove')[0] if b else 0.0, 'solve': ctx.phase_ms('solve')[0]},
                'host_ms': dict(zip(('remove', 'solve', 'model'), [1e3 * (t[i + 1] - t[i]) for i in range(3)]))}
         kern = {k: ctx.kernel_stat(k)[0] for k in ('remove_compact', 'remove_panel', 'remove_apply')}
+        if any(kern.values()):
+            out['kernel_ms'] = kern
+        return out
+
+    # ---- choosing what to label next (csrc/select.hip)
+
+    def select_training_points(self, R_pool, n_select, min_gain=None, prescreen=None):
+        """Choose which n_select of the unlabelled geometries R_pool (B,3N) to label next, by the greedy batch rule on the
+        JOINT information gain.  Sorting predict_uncertainty() by variance scores every geometry alone, and a pool cut from a
+        trajectory is full of near-copies: the top of that ranking is one geometry several times.  Here every pick conditions
+        the posterior on the points already picked (a block-pivoted Cholesky of the pool's joint posterior covariance on the
+        first GPU), so a copy of a picked geometry only averages the label noise afterwards (at most 3N log 2).  The gain of
+        candidate q at step t is
+            log det(Sig_q^(t) / lam + I)    (nats)
+        with Sig_q^(t) its posterior force covariance given the training set and the t earlier picks: twice the mutual
+        information between the model and a noisy label at q.  It needs no labels and does not depend on std or
+        `uncertainty_scale`; ties go to the lowest pool index.  Works after prepare_uncertainty(), with or without F_train;
+        the model and the factor are only read.
+
+        min_gain: stop before a pick whose gain is below it (None: always pick n_select).
+        prescreen=K: the initial gains of the whole pool are computed in a streaming pass (any pool size), the joint
+        selection runs on the K best candidates only and the indices are mapped back.  Greedy gains never increase (the
+        criterion is submodular), so the result equals the un-screened one whenever the largest initial gain among the dropped
+        candidates is below the last pick's gain (and below min_gain when that ended the sweep): that check is returned as
+        'prescreen_exact'.  The same runs automatically, with the largest K that fits, when the joint selection on the whole
+        pool does not fit in device memory.
+
+        Returns a dict: 'idx' (k,) pool indices in pick order, k <= n_select; 'gain' (k,) their gains when picked;
+        'gain_initial' (B,) the gains of all candidates before the first pick; 'total_gain' = sum of 'gain' = log det of the
+        enlarged system matrix minus that of the present one minus 3N k log lam; 'prescreen_exact' (None without
+        prescreening); 'phase_ms': {'select'} device time; 'kernel_ms' per-kernel times when the context is profiling.
+
+        Raises ValueError without a prepared factor (prepare_uncertainty never called, released, or overwritten by an assembly
+        since) or for arguments that do not fit, NotImplementedError for models with
+        energy constraints, MemoryError when not even a prescreened pool fits, numpy.linalg.LinAlgError when a candidate's
+        covariance is not positive definite."""
+        if self._use_E_cstr:
+            raise NotImplementedError('selecting training points for models with energy constraints is not supported')
+        n3 = 3 * self.n_atoms
+        R_pool = np.asarray(R_pool, dtype=np.float64)
+        if R_pool.size % n3:
+            raise ValueError('R_pool holds {} values, not a multiple of 3N = {}'.format(R_pool.size, n3))
+        R_pool = np.ascontiguousarray(R_pool.reshape(-1, n3))
+        B = R_pool.shape[0]
+        if int(n_select) != n_select or not 0 <= n_select <= B:
+            raise ValueError('n_select must be an integer in [0, {}]'.format(B))
+        n_select = int(n_select)
+        if prescreen is not None and (int(prescreen) != prescreen or prescreen < max(n_select, 1)):
+            raise ValueError('prescreen must be an integer of at least max(n_select, 1)')
+        ctx = self._ctx
+        if not hasattr(ctx, 'n_atoms'):  # no training set was ever uploaded: the library would answer GDML_ERR_STATE
+            raise ValueError('select_training_points needs prepare_uncertainty(R_train) first')
+        kern_names = ('select_cross', 'select_solve', 'select_gram', 'select_score', 'select_column', 'select_update')
+        phase = [0.0]
+        kern0 = {k: ctx.kernel_stat(k)[0] for k in kern_names}
+
+        def run(R, b):
+            try:
+                out = ctx.select_points(R, self.lat_and_inv, b, min_gain)
+            except _lib.GDMLHipError as e:  # GDML_ERR_STATE: released, or overwritten by an assembly since
+                if str(e).startswith('[{}]'.format(_lib.ERR_STATE)):
+                    raise ValueError('select_training_points needs the factor of prepare_uncertainty(): ' + str(e)) from e
+                raise
+            if len(R):
+                phase[0] += ctx.phase_ms('select')[0]
+            return out
+
+        keep = None
+        if prescreen is None:
+            try:
+                idx, gain, gain0 = run(R_pool, n_select)
+            except MemoryError as e:
+                fits = re.search(r'largest pool that fits: (\d+)', str(e))
+                if fits is None or int(fits.group(1)) < max(n_select, 1):
+                    raise
+                prescreen = int(fits.group(1))
+        if prescreen is not None:
+            gain0 = run(R_pool, 0)[2]
+            K = min(int(prescreen), B)
+            keep = np.sort(np.argsort(-gain0, kind='stable')[:K])  # the K best; in pool order, so that ties resolve as un-screened
+            sub_idx, gain, _ = run(R_pool[keep], n_select)
+            idx = keep[sub_idx]
+        exact = None
+        if keep is not None:
+            dropped = np.ones(B, dtype=bool)
+            dropped[keep] = False
+            top = gain0[dropped].max() if dropped.any() else -np.inf
+            exact = bool(top < gain[-1]) if len(gain) else True
+            if len(gain) < n_select and min_gain is not None:
+                exact = exact and bool(top < min_gain)
+        out = {'idx': idx, 'gain': gain, 'gain_initial': gain0, 'total_gain': float(np.sum(gain)), 'prescreen_exact': exact,
+               'phase_ms': {'select': phase[0]}}
+        kern = {k: ctx.kernel_stat(k)[0] - kern0[k] for k in kern_names}
         if any(kern.values()):
             out['kernel_ms'] = kern
         return out
