@@ -169,6 +169,10 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *   predict.cov_chunk (64)     geometries per pass of gdml_predict_cov / gdml_uncert_cross (their rows of the cross-kernel are 3N n
  *                         doubles each; fewer when free memory is short)
  *   predict.cov_global (0)    1: the cross-kernel keeps its per-permutation vectors in global memory (the path of N > 374; tests)
+ *   predict.cov_few_rows (256) most rows 3N B that gdml_predict_cov_few sends through its own solve; 0 = always the batched path of
+ *                         gdml_predict_cov; values above GDML_COV_FEW_ROWS count as GDML_COV_FEW_ROWS
+ *   predict.cov_few_split_timers (0)  1: under gdml_profile the two per-step kernels of gdml_predict_cov_few are timed one by one
+ *                         ("few_diag", "few_upd") instead of the whole solve ("few_solve"); the events slow the solve down
  *   chol.loo_chunk (64)            training points per pass of gdml_loo (their rows of L^-T are 3N n doubles each; fewer when free
  *                         memory is short).  The results do not depend on it
  *   chol.extend_chunk (64)         points per pass of gdml_factor_extend (their 3N rows are assembled, solved and factored together;
@@ -344,6 +348,30 @@ int gdml_predict_cov(gdml_ctx* ctx, const double* R, int64_t B, const double* la
                      double* cov_out);
 int gdml_predict_cov_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat, const double* lat_inv,
                          int full, double* cov_dev);
+
+/* The same covariance for a handful of geometries at low latency (one geometry per step of an MD loop): Sig_q = -k_qq - Z_q Z_q^T,
+ * Z_q = (-Kx_q) L^-T as above, with a forward solve made for r = 3N B <= GDML_COV_FEW_ROWS rows (one geometry of up to 85 atoms,
+ * two of 42, four of 21): steps of 256 columns, the diagonal part through per-call inverses of the 64 x 64 diagonal blocks of L and
+ * MFMA sub-updates, the trailing update in strips that read L exactly once (csrc/uncert_few.hip).  Arguments, units, states and
+ * error codes are those of gdml_predict_cov[_dev]; B = 0 is a no-op; the factor and the training set are only read.
+ * When 3N B exceeds the limit (option predict.cov_few_rows, default and maximum GDML_COV_FEW_ROWS, 0 = never) the call IS
+ * gdml_predict_cov[_dev], with its bits, so callers need not know the limit.  Within the limit the results agree with
+ * gdml_predict_cov to rounding (another summation order), not bit for bit.
+ * Invariants of the path within the limit:
+ *   1. repeated calls give identical bits;
+ *   2. the _dev entry equals the host entry bit for bit;
+ *   3. the variances (full = 0) equal the diagonal of the full form bit for bit;
+ *   4. a geometry's result does not depend on which other geometries share the call, nor on its position in it, bit for bit;
+ *   5. gdml_predict_cov, gdml_loo and gdml_chol_solve give the same bits before and after a call;
+ *   6. the path works at once on the factor left by gdml_factor_extend / gdml_factor_remove.
+ * Not offered: factors with energy-constraint rows (GDML_ERR_UNSUPPORTED) or of a multi-rank context, inverses cached across
+ * calls, a persistent single-launch form, bit equality with gdml_predict_cov.  Timers: phase "uncert_few"; kernels "few_cross",
+ * "few_inv", "few_solve" (or "few_diag" / "few_upd", see predict.cov_few_split_timers), "few_gram". */
+#define GDML_COV_FEW_ROWS 256
+int gdml_predict_cov_few(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv, int full,
+                         double* cov_out);
+int gdml_predict_cov_few_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat, const double* lat_inv,
+                             int full, double* cov_dev);
 
 /* Leave-one-out force errors, their predictive covariances and log det A from the resident Cholesky factor: what M
  * retrainings on M - 1 points each would give, in one pass (Rasmussen & Williams, Gaussian Processes for Machine Learning,

@@ -54,6 +54,8 @@ SIGNATURES = {
     'gdml_uncert_cross': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     'gdml_predict_cov': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
     'gdml_predict_cov_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
+    'gdml_predict_cov_few': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
+    'gdml_predict_cov_few_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
     'gdml_loo': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     'gdml_factor_extend': (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int)]),
     'gdml_factor_remove': (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(C.c_int)]),
@@ -617,6 +619,29 @@ class Context(object):
             lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
         self._check(self._lib.gdml_predict_cov_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), int(bool(full)),
                                                    cov_dev))
+
+    def predict_cov_few(self, R, lat_and_inv=None, full=False):
+        """predict_cov for a handful of geometries at low latency (gdml_predict_cov_few): the same quantity and shapes through a
+        solve made for up to COV_FEW_ROWS = 256 rows 3N B; a larger batch is predict_cov itself, bit for bit."""
+        if not hasattr(self, 'n_atoms'):
+            raise GDMLHipError('predict_cov_few: no training set resident (train_upload, uncert_prepare)')
+        n3 = 3 * self.n_atoms
+        R = f64(R).reshape(-1, n3)
+        B = R.shape[0]
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        out = np.empty((B, n3, n3) if full else (B, n3))
+        self._check(self._lib.gdml_predict_cov_few(self._h, _ptr(R), B, _ptr(lat), _ptr(lat_inv), int(bool(full)), _ptr(out)))
+        return out
+
+    def predict_cov_few_dev(self, R_dev, B, cov_dev, lat_and_inv=None, full=False):
+        """gdml_predict_cov_few_dev on device pointers (ints or c_void_p)."""
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        self._check(self._lib.gdml_predict_cov_few_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), int(bool(full)),
+                                                       cov_dev))
 
     def loo(self, alphas, cov=None):
         """Leave-one-out pass over the resident Cholesky factor (gdml_loo), in normalised units: (resid (M,3N), cov, logdet) with

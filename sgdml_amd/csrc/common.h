@@ -81,8 +81,10 @@ struct Model {
 //   SLOT_PRECON_GEMV  the fp32 form (precon_form 3) and the fp64 form are two branches of precon_apply_device
 //   SLOT_PRECON_MF    build_f32_form reads its flag back and synchronises before it goes on, and applies no preconditioner;
 //                     precon_apply_mf calls matvec_device, which requests other slots only
-//   SLOT_GRAM_WS/ROWS gdml_uncert_cross, gdml_predict_cov, gdml_loo and gdml_select_points each carve them anew (gram_workspace)
-//                     and call none of the others; tall_trsm in between requests SLOT_PANEL_TRSM only
+//   SLOT_GRAM_WS/ROWS gdml_uncert_cross, gdml_predict_cov, gdml_predict_cov_few, gdml_loo and gdml_select_points each carve them anew
+//                     (gram_workspace) and call none of the others while they hold them (gdml_predict_cov_few hands a batch beyond
+//                     its limit to gdml_predict_cov BEFORE it carves anything; its inverted diagonal blocks are the fixed part of
+//                     SLOT_GRAM_WS and live for one call); tall_trsm in between requests SLOT_PANEL_TRSM only
 enum CtxSlot {
   SLOT_PREDICT_WS = 0,      // row-split partials of F_x and E (predict_device, predict_fused); workspace of hess_device
   SLOT_MATVEC_OUT = 1,      // forces and energies of this rank's query points (matvec_device)

@@ -290,16 +290,21 @@ class GDMLPredict(object):
         """Free the resident factor of prepare_uncertainty()."""
         self._ctx.uncert_release()
 
-    def predict_uncertainty(self, R, full_cov=False):
+    def predict_uncertainty(self, R, full_cov=False, low_latency=False):
         """(E, F, var) for geometries R (B,3N) or (3N,): E, F as predict(R); var (B,3N) the marginal posterior variances of
         the force components, or with full_cov the (B,3N,3N) posterior covariances, in the units of F squared (std^2 times
         `uncertainty_scale`: see prepare_uncertainty on what the magnitudes mean without calibration).  Runs on the first GPU
-        only; set_alphas() does not invalidate the factor (it depends on the training geometries, sig and lam alone)."""
+        only; set_alphas() does not invalidate the factor (it depends on the training geometries, sig and lam alone).
+
+        low_latency=True takes the few-row solve (gdml_predict_cov_few) made for one or a few geometries per call, as in an MD
+        loop that watches its own variance: up to 256 rows 3N B per call, a larger batch silently goes the default route.  Its
+        covariances agree with the default's to rounding, not bit for bit; E, F, the scaling and the shapes are the same."""
         R = np.asarray(R, dtype=np.float64)
         if R.ndim == 1:
             R = R[None, :]
         R = R.reshape(R.shape[0], -1)
-        cov = self._ctx.predict_cov(R, self.lat_and_inv, full=full_cov)
+        cov_fn = self._ctx.predict_cov_few if low_latency else self._ctx.predict_cov
+        cov = cov_fn(R, self.lat_and_inv, full=full_cov)
         E, F = self.predict(R)
         cov *= self.std * self.std * self.uncertainty_scale
         return E, F, cov
