@@ -79,7 +79,7 @@ int gdml_mem_info(gdml_ctx* ctx, int64_t* held, int64_t* free_b, int64_t* total_
 int gdml_mem_reserve(gdml_ctx* ctx, int64_t bytes, int64_t* reserved_out);
 
 /* Elapsed milliseconds (HIP events on the compute stream) of the most recent call of the
- * named phase: "desc", "assemble", "factor", "solve", "predict", "matvec", "precon", "uncert", "loo".
+ * named phase: "desc", "assemble", "factor", "solve", "predict", "matvec", "precon", "uncert", "loo", "evidence".
  * Also returns how many kernel launches the phase issued. */
 int gdml_phase_ms(gdml_ctx* ctx, const char* phase, double* ms_out, int64_t* launches_out);
 
@@ -182,6 +182,12 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *   chol.select_chunk (64)         candidates per pass of gdml_select_points' first stage (their rows of the cross-kernel are 3N n
  *                         doubles each; fewer when free memory is short).  The results do not depend on it
  *   chol.select_mem_budget (0)     bytes the retained buffers of gdml_select_points may take; 0 = 90 % of free device memory (tests)
+ *   chol.evidence_chunk (64)       training points per pass of gdml_evidence_grad (their rows of L^-T and of A^-1 are 3N n doubles
+ *                         each; fewer when free memory is short).  Different values agree to rounding, not bit for bit
+ *   chol.evidence_mem_budget (0)   bytes gdml_evidence_grad takes for free when it sizes its second matrix; 0 = what
+ *                         gdml_mem_info reports (tests)
+ *   chol.evidence_global (0)       1: the contraction kernel of gdml_evidence_grad keeps its per-pair vectors and the tile in
+ *                         global memory (the path of descriptors beyond LDS, N > 140 or so; tests)
  *   pcg.f32_min_pivot (1e-7)  fp32 form: smallest squared Cholesky pivot of the rounded factor's Gram matrix below which the
  *                         reference's fp64 form is kept (gdml_get_option("pcg.f32_last_min_pivot") reads the last value seen)
  * Unknown keys return GDML_ERR_INVALID. */
@@ -395,6 +401,41 @@ int gdml_predict_cov_few_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, cons
  * Not offered: leave-one-out energies (the integration constant is refitted per fold) and systems with energy constraints. */
 int gdml_loo(gdml_ctx* ctx, const double* alphas, int64_t n, int cov_mode, double* resid_out, double* cov_out,
              double* logdet_out, int* info);
+
+/* Gradient of the model evidence (log marginal likelihood) in the length scale sig and the regularisation lam from the resident
+ * Cholesky factor: what type-II maximum likelihood needs to set both without a grid and without held-back data.  The reference
+ * has no counterpart (it picks an integer sig by validation error and never tunes lam).  In the library's conventions -- K the
+ * un-negated kernel matrix, A = -K + lam I = L L^T, labels y normalised by std, a = A^-1 y = -alphas, model y ~ N(0, s^2 A),
+ *   lml = -1/2 y^T a / s^2 - 1/2 (log det A + n log s^2) - n/2 log 2 pi                     (GDMLPredict.loo_errors)
+ * -- and with K' = dK/dsig at the factor's own sig (the sig of the assembly the factor came from):
+ *   d lml / d sig = 1/2 ( <A^-1, K'> - a^T K' a / s^2 ),     <X, Y> = sum_ij X_ij Y_ij
+ *   d lml / d lam = 1/2 ( a^T a / s^2 - tr A^-1 )
+ * at fixed s^2; at the maximum-likelihood s^2 = y^T a / n these are the total derivatives of the profiled evidence.
+ *   terms_out[5] = { tr A^-1, <A^-1, K'>, a^T K' a, a^T a, log det A }
+ * The caller combines them with s^2: the library knows nothing of labels or s^2, as gdml_loo knows nothing of them.  K' has the
+ * block structure of K: for a pair of points, a permutation p, d = x_i - P_p x_j, r = sqrt(5) |d|, e = exp(-r / sig) the block
+ * J_i^T [f1 d d^T - f2 I] J_j^p of K (f1 = 25 e / (3 sig^4), f2 = 5 e (sig + r) / (3 sig^3)) becomes that of K' with
+ *   f1' = f1 (r - 4 sig) / sig^2,     f2' = 5 e (r^2 - 2 sig r - 2 sig^2) / (3 sig^5);
+ * it is contracted against the tiles of A^-1 on the fly and never assembled or stored.
+ * alphas (n = 3N M): host coefficients that belong to the resident factor's matrix (gdml_chol_solve), as for gdml_loo.
+ * Three passes, chunk by chunk over the training points (option chol.evidence_chunk): the rows of Z = L^-T by the seed and the
+ * right-looking solve of gdml_loo, solved in the chunk buffer and the true rows (not the rows padded to 128 behind them) copied
+ * into a SECOND n x pitch matrix that is allocated for the call; the rows of -A^-1 up to the diagonal, one GEMM per chunk; the
+ * contraction kernel over the lower block triangle (off-diagonal pairs count twice).  MEMORY: the second matrix is as large
+ * as the factor (31.7 GB at n = 63 000), so the call needs twice the factor's memory; GDML_ERR_OOM, with the bytes needed
+ * and the bytes free in the message, when it does not fit.
+ * Invariants: the factor and the training set are only read -- gdml_predict_cov, gdml_loo and gdml_chol_solve give the same
+ * bits before and after a call; every buffer of the call is released on every exit path; fp64 throughout, no atomics, every
+ * sum in a fixed order (the four sums stay apart down to the host): repeated calls give identical bits; log det A is
+ * gdml_loo's, bit for bit; different values of chol.evidence_chunk agree to rounding, not bit for bit.
+ * Needs what gdml_loo needs: a factor WITHOUT energy-constraint rows resident for the training set of gdml_train_upload on a
+ * single-rank context.  GDML_ERR_STATE without a factor or with one that does not belong to the training set,
+ * GDML_ERR_UNSUPPORTED for a factor with energy-constraint rows or a multi-rank context, GDML_ERR_INVALID for NULL arguments
+ * or a wrong n.  *info is set to 0 (optional).  Phase "evidence"; kernel timers evidence_seed, evidence_solve, evidence_inv,
+ * evidence_contract.
+ * Not offered: energy-constraint systems, multi-GPU factors, gradients of the leave-one-out error, per-atom-type or anisotropic
+ * length scales, a stochastic (Hutchinson) trace estimate for systems whose second matrix does not fit. */
+int gdml_evidence_grad(gdml_ctx* ctx, const double* alphas, int64_t n, double* terms_out /* 5 */, int* info);
 
 /* Appending b training points to the factor of gdml_uncert_prepare without factoring again (on-the-fly learning: label the
  * geometries gdml_predict_cov flags, add them, go on).  The reference has no counterpart (it retrains from nothing).  With

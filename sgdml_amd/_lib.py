@@ -57,6 +57,7 @@ SIGNATURES = {
     'gdml_predict_cov_few': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
     'gdml_predict_cov_few_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int, _vp]),
     'gdml_loo': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    'gdml_evidence_grad': (C.c_int, [_vp, _vp, C.c_int64, _vp, C.POINTER(C.c_int)]),
     'gdml_factor_extend': (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int)]),
     'gdml_factor_remove': (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(C.c_int)]),
     'gdml_select_points': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_double, _vp, _vp, _vp, _ip,
@@ -660,6 +661,19 @@ class Context(object):
         self._check(self._lib.gdml_loo(self._h, _ptr(alphas), alphas.size, {None: 0, 'diag': 1, 'full': 2}[cov], _ptr(resid),
                                        _ptr(c), C.byref(logdet), C.byref(info)))
         return resid, c, logdet.value
+
+    def evidence_grad(self, alphas):
+        """The five sums behind the gradient of the model evidence in sig and lam (gdml_evidence_grad), in normalised units:
+        array (tr A^-1, <A^-1, K'>, a^T K' a, a^T a, log det A) with K' = dK/dsig at the factor's sig and a = -alphas, alphas
+        the library's coefficients -A^-1 y of this factor.  The caller combines them with s^2:
+        d lml / d sig = (<A^-1, K'> - a^T K' a / s^2) / 2, d lml / d lam = (a^T a / s^2 - tr A^-1) / 2.  The rows of L^-T are
+        kept in a second matrix as large as the factor for the duration of the call: MemoryError when it does not fit."""
+        if not hasattr(self, 'n_atoms'):
+            raise GDMLHipError('evidence_grad: no training set resident (train_upload)')
+        alphas = f64(alphas).ravel()
+        terms, info = np.empty(5), C.c_int(0)
+        self._check(self._lib.gdml_evidence_grad(self._h, _ptr(alphas), alphas.size, _ptr(terms), C.byref(info)))
+        return terms
 
     def factor_extend(self, R_desc_new, R_d_desc_new):
         """Append training points (descriptors (b,D), compressed Jacobians (b,D,3)) to the training set and to the factor of

@@ -20,6 +20,66 @@ def integration_constant(E_ref, E_pred):
     return np.sum(E_ref - E_pred) / E_ref.shape[0]
 
 
+def ascend(fun, x0, max_iter=20, gtol=1e-3, bounds=None, max_step=1.0):
+    """Quasi-Newton ascent of a smooth function with backtracking: the stepping rule of
+    GDMLPredict.optimize_hyperparameters, free of any GPU so that it can be tested on its own.
+
+    fun(x) -> (value, gradient) for a 1-d array x; it may raise numpy.linalg.LinAlgError for a point it cannot evaluate (a
+    matrix that is not positive definite), which counts as a failed step and halves the step.  BFGS on the inverse Hessian of
+    -fun, started at the identity; a step is at most max_step in the largest component (the variables are logarithms: a factor
+    e), projected onto bounds = (lower, upper) arrays, and accepted when the value rises by at least 1e-4 of the predicted
+    first-order gain (Armijo); it is halved up to 30 times otherwise.  Ends after max_iter accepted steps, when the largest
+    gradient component is at most gtol (components held by a bound do not count), or when no step is accepted.
+    Returns (x_best, trace): trace holds one (x, value, gradient) per accepted point, the start included, and x_best is the
+    last of them -- the values never decrease along the trace."""
+    x = np.array(x0, dtype=np.float64).ravel()
+    lo = np.full(x.shape, -np.inf) if bounds is None else np.asarray(bounds[0], dtype=np.float64)
+    hi = np.full(x.shape, np.inf) if bounds is None else np.asarray(bounds[1], dtype=np.float64)
+    x = np.clip(x, lo, hi)
+    f, g = fun(x)
+    g = np.asarray(g, dtype=np.float64)
+    H = np.eye(x.size)
+    trace = [(x.copy(), float(f), g.copy())]
+    for _ in range(int(max_iter)):
+        free = ~(((x <= lo) & (g < 0.0)) | ((x >= hi) & (g > 0.0)))
+        if not free.any() or np.abs(g[free]).max() <= gtol:
+            break
+        p = H @ g
+        if np.dot(p, g) <= 0.0:
+            H = np.eye(x.size)
+            p = g.copy()
+        t = min(1.0, max_step / np.abs(p).max())
+        accepted = None
+        for _half in range(30):
+            xn = np.clip(x + t * p, lo, hi)
+            step = xn - x
+            if not step.any():
+                break
+            try:
+                fn, gn = fun(xn)
+            except np.linalg.LinAlgError:
+                t *= 0.5
+                continue
+            if np.isfinite(fn) and fn >= f + 1e-4 * np.dot(g, step):
+                accepted = (xn, float(fn), np.asarray(gn, dtype=np.float64))
+                break
+            t *= 0.5
+        if accepted is None:
+            break
+        xn, fn, gn = accepted
+        sv, yv = xn - x, g - gn
+        sy = np.dot(sv, yv)
+        if sy > 1e-12 * np.linalg.norm(sv) * np.linalg.norm(yv):
+            rho = 1.0 / sy
+            V = np.eye(x.size) - rho * np.outer(sv, yv)
+            H = V @ H @ V.T + rho * np.outer(sv, sv)
+        else:
+            H = np.eye(x.size)
+        x, f, g = xn, fn, gn
+        trace.append((x.copy(), f, g.copy()))
+    return x, trace
+
+
 class GDMLPredict(object):
     def __init__(
         self,
@@ -109,6 +169,8 @@ class GDMLPredict(object):
         # idxs_train as export_model writes it once the training set was edited (-1 for added points, removed entries dropped)
         self._idxs_train = np.asarray(model['idxs_train']).astype(np.int64) if 'idxs_train' in model else None
         self._edited = False
+        self._unc_prepared = False  # the factor of prepare_uncertainty() is resident (optimize_hyperparameters restores it)
+        self._hyper_edited = False  # optimize_hyperparameters moved sig / lam: export_model writes them
 
     def __del__(self):
         for ctx in getattr(self, '_replicas', []):
@@ -285,10 +347,12 @@ class GDMLPredict(object):
         self._ctx.uncert_prepare(self.sig, self._lam)
         self.uncertainty_scale = scale
         self._unc_R, self._unc_gd, self._unc_y = (R_train.copy(), gd, y) if y is not None else (None, None, None)
+        self._unc_prepared = True
 
     def release_uncertainty(self):
         """Free the resident factor of prepare_uncertainty()."""
         self._ctx.uncert_release()
+        self._unc_prepared = False
 
     def predict_uncertainty(self, R, full_cov=False, low_latency=False):
         """(E, F, var) for geometries R (B,3N) or (3N,): E, F as predict(R); var (B,3N) the marginal posterior variances of
@@ -356,6 +420,153 @@ class GDMLPredict(object):
             out['log_marginal_likelihood'] = float(-0.5 * (-np.dot(y, alphas)) / s2 - 0.5 * (logdet + n * np.log(s2))
                                                    - 0.5 * n * np.log(2.0 * np.pi))
         return out
+
+    # ---- gradient of the model evidence in sig and lam, and its ascent (csrc/evidence.hip)
+
+    @staticmethod
+    def _evidence_from_terms(y, alphas, terms, sig, lam):
+        n = y.size
+        yAy = float(-np.dot(y, alphas))
+        s2 = yAy / n
+        tr, ik, aka, aa, logdet = (float(t) for t in terms)
+        d_sig = 0.5 * (ik - aka / s2)
+        d_lam = 0.5 * (aa / s2 - tr)
+        return {'log_marginal_likelihood': float(-0.5 * yAy / s2 - 0.5 * (logdet + n * np.log(s2)) - 0.5 * n * np.log(2.0 * np.pi)),
+                'signal_variance': s2, 'd_sig': d_sig, 'd_lam': d_lam, 'd_log_sig': sig * d_sig, 'd_log_lam': lam * d_lam,
+                'log_det_A': logdet, 'terms': np.array(terms, dtype=np.float64)}
+
+    def evidence_gradient(self, F_train=None):
+        """The model evidence (log marginal likelihood of the normalised training labels) and its gradient in the length scale
+        sig and the regularisation lam, from the factor of prepare_uncertainty(): what type-II maximum likelihood needs to
+        set both without a grid of retrainings and without held-back data.
+
+        The labels are F_train (M,3N), or those given to prepare_uncertainty(R_train, F_train); ValueError without either.
+        The coefficients are solved through the resident factor, as in loo_errors(F_train), and the signal variance is its
+        maximum-likelihood value s^2 = y^T A^-1 y / n, at which the partial derivatives below are the total derivatives of
+        the profiled evidence.  Returns a dict:
+            'log_marginal_likelihood'   -1/2 y^T A^-1 y / s^2 - 1/2 (log det A + n log s^2) - n/2 log 2 pi  (as loo_errors)
+            'signal_variance'           s^2
+            'd_sig', 'd_lam'            1/2 (<A^-1, K'> - a^T K' a / s^2),  1/2 (a^T a / s^2 - tr A^-1),  K' = dK/dsig
+            'd_log_sig', 'd_log_lam'    sig d_sig, lam d_lam: the gradient in (log sig, log lam)
+            'log_det_A', 'terms'        the raw sums (tr A^-1, <A^-1, K'>, a^T K' a, a^T a, log det A) of gdml_evidence_grad
+        MEMORY: the call keeps the rows of L^-T in a second matrix as large as the factor, so it needs twice the factor's
+        memory (MemoryError otherwise).  Models with energy constraints raise NotImplementedError."""
+        if self._use_E_cstr:
+            raise NotImplementedError('the evidence gradient of models with energy constraints is not supported')
+        n = 3 * self.n_atoms * self.n_train
+        if F_train is not None:
+            y = np.asarray(F_train, dtype=np.float64).ravel() / self.std
+            if y.size != n:
+                raise ValueError('F_train holds {} values, the model has {} coefficients'.format(y.size, n))
+        elif self._unc_y is not None:
+            y = self._unc_y
+        else:
+            raise ValueError('evidence_gradient needs F_train, here or in prepare_uncertainty(R_train, F_train)')
+        alphas = self._ctx.chol_solve(y)
+        terms = self._ctx.evidence_grad(alphas)
+        return self._evidence_from_terms(y, alphas, terms, self.sig, self._lam)
+
+    def optimize_hyperparameters(self, R_train, F_train, E_train=None, params=('sig', 'lam'), max_iter=20, gtol=1e-3,
+                                 bounds=None):
+        """Set sig and / or lam by ascent of the profiled model evidence in (log sig, log lam) (type-II maximum likelihood): a
+        BFGS step with backtracking on the evidence (`ascend`), every trial point one factorisation of the system matrix on the
+        first GPU plus one evidence_gradient().  A trial point whose matrix is not positive definite counts as a failed step.
+
+        R_train (M,3N), F_train (M,3N): the training geometries and labels in the model's order (checked as in
+        prepare_uncertainty).  params: which of 'sig', 'lam' move.  gtol: the ascent ends when every component of the gradient
+        in the logarithms is at most gtol.  bounds: {'sig': (lo, hi), 'lam': (lo, hi)}; default sig within a factor 100 of the
+        model's, lam in [1e-14, 1e2].  E_train (M,): the integration constant c is recomputed by the trainer's rule.
+
+        Afterwards the model's sig, lam and alphas_F are those of the best point (the coefficients solved through that point's
+        factor, which stays resident as after prepare_uncertainty(R_train, F_train)), every replica predicts with them and
+        export_model() returns them; the stored validation errors are reset to NaN.  On any exception the predictor -- and
+        the resident factor, if there was one -- is left as it was.
+        Returns the trace: one dict {'sig', 'lam', 'log_marginal_likelihood', 'd_log_sig', 'd_log_lam'} per accepted point,
+        the start first."""
+        if self._use_E_cstr:
+            raise NotImplementedError('optimising the hyper-parameters of models with energy constraints is not supported')
+        if self._lam is None:
+            raise ValueError("the model carries no regularisation strength 'lam'")
+        params = tuple(params)
+        if not params or any(k not in ('sig', 'lam') for k in params) or len(set(params)) != len(params):
+            raise ValueError("params must name 'sig', 'lam' or both")
+        n3 = 3 * self.n_atoms
+        R_train = np.asarray(R_train, dtype=np.float64)
+        if R_train.size != self.n_train * n3:
+            raise ValueError('R_train holds {} values, the model was trained on {} geometries of {} atoms'.format(
+                R_train.size, self.n_train, self.n_atoms))
+        R_train = R_train.reshape(self.n_train, n3)
+        y = np.asarray(F_train, dtype=np.float64).ravel() / self.std
+        if y.size != self.n_train * n3:
+            raise ValueError('F_train holds {} values, the model has {} coefficients'.format(y.size, self.n_train * n3))
+        if E_train is not None:
+            E_train = np.asarray(E_train, dtype=np.float64).ravel()
+            if E_train.size != self.n_train:
+                raise ValueError('E_train holds {} energies, the model has {} training points'.format(E_train.size, self.n_train))
+        dflt = {'sig': (self.sig / 100.0, self.sig * 100.0), 'lam': (1e-14, 1e2)}
+        bounds = dict(dflt, **(bounds or {}))
+        fixed = {'sig': self.sig, 'lam': self._lam}
+        # the variables are the logarithms RELATIVE to the model's values: the start is 0, i.e. exactly the model's point
+        lo = np.log([float(bounds[k][0]) / fixed[k] for k in params])
+        hi = np.log([float(bounds[k][1]) / fixed[k] for k in params])
+        ctx = self._ctx
+        xd, gd = ctx.desc_from_R(R_train, self.n_atoms, self.lat_and_inv)
+        if not np.allclose(xd, self._R_desc_train, rtol=1e-10, atol=0.0):
+            raise ValueError("R_train does not reproduce the model's training descriptors (wrong geometries or order)")
+        keys = ('sig', '_lam', '_alphas_F', '_R_d_desc_alpha', 'c', 'uncertainty_scale', '_unc_R', '_unc_gd', '_unc_y', '_edited',
+                '_hyper_edited', '_unc_prepared', '_train_resident', '_replicas_stale')
+        saved = {k: getattr(self, k) for k in keys}
+        last = {}
+
+        def point(xv):
+            hp = dict(fixed)
+            hp.update({k: fixed[k] * float(np.exp(v)) for k, v in zip(params, xv)})
+            return hp
+
+        def fun(xv):
+            hp = point(xv)
+            ctx.uncert_prepare(hp['sig'], hp['lam'])  # numpy.linalg.LinAlgError: a failed step
+            alphas = ctx.chol_solve(y)
+            ev = self._evidence_from_terms(y, alphas, ctx.evidence_grad(alphas), hp['sig'], hp['lam'])
+            last.update(x=np.array(xv), alphas=alphas, ev=ev)
+            return ev['log_marginal_likelihood'], np.array([ev['d_log_' + k] for k in params])
+
+        try:
+            ctx.train_upload(xd, gd, self._tril_perms)
+            self._train_resident = False
+            x_best, tr = ascend(fun, np.zeros(len(params)), max_iter=max_iter, gtol=gtol, bounds=(lo, hi))
+            if not np.array_equal(last['x'], x_best):  # the last trial was rejected: the best point's factor once more
+                fun(x_best)
+            hp, alphas, ev = point(x_best), last['alphas'], last['ev']
+            R_d_desc_alpha = self.desc.d_desc_dot_vec(gd, alphas.reshape(-1, n3))
+            for c_ in [ctx] + self._replicas:
+                c_.predict_upload_model(self._R_desc_train, R_d_desc_alpha, self._tril_perms, hp['sig'], None)
+            self.sig, self._lam = hp['sig'], hp['lam']
+            self._alphas_F, self._R_d_desc_alpha = alphas, R_d_desc_alpha
+            self._replicas_stale = False
+            self.uncertainty_scale = ev['signal_variance']
+            self._unc_R, self._unc_gd, self._unc_y = R_train.copy(), gd, y
+            self._unc_prepared = True
+            self._edited = self._hyper_edited = True
+            if E_train is not None:
+                self.c = 0.0
+                self.c = float(integration_constant(E_train, self.predict(R_train)[0]))
+        except BaseException:
+            for k, v in saved.items():
+                setattr(self, k, v)
+            try:
+                for c_ in [ctx] + self._replicas:
+                    c_.predict_upload_model(self._R_desc_train, self._R_d_desc_alpha, self._tril_perms, self.sig, None)
+                if saved['_unc_prepared']:  # the same assembly and factorisation as before: the same bits
+                    ctx.train_upload(xd, gd, self._tril_perms)
+                    ctx.uncert_prepare(self.sig, self._lam)
+                else:
+                    ctx.uncert_release()
+            except Exception:
+                self.log.error('optimize_hyperparameters: the resident factor could not be restored')
+            raise
+        return [dict(point(xv), log_marginal_likelihood=f, **{'d_log_' + k: float(gk) for k, gk in zip(params, gv)})
+                for xv, f, gv in tr]
 
     # ---- growing the training set through the resident factor (csrc/extend.hip)
 
@@ -604,7 +815,8 @@ class GDMLPredict(object):
 
     def export_model(self):
         """The current model as a dict in the reference's schema (what GDMLPredict and the model files take): the keys the
-        constructor was given, with R_desc, R_d_desc_alpha, alphas_F, c and std as they are now.  After add_training_points
+        constructor was given, with R_desc, R_d_desc_alpha, alphas_F, c and std as they are now (and sig and lam after
+        optimize_hyperparameters).  After add_training_points
         idxs_train carries -1 for every added point (they come from no dataset index), after remove_training_points it has
         lost the removed entries, and the stored validation errors are reset to NaN, as the trainer sets them for a model that
         has not been validated."""
@@ -615,6 +827,8 @@ class GDMLPredict(object):
             m['alphas_F'] = self._alphas_F
         m['c'] = self.c
         m['std'] = self.std
+        if self._hyper_edited:
+            m['sig'], m['lam'] = self.sig, self._lam
         if self._edited:
             if self._idxs_train is not None:
                 m['idxs_train'] = self._idxs_train.copy()
