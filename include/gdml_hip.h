@@ -132,6 +132,7 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *   nys.trsm_left (1)     tall triangular solves of the Nystroem build left-looking (one deep product per 512-column strip); 0 = right-looking
  *   chol.nb (512)         panel width of the blocked Cholesky (a multiple of 64 up to 512, anything else falls back to 512)
  *   chol.fused_min_rows (12288)  trailing rows from which a panel's diagonal block is factored inside the trailing-update launch
+ *                         (at least 1: a fused launch needs a trailing matrix; smaller values are taken as 1)
  *   chol.outer (1024)     panel pairs: K = 2 nb trailing update in two launches (= chol.nb, or chol.nb not a multiple of 128:
  *                         single panels only)
  *   chol.outer_min_rows (16384)  trailing rows below which new panels are single again

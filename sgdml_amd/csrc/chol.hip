@@ -1336,7 +1336,11 @@ int chol_factor_device(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int* inf
   // hidden inside the SYRK launch; only the row-local solve (one launch) stays between two GEMM launches.  Near the end (SYRK
   // shorter than the single-workgroup block factorisation) the block is factored by the multi-workgroup step chain instead.
   hipStream_t st = ctx->stream;
-  const int64_t min_rows = (int64_t)ctx_opt(ctx, "chol.fused_min_rows", 12288);
+  int64_t min_rows = (int64_t)ctx_opt(ctx, "chol.fused_min_rows", 12288);
+  // a fused launch needs a trailing matrix to ride in: with 0 the last panel of a matrix with a carried right-hand-side
+  // row (n - t1 = 0, n_rows - t1 = 1) asked for a fused launch with an empty update, which launch_gemm_nt_sub_part skips
+  // together with its diagonal-block workgroup -- the block was never factored
+  if (min_rows < 1) min_rows = 1;
   // Panel PAIRS: while the trailing matrix is large, two NB-wide panels a | b form an outer panel of OB = 2 NB columns
   // and the bulk of the trailing update runs with K = OB, which halves the C read-modify-write traffic per flop of the
   // SYRK (its epilogue is ~6 % of the launch at K = 512).  ONE lower SYRK covers everything right of the finished panel, in
