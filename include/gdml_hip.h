@@ -309,6 +309,24 @@ int gdml_predict(gdml_ctx* ctx, const double* R, int64_t B, const double* lat,
 int gdml_predict_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat,
                      const double* lat_inv, double* E_dev, double* F_dev);
 
+/* Strain derivative (virial) of B geometries: what pressure, NPT dynamics, cell relaxation and equation-of-state scans of a
+ * periodic model need, and what its forces cannot give (with minimum-image pair vectors sum_i f_i (x) r_i is not the strain
+ * derivative).  The reference has no counterpart.  Straining atoms and cell together, r -> (I + eps) r, lattice -> (I + eps)
+ * lattice, leaves the minimum-image integers as they are, so with the descriptor-space gradient F_x of the predictor
+ * (F = J_x^T F_x), d_k the minimum-image pair vector of descriptor entry k, x_k = 1 / |d_k| and g_k = d_k / |d_k|^3:
+ *   W = dE' / d eps = sum_k F_x[k] g_k (x) d_k        (symmetric 3 x 3; stress = std W / |det lattice|, +dE/d eps: ASE's sign)
+ * Outputs are UNSCALED like gdml_predict (the caller multiplies by std): E_out (B) = E', F_out (B,3N) = F (both may be NULL)
+ * and bit-identical to gdml_predict's for the same input on the same route, W_out (B,3,3) row-major, both triangles written.
+ * R may not be NULL (no training-set mode); lat / lat_inv both or neither -- without a lattice W is still defined and equals
+ * -sum_i f_i (x) r_i.  One to eight host geometries (the shapes of predict.fused) stay ONE launch without a copy: W follows F
+ * in the host-mapped block.  Every other route ends in an epilogue that sums W next to the back-projection (d_k = g_k / x_k^3
+ * from the query tables).  fp64 throughout, fixed reduction trees, no atomics: the same input on the same context gives
+ * bit-identical results, and the _dev variant (device pointers throughout) equals the host one on the same route. */
+int gdml_predict_virial(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv,
+                        double* E_out, double* F_out, double* W_out);
+int gdml_predict_virial_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat,
+                            const double* lat_inv, double* E_dev, double* F_dev, double* W_dev);
+
 /* Analytic Hessians (force constants) H' = d^2 E' / dR^2 of B geometries, unscaled like gdml_predict (the caller
  * multiplies by std).  The reference has no counterpart: its users take finite differences of predict().
  * With the predictor's per-row quantities (d = x - X_rho, n = sqrt5 |d|, b = 5/(3 sig^3) exp(-n/sig), a = d . v_rho,

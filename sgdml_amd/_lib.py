@@ -47,6 +47,8 @@ SIGNATURES = {
     'gdml_set_alphas': (C.c_int, [_vp, _vp, _vp]),
     'gdml_predict': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     'gdml_predict_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
+    'gdml_predict_virial': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_predict_virial_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_uncert_prepare': (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_int)]),
@@ -542,6 +544,32 @@ class Context(object):
             self._check(self._lib.gdml_predict(self._h, _ptr(R[b0:b1]), b1 - b0, _ptr(lat), _ptr(lat_inv), _ptr(Ec),
                                                _ptr(F[b0:b1])))
         return E, F
+
+    def predict_virial(self, R, lat_and_inv=None):
+        """Unscaled E' (B,), F (B,3N) and strain derivative W = dE'/d eps (B,3,3) of geometries R (B,3N) (gdml_predict_virial);
+        batches beyond max_query_batch go through in slices, as in predict()."""
+        if R is None:
+            raise ValueError('predict_virial needs geometries (there is no training-set mode)')
+        n3 = 3 * self.model_n_atoms
+        R = f64(R).reshape(-1, n3)
+        B = R.shape[0]
+        E, F, W = np.empty(B), np.empty((B, n3)), np.empty((B, 3, 3))
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        for b0 in range(0, max(B, 1), self.max_query_batch):
+            b1 = min(B, b0 + self.max_query_batch)
+            self._check(self._lib.gdml_predict_virial(self._h, _ptr(R[b0:b1]), b1 - b0, _ptr(lat), _ptr(lat_inv),
+                                                      _ptr(E[b0:b1]), _ptr(F[b0:b1]), _ptr(W[b0:b1])))
+        return E, F, W
+
+    def predict_virial_dev(self, R_dev, B, E_dev, F_dev, W_dev, lat_and_inv=None):
+        """gdml_predict_virial_dev on device pointers (ints or c_void_p; E_dev / F_dev may be None)."""
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        self._check(self._lib.gdml_predict_virial_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), E_dev, F_dev,
+                                                      W_dev))
 
     def hessian_batch(self):
         """Geometries per gdml_predict_hessian call: max_query_batch scaled down by the 3N-fold larger output (9N^2 vs 3N)."""

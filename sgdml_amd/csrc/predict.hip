@@ -810,6 +810,112 @@ __global__ void __launch_bounds__(256) predict_epilogue_kernel(const double* __r
   }
 }
 
+// predict_epilogue_kernel plus the strain derivative W = dE'/d eps = sum_k F_x[k] g_k (x) d_k of gdml_predict_virial (atoms and
+// cell strained together: the minimum-image integers do not move, d_k -> (I + eps) d_k).  E and F: the statements of
+// predict_epilogue_kernel in the same order (the same bits; F_out may be NULL).  The pair vector is taken from the query
+// tables, d_k = g_k / x_k^3, so every summand is (F_x[k] / x_k^3) g_k g_k^T: six components, the lower triangle mirrored.
+// Fixed reduction tree: thread t sums k = t, t + 256, ... in order -> xor-shuffle tree over the wavefront -> the four
+// wavefronts in order through LDS.  No atomics.
+template <bool LDSFX>
+__global__ void __launch_bounds__(256) predict_epilogue_virial_kernel(const double* __restrict__ part_F,
+                                                                      const double* __restrict__ part_E,
+                                                                      const double* __restrict__ xq,
+                                                                      const double* __restrict__ gq,
+                                                                      int64_t B, int N, int D, int JS,
+                                                                      double* __restrict__ E_out,
+                                                                      double* __restrict__ F_out,
+                                                                      double* __restrict__ W_out) {
+  extern __shared__ __attribute__((aligned(16))) double fxs[];
+  __shared__ double s_w[4][6];
+  const int64_t q = blockIdx.x;
+  const int tid = threadIdx.x, T = blockDim.x;
+  const double* fx = LDSFX ? fxs : part_F + q * D;
+  if (LDSFX) {
+    for (int k = tid; k < D; k += T) {
+      double s = 0.0;
+      for (int sp0 = 0; sp0 < JS; sp0 += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int sp = sp0 + u < JS ? sp0 + u : JS - 1;
+          v[u] = part_F[((int64_t)sp * B + q) * D + k];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          if (sp0 + u < JS) s += v[u];
+      }
+      fxs[k] = s;
+    }
+  }
+  if (tid == 0 && E_out) {
+    double s = 0.0;
+    for (int sp0 = 0; sp0 < JS; sp0 += 8) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = part_E[(int64_t)(sp0 + u < JS ? sp0 + u : JS - 1) * B + q];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (sp0 + u < JS) s += v[u];
+    }
+    E_out[q] = s;
+  }
+  __syncthreads();
+  const double* g = gq + q * 3 * D;
+  if (F_out) {
+    for (int t = tid; t < 3 * N; t += T) {
+      const int a = t / 3, al = t - 3 * a;
+      const int other = a == 0 ? 1 : 0;
+      double s = 0.0;
+      for (int m0 = 0; m0 < N && N >= 2; m0 += 8) {
+        double gv[8], fv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int mc = m0 + u < N ? m0 + u : N - 1;
+          const int k = pair_idx(a, mc == a ? other : mc);
+          gv[u] = g[k * 3 + al];
+          fv[u] = fx[k];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int m = m0 + u;
+          if (m < N && m != a) {
+            const double v = gv[u] * fv[u];
+            s += (a < m) ? v : -v;
+          }
+        }
+      }
+      F_out[q * 3 * N + t] = s;
+    }
+  }
+  const double* x = xq + q * D;
+  double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // xx, yy, zz, yz, xz, xy
+  for (int k = tid; k < D; k += T) {
+    const double xk = x[k];
+    const double g0 = g[k * 3], g1 = g[k * 3 + 1], g2 = g[k * 3 + 2];
+    const double c = fx[k] / (xk * xk * xk);
+    const double c0 = c * g0, c1 = c * g1, c2 = c * g2;
+    w[0] += c0 * g0;
+    w[1] += c1 * g1;
+    w[2] += c2 * g2;
+    w[3] += c1 * g2;
+    w[4] += c0 * g2;
+    w[5] += c0 * g1;
+  }
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const double v = wave_sum(w[c]);
+    if ((tid & 63) == 0) s_w[tid >> 6][c] = v;
+  }
+  __syncthreads();
+  if (tid < 6) {
+    const double v = (s_w[0][tid] + s_w[1][tid]) + (s_w[2][tid] + s_w[3][tid]);
+    const int r = tid < 3 ? tid : (tid == 3 ? 1 : 0), cc = tid < 3 ? tid : (tid == 5 ? 1 : 2);
+    double* W = W_out + q * 9;
+    W[r * 3 + cc] = v;
+    W[cc * 3 + r] = v;
+  }
+}
+
 template <int KPL, int QB>
 static void launch_pred(gdml_ctx* ctx, const PredArgs& A) {
   int64_t n_qt = (A.B + QB - 1) / QB;
@@ -830,8 +936,10 @@ static void dispatch_qb(gdml_ctx* ctx, const PredArgs& A, int QB) {
 
 static int max_qb_for(int KPL) { return KPL <= 4 ? 8 : (KPL == 8 ? 4 : (KPL == 16 ? 2 : 1)); }
 
-int predict_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B, double* d_E,
-                   double* d_F) {
+// d_W == nullptr: the launches of gdml_predict.  Otherwise the epilogue is predict_epilogue_virial_kernel, which also writes
+// W (B,3,3); d_F may then be NULL.
+static int predict_device_w(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B, double* d_E, double* d_F,
+                            double* d_W) {
   Model& md = ctx->model;
   if (!md.xp) return gdml_fail(ctx, GDML_ERR_STATE, "predict: no model resident");
   if (B == 0) return GDML_OK;
@@ -854,7 +962,13 @@ int predict_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_
     const int slot = ktime_begin(ctx);
     GDML_TRY(predict_wide_device(ctx, d_xq, B, part, part + B * (int64_t)D));
     ktime_end(ctx, slot, "predict", 10.0 * (double)D * (double)B * (double)MP);
-    if (beyond)  // F_x row longer than the LDS row of the epilogue: read in place (JS = 1)
+    if (d_W && beyond)
+      hipLaunchKernelGGL(predict_epilogue_virial_kernel<false>, dim3((unsigned)B), dim3(256), 0, ctx->stream, part,
+                         part + B * (int64_t)D, d_xq, d_gq, B, N, D, 1, d_E, d_F, d_W);
+    else if (d_W)
+      hipLaunchKernelGGL(predict_epilogue_virial_kernel<true>, dim3((unsigned)B), dim3(256), (size_t)D * 8, ctx->stream,
+                         part, part + B * (int64_t)D, d_xq, d_gq, B, N, D, 1, d_E, d_F, d_W);
+    else if (beyond)  // F_x row longer than the LDS row of the epilogue: read in place (JS = 1)
       hipLaunchKernelGGL(predict_epilogue_kernel<false>, dim3((unsigned)B), dim3(256), 0, ctx->stream, part,
                          part + B * (int64_t)D, d_gq, B, N, D, 1, d_E, d_F);
     else
@@ -962,13 +1076,22 @@ int predict_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_
   ctx->launch_counter++;
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(predict_epilogue_kernel<true>, dim3((unsigned)B), dim3(256), (size_t)D * 8,
-                       ctx->stream, A.part_F, A.part_E, d_gq, B, N, D, (int)JS, d_E, d_F);
+    if (d_W)
+      hipLaunchKernelGGL(predict_epilogue_virial_kernel<true>, dim3((unsigned)B), dim3(256), (size_t)D * 8,
+                         ctx->stream, A.part_F, A.part_E, d_xq, d_gq, B, N, D, (int)JS, d_E, d_F, d_W);
+    else
+      hipLaunchKernelGGL(predict_epilogue_kernel<true>, dim3((unsigned)B), dim3(256), (size_t)D * 8,
+                         ctx->stream, A.part_F, A.part_E, d_gq, B, N, D, (int)JS, d_E, d_F);
     ctx->launch_counter++;
     e = hipGetLastError();
   }
   if (e != hipSuccess) return gdml_fail(ctx, GDML_ERR_HIP, "predict launch: %s", hipGetErrorString(e));
   return GDML_OK;
+}
+
+int predict_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B, double* d_E,
+                   double* d_F) {
+  return predict_device_w(ctx, d_xq, d_gq, B, d_E, d_F, nullptr);
 }
 
 static int model_free(gdml_ctx* ctx) {
@@ -1122,7 +1245,9 @@ __device__ __forceinline__ void fused_pair_of(int k, int& i, int& j) {  // k = i
   j = k - i * (i - 1) / 2;
 }
 
-template <int KPL>
+// VIRIAL (gdml_predict_virial): the query's last workgroup also sums W = sum_k F_x[k] d_k (x) d_k / |d_k|^3 from the pair
+// vectors it recomputes for the Jacobian, and writes it as (B, 9) behind F in the mapped block.
+template <int KPL, bool VIRIAL = false>
 __global__ void __launch_bounds__(256) predict_fused_kernel(FusedArgs A) {
   __shared__ double s_fx[4][KPL * 64];  // per-wavefront F_x; reused by the query's last workgroup: [0] = its summed F_x
   __shared__ double s_E[4];
@@ -1245,6 +1370,7 @@ __global__ void __launch_bounds__(256) predict_fused_kernel(FusedArgs A) {
     if (k < D) fxs[k] = s;
     else if (A.want_E) A.out[q] = s;
   }
+  double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // VIRIAL: xx, yy, zz, yz, xz, xy of this thread's pairs
   for (int k = tid; k < D; k += 256) {  // Jacobian entries (r_i - r_j) / d^3  (desc.py:193-205)
     int i, j;
     fused_pair_of(k, i, j);
@@ -1255,8 +1381,34 @@ __global__ void __launch_bounds__(256) predict_fused_kernel(FusedArgs A) {
     s_g[k * 3 + 0] = d[0] * inv3;
     s_g[k * 3 + 1] = d[1] * inv3;
     s_g[k * 3 + 2] = d[2] * inv3;
+    if constexpr (VIRIAL) {
+      const double c = fxs[k] * inv3;  // fxs[k] was written by this thread
+      const double c0 = c * d[0], c1 = c * d[1], c2 = c * d[2];
+      w[0] += c0 * d[0];
+      w[1] += c1 * d[1];
+      w[2] += c2 * d[2];
+      w[3] += c1 * d[2];
+      w[4] += c0 * d[2];
+      w[5] += c0 * d[1];
+    }
+  }
+  if constexpr (VIRIAL) {  // fixed tree: per-thread sums -> xor shuffles -> the four wavefronts in order (s_fx[1] is free here)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      const double v = wave_sum(w[c]);
+      if (lane == 0) s_fx[1][wave * 6 + c] = v;
+    }
   }
   __syncthreads();
+  if constexpr (VIRIAL) {
+    if (tid < 6) {
+      const double v = (s_fx[1][tid] + s_fx[1][6 + tid]) + (s_fx[1][12 + tid] + s_fx[1][18 + tid]);
+      const int r = tid < 3 ? tid : (tid == 3 ? 1 : 0), cc = tid < 3 ? tid : (tid == 5 ? 1 : 2);
+      double* W = A.out + B + (int64_t)B * 3 * N + q * 9;
+      W[r * 3 + cc] = v;
+      W[cc * 3 + r] = v;
+    }
+  }
   for (int t = tid; t < 3 * N; t += 256) {  // F = J_x^T F_x  (desc.py:405-408), same order as predict_epilogue_kernel
     const int a = t / 3, al = t - 3 * a;
     double s = 0.0;
@@ -1283,7 +1435,7 @@ __global__ void __launch_bounds__(256) predict_fused_kernel(FusedArgs A) {
 
 // Host side of the single-launch path.  Returns GDML_OK with *done = 0 when the shape is not served.
 static int predict_fused(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv, double* E_out,
-                         double* F_out, int* done) {
+                         double* F_out, double* W_out, int* done) {
   *done = 0;
   Model& md = ctx->model;
   const int N = md.N, D = md.D;
@@ -1334,10 +1486,18 @@ static int predict_fused(gdml_ctx* ctx, const double* R, int64_t B, const double
   int KPL = 1;
   while (KPL * 64 < D) KPL <<= 1;
   const dim3 grid((unsigned)n_wg, (unsigned)B);
-  switch (KPL) {
-    case 1: hipLaunchKernelGGL(predict_fused_kernel<1>, grid, dim3(256), 0, ctx->stream, A); break;
-    case 2: hipLaunchKernelGGL(predict_fused_kernel<2>, grid, dim3(256), 0, ctx->stream, A); break;
-    default: hipLaunchKernelGGL(predict_fused_kernel<4>, grid, dim3(256), 0, ctx->stream, A); break;
+  if (W_out) {
+    switch (KPL) {
+      case 1: hipLaunchKernelGGL((predict_fused_kernel<1, true>), grid, dim3(256), 0, ctx->stream, A); break;
+      case 2: hipLaunchKernelGGL((predict_fused_kernel<2, true>), grid, dim3(256), 0, ctx->stream, A); break;
+      default: hipLaunchKernelGGL((predict_fused_kernel<4, true>), grid, dim3(256), 0, ctx->stream, A); break;
+    }
+  } else {
+    switch (KPL) {
+      case 1: hipLaunchKernelGGL(predict_fused_kernel<1>, grid, dim3(256), 0, ctx->stream, A); break;
+      case 2: hipLaunchKernelGGL(predict_fused_kernel<2>, grid, dim3(256), 0, ctx->stream, A); break;
+      default: hipLaunchKernelGGL(predict_fused_kernel<4>, grid, dim3(256), 0, ctx->stream, A); break;
+    }
   }
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
@@ -1368,29 +1528,31 @@ static int predict_fused(gdml_ctx* ctx, const double* R, int64_t B, const double
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
   const double* h_out = ctx->h_map + 8;
   if (E_out) memcpy(E_out, h_out, (size_t)B * 8);
-  memcpy(F_out, h_out + B, (size_t)B * 3 * N * 8);
+  if (F_out) memcpy(F_out, h_out + B, (size_t)B * 3 * N * 8);
+  if (W_out) memcpy(W_out, h_out + B + B * 3 * N, (size_t)B * 9 * 8);
   *done = 1;
   return GDML_OK;
 }
 
+// W_out != nullptr: gdml_predict_virial (R given; E_out and F_out may be NULL).  W_out == nullptr: gdml_predict, as ever.
 static int predict_common(gdml_ctx* ctx, const double* R, bool R_on_device, int64_t B,
                           const double* lat, const double* lat_inv, double* E_out, double* F_out,
-                          bool out_on_device) {
+                          bool out_on_device, double* W_out = nullptr) {
   Model& md = ctx->model;
   if (!md.xp) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_predict: upload a model first");
-  if (!F_out) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict: F_out is NULL");
+  if (!F_out && !W_out) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict: F_out is NULL");
   if ((lat == nullptr) != (lat_inv == nullptr))
     return gdml_fail(ctx, GDML_ERR_INVALID, "lattice and inverse must both be given or both NULL");
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int N = md.N, D = md.D;
   if (R != nullptr && !R_on_device && !out_on_device && B >= 1 && B <= FUSED_MAX_Q) {
     int done = 0;
-    GDML_TRY(predict_fused(ctx, R, B, lat, lat_inv, E_out, F_out, &done));
+    GDML_TRY(predict_fused(ctx, R, B, lat, lat_inv, E_out, F_out, W_out, &done));
     if (done) return GDML_OK;
   }
   const double *d_xq, *d_gq;
   double* buf = nullptr;
-  double *d_E = E_out, *d_F = F_out;
+  double *d_E = E_out, *d_F = F_out, *d_W = W_out;
   bool use_pin = false;
   constexpr int64_t PIN_BYTES = 1 << 20;
   if (R == nullptr) {  // training-set mode (predict.py:1221-1233)
@@ -1409,7 +1571,8 @@ static int predict_common(gdml_ctx* ctx, const double* R, bool R_on_device, int6
   } else {
     if (B < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict: B < 0");
     if (B == 0) return GDML_OK;
-    int64_t nR = B * N * 3, nx = B * (int64_t)D, ng = nx * 3, nout = out_on_device ? 0 : B + nR;
+    const int64_t nW = W_out ? B * 9 : 0;  // W follows E and F in the work buffer and in the pinned block
+    int64_t nR = B * N * 3, nx = B * (int64_t)D, ng = nx * 3, nout = out_on_device ? 0 : B + nR + nW;
     GDML_TRY(ctx_scratch(ctx, (nR + nx + ng + nout) * 8, &buf));
     double* d_R = buf;
     double* dx = buf + nR;
@@ -1423,6 +1586,21 @@ static int predict_common(gdml_ctx* ctx, const double* R, bool R_on_device, int6
       else
         use_pin = false;
     }
+    // W rides in the same pinned block, so the batch size at which the staged path ends is gdml_predict's: 9 B doubles fit
+    // into a second PIN_BYTES (72 B <= 8 B (6 N + 1) <= PIN_BYTES from N = 2 on); the block grows once, on the first such call
+    if (use_pin && nW && (nR + B + nR + nW) * 8 > ctx->h_pin_bytes) {
+      double* grown = nullptr;
+      if ((nR + B + nR + nW) * 8 <= 2 * PIN_BYTES &&
+          hipHostMalloc((void**)&grown, 2 * PIN_BYTES, hipHostMallocDefault) == hipSuccess) {
+        HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipHostFree(ctx->h_pin);
+        ctx->h_pin = grown;
+        ctx->h_pin_bytes = 2 * PIN_BYTES;
+      } else {
+        (void)hipGetLastError();
+        use_pin = false;
+      }
+    }
     if (R_on_device) {
       HIP_CHECK(ctx, hipMemcpyAsync(d_R, R, nR * 8, hipMemcpyDeviceToDevice, ctx->stream));
     } else if (use_pin) {
@@ -1434,6 +1612,7 @@ static int predict_common(gdml_ctx* ctx, const double* R, bool R_on_device, int6
     if (!out_on_device) {
       d_E = dg + ng;
       d_F = d_E + B;
+      if (W_out) d_W = d_F + nR;
     }
     phase_begin(ctx);
     GDML_TRY(desc_device(ctx, R_on_device ? R : d_R, B, N, lat, lat_inv, dx, dg));
@@ -1441,22 +1620,40 @@ static int predict_common(gdml_ctx* ctx, const double* R, bool R_on_device, int6
     d_gq = dg;
   }
   if (R == nullptr) phase_begin(ctx);
-  GDML_TRY(predict_device(ctx, d_xq, d_gq, B, (E_out || !out_on_device) ? d_E : nullptr, d_F));
+  GDML_TRY(predict_device_w(ctx, d_xq, d_gq, B, (E_out || !out_on_device) ? d_E : nullptr, d_F, d_W));
   GDML_TRY(phase_end(ctx, "predict"));
   if (!out_on_device) {
-    if (use_pin) {  // E and F are adjacent in the work buffer: one copy
+    if (use_pin) {  // E and F (and W) are adjacent in the work buffer: one copy
       double* h_out = ctx->h_pin + B * 3 * N;
-      HIP_CHECK(ctx, hipMemcpyAsync(h_out, d_E, (B + B * 3 * N) * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(ctx, hipMemcpyAsync(h_out, d_E, (B + B * 3 * N + (W_out ? B * 9 : 0)) * 8, hipMemcpyDeviceToHost, ctx->stream));
       HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
       if (E_out) memcpy(E_out, h_out, B * 8);
-      memcpy(F_out, h_out + B, B * 3 * N * 8);
+      if (F_out) memcpy(F_out, h_out + B, B * 3 * N * 8);
+      if (W_out) memcpy(W_out, h_out + B + B * 3 * N, B * 9 * 8);
     } else {
       if (E_out) HIP_CHECK(ctx, hipMemcpyAsync(E_out, d_E, B * 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_CHECK(ctx, hipMemcpyAsync(F_out, d_F, B * 3 * N * 8, hipMemcpyDeviceToHost, ctx->stream));
+      if (F_out) HIP_CHECK(ctx, hipMemcpyAsync(F_out, d_F, B * 3 * N * 8, hipMemcpyDeviceToHost, ctx->stream));
+      if (W_out) HIP_CHECK(ctx, hipMemcpyAsync(W_out, d_W, B * 9 * 8, hipMemcpyDeviceToHost, ctx->stream));
       HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
   }
   return GDML_OK;
+}
+
+extern "C" int gdml_predict_virial(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv,
+                                   double* E_out, double* F_out, double* W_out) {
+  if (!ctx) return GDML_ERR_INVALID;
+  if (!R) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_virial: R is NULL (there is no training-set mode)");
+  if (!W_out) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_virial: W_out is NULL");
+  return predict_common(ctx, R, false, B, lat, lat_inv, E_out, F_out, false, W_out);
+}
+
+extern "C" int gdml_predict_virial_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat,
+                                       const double* lat_inv, double* E_dev, double* F_dev, double* W_dev) {
+  if (!ctx) return GDML_ERR_INVALID;
+  if (!R_dev) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_virial_dev: R_dev is NULL");
+  if (!W_dev) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_virial_dev: W_dev is NULL");
+  return predict_common(ctx, R_dev, true, B, lat, lat_inv, E_dev, F_dev, true, W_dev);
 }
 
 extern "C" int gdml_predict(gdml_ctx* ctx, const double* R, int64_t B, const double* lat,

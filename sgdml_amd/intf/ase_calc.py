@@ -4,6 +4,9 @@ Same constructor arguments, unit handling and `results` dictionary as the refere
 `SGDMLCalculator`; the model stays resident on the GPU and every `calculate` is one
 single-geometry `GDMLPredict.predict` call (~70 us host-to-host for a 21-atom, 1000-point model,
 `profiles/r01_latency_probe.txt`).  ASE is an optional dependency exactly as in the reference.
+
+Beyond the reference: a model with a lattice also returns `stress` (Voigt, eV/Ang^3, ASE's sign), evaluated in the cell of the
+`atoms` object of each call -- NPT dynamics, cell relaxation and equation-of-state scans work (`GDMLPredict.predict_stress`).
 """
 import logging
 
@@ -34,9 +37,18 @@ class SGDMLCalculator(Calculator):
         self.E_to_eV = E_to_eV                  # model energy unit -> eV
         self.Ang_to_R = F_to_eV_Ang / E_to_eV   # Angstrom -> model length unit
         self.F_to_eV_Ang = F_to_eV_Ang          # model force unit -> eV/Ang
+        self.periodic = self.gdml_predict.lat_and_inv is not None
+        if self.periodic:
+            self.implemented_properties = ['energy', 'forces', 'stress']
 
     def calculate(self, atoms=None, *args, **kwargs):
         super().calculate(atoms, *args, **kwargs)
         r = np.array(atoms.get_positions()) * self.Ang_to_R
-        e, f = self.gdml_predict.predict(r.ravel())
+        if self.periodic:  # the cell of THIS call (ASE: vectors in rows; the model: in columns), one launch like predict()
+            lattice = np.array(atoms.cell).T * self.Ang_to_R
+            e, f, s = self.gdml_predict.predict_stress(r.ravel(), lattice=lattice, voigt=True)
+        else:
+            e, f = self.gdml_predict.predict(r.ravel())
         self.results = {'energy': e * self.E_to_eV, 'forces': (f * self.F_to_eV_Ang).reshape(-1, 3)}
+        if self.periodic:
+            self.results['stress'] = s[0] * (self.E_to_eV * self.Ang_to_R**3)

@@ -80,6 +80,34 @@ def ascend(fun, x0, max_iter=20, gtol=1e-3, bounds=None, max_step=1.0):
     return x, trace
 
 
+def _cofactors3(lat):
+    """Transposed cofactors (adjugate, row-major) and determinant of a 3 x 3 array, on Python floats: a per-call lattice sits
+    in the single-geometry latency path, where numpy.linalg.inv / det / matrix_rank cost half of the whole call."""
+    (a, b, c), (d, e, f), (g, h, i) = lat.tolist()
+    adj = (e * i - f * h, c * h - b * i, b * f - c * e,
+           f * g - d * i, a * i - c * g, c * d - a * f,
+           d * h - e * g, b * g - a * h, a * e - b * d)
+    return adj, a * adj[0] + b * adj[3] + c * adj[6], max(abs(v) for v in (a, b, c, d, e, f, g, h, i))
+
+
+def det3(lat):
+    """Determinant of a 3 x 3 array."""
+    return _cofactors3(lat)[1]
+
+
+def check_lattice(lattice):
+    """(lattice, inverse) as float64 for a per-call lattice: 3 x 3, cell vectors in the COLUMNS (the reference's convention,
+    desc.py:44-77); ValueError for any other shape, non-finite entries or a singular matrix (|det| at most 1e-12 of the cube
+    of the largest entry).  The inverse is adjugate / det (it only feeds the rounding to the minimum image)."""
+    lat = np.array(lattice, dtype=np.float64)
+    if lat.shape != (3, 3):
+        raise ValueError('lattice must be a 3 x 3 matrix (cell vectors in its columns), got shape {}'.format(lat.shape))
+    adj, det, big = _cofactors3(lat)
+    if not (big < float('inf') and abs(det) > 1e-12 * big ** 3):  # (a NaN fails both comparisons)
+        raise ValueError('lattice is singular or not finite')
+    return lat, np.array(adj, dtype=np.float64).reshape(3, 3) / det
+
+
 class GDMLPredict(object):
     def __init__(
         self,
@@ -286,16 +314,26 @@ class GDMLPredict(object):
 
     # ---- prediction
 
-    def predict_hessian(self, R):
+    def _lat_and_inv(self, lattice):
+        """The lattice of one call: the model's (or none) by default, else the validated per-call one."""
+        if lattice is None:
+            return self.lat_and_inv
+        lat_and_inv = check_lattice(lattice)
+        if self.lat_and_inv is not None and np.array_equal(lat_and_inv[0], self.lat_and_inv[0]):
+            return self.lat_and_inv  # the model's own cell: its stored inverse, hence the bits of the default
+        return lat_and_inv
+
+    def predict_hessian(self, R, lattice=None):
         """Energies (B,), forces (B,3N) and analytic Hessians d^2E/dR^2 (B,3N,3N) for geometries R (B,3N) or (3N,),
-        scaled like predict() (E std + c, F std, H std).  No training-set mode: R is required."""
+        scaled like predict() (E std + c, F std, H std).  No training-set mode: R is required.  lattice: as in predict()."""
         if R is None:
             raise ValueError('predict_hessian needs geometries R (there is no training-set mode)')
         R = np.asarray(R, dtype=np.float64)
         if R.ndim == 1:
             R = R[None, :]
         R = R.reshape(R.shape[0], -1)
-        parts = self._sharded(R.shape[0], lambda ctx, lo, hi: ctx.predict_hessian(R[lo:hi], self.lat_and_inv),
+        lat_and_inv = self._lat_and_inv(lattice)
+        parts = self._sharded(R.shape[0], lambda ctx, lo, hi: ctx.predict_hessian(R[lo:hi], lat_and_inv),
                               min_shard=self._min_shard_hessian)
         E, F, H = (parts[0] if len(parts) == 1 else [np.concatenate([p_[i] for p_ in parts]) for i in range(3)])
         E *= self.std
@@ -303,6 +341,43 @@ class GDMLPredict(object):
         F *= self.std
         H *= self.std
         return E, F, H
+
+    # ---- strain derivative and stress (gdml_predict_virial, csrc/predict.hip)
+
+    def predict_virial(self, R, lattice=None):
+        """Energies (B,), forces (B,3N) and the strain derivative W = dE/d eps (B,3,3) for geometries R (B,3N) or (3N,): the
+        change of the energy when atoms and cell are strained together, r -> (I + eps) r, lattice -> (I + eps) lattice.  E and
+        F are those of predict(R, lattice=lattice), bit for bit; W is symmetric and scaled by std like F.  Works for
+        non-periodic models too (W = -sum_i f_i (x) r_i there).  lattice: as in predict().  No training-set mode."""
+        return self._virial(R, self._lat_and_inv(lattice))
+
+    def _virial(self, R, lat_and_inv):
+        if R is None:
+            raise ValueError('predict_virial needs geometries R (there is no training-set mode)')
+        R = np.asarray(R, dtype=np.float64)
+        if R.ndim == 1:
+            R = R[None, :]
+        R = R.reshape(R.shape[0], -1)
+        parts = self._sharded(R.shape[0], lambda ctx, lo, hi: ctx.predict_virial(R[lo:hi], lat_and_inv))
+        E, F, W = (parts[0] if len(parts) == 1 else [np.concatenate([p_[i] for p_ in parts]) for i in range(3)])
+        E *= self.std
+        E += self.c
+        F *= self.std
+        W *= self.std
+        return E, F, W
+
+    def predict_stress(self, R, lattice=None, voigt=False):
+        """(E, F, S) with the stress S = W / |det lattice| (B,3,3) of predict_virial: +dE/d eps per volume, ASE's sign, in the
+        model's energy unit per length unit cubed.  voigt=True: S (B,6) in ASE's order xx, yy, zz, yz, xz, xy.  ValueError when
+        neither the model nor the call supplies a lattice (a volume)."""
+        lat_and_inv = self._lat_and_inv(lattice)
+        if lat_and_inv is None:
+            raise ValueError('predict_stress needs a lattice: the model has none and none was given')
+        E, F, W = self._virial(R, lat_and_inv)
+        W /= abs(det3(lat_and_inv[0]))
+        if voigt:
+            W = np.ascontiguousarray(W.reshape(-1, 9)[:, [0, 4, 8, 5, 2, 1]])
+        return E, F, W
 
     # ---- posterior force covariance (csrc/uncert.hip)
 
@@ -837,17 +912,22 @@ class GDMLPredict(object):
                 m['e_err'] = {'mae': np.nan, 'rmse': np.nan}
         return m
 
-    def predict(self, R=None, return_E=True):
-        """Energies (B,) and forces (B,3N) for geometries R (B,3N); R=None -> training-set mode."""
+    def predict(self, R=None, return_E=True, lattice=None):
+        """Energies (B,) and forces (B,3N) for geometries R (B,3N); R=None -> training-set mode.
+        lattice: a 3 x 3 matrix with the cell vectors in its columns, used for THIS call instead of the model's (one lattice
+        per call; ValueError unless 3 x 3 and regular).  None: the model's lattice, or none."""
         if R is not None:
             R = np.asarray(R, dtype=np.float64)
             if R.ndim == 1:
                 R = R[None, :]
             R = R.reshape(R.shape[0], -1)
-            parts = self._sharded(R.shape[0], lambda ctx, lo, hi: ctx.predict(R[lo:hi], self.lat_and_inv, return_E=return_E))
+            lat_and_inv = self._lat_and_inv(lattice)
+            parts = self._sharded(R.shape[0], lambda ctx, lo, hi: ctx.predict(R[lo:hi], lat_and_inv, return_E=return_E))
             F = parts[0][1] if len(parts) == 1 else np.concatenate([p_[1] for p_ in parts])
             E = None if not return_E else (parts[0][0] if len(parts) == 1 else np.concatenate([p_[0] for p_ in parts]))
         else:
+            if lattice is not None:
+                raise ValueError('a per-call lattice needs geometries R (the training-set mode uses cached descriptors)')
             if self.R_desc is None or self.R_d_desc is None:
                 self.log.critical(
                     'A reference to the training geometry descriptors and Jacobians needs to be set '
