@@ -136,6 +136,8 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *   chol.outer (1024)     panel pairs: K = 2 nb trailing update in two launches (= chol.nb, or chol.nb not a multiple of 128:
  *                         single panels only)
  *   chol.outer_min_rows (16384)  trailing rows below which new panels are single again
+ *   gemm.balance (1)      lower (SYRK-shaped) trailing updates: tile list dealt evenly over the 8 XCDs, no empty workgroups
+ *                         (csrc/tile_sched.h); 0: the 8 x 8 super-tile enumeration with 64 block slots per super tile.  Same factor bit for bit
  *   trsm.debug (0)        timing-only ablation mask of the row-local panel solve (results are wrong when set)
  *   trsv.persist (1)      backward substitution as one persistent launch
  *   predict.wave_only (0), predict.mfma (1), predict.mfma_wide (1), predict.fill   prediction kernel choice

@@ -21,6 +21,8 @@
 // CU-masked / split-stream / chunked variants of rounds 1-2 (profiles/r01_chol_timeline_split.txt, r02_sched_probe.txt) and the
 // two-level, persistent and narrow-tile forms of round 6 were measured slower and are gone.
 #include "common.h"
+#include "tile_sched.h"
+#include <array>
 #include <type_traits>
 #include <utility>
 
@@ -74,6 +76,10 @@ struct GemmArgs {
   double* C2;
   int64_t M2, N2, K2;
   int tiles2;
+  int second_compact;  // its tiles2 workgroups all hold a tile (tile_decode_second)
+  // balanced tile list of a lower launch (tile_sched.h, option gemm.balance); 0: the super-tile enumeration
+  int bal;
+  TileLaunch tl;
 };
 
 __global__ void __launch_bounds__(256, 2) gemm_nt_sub_diag_kernel(GemmArgs g);
@@ -303,13 +309,18 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, double (*lds)[
   }
 }
 
-// block index -> tile (XCD-aware 8x8 super tiles: block b runs on XCD b % 8) and the tile's GEMM
+// block index -> tile (tile_sched.h: XCD-aware 8x8 super tiles, block b runs on XCD b % 8) and the tile's GEMM
 template <bool OW>
 __device__ __forceinline__ void gemm_block(const GemmArgs& g, double (*lds)[2][GT * GPITCH], int64_t b) {
   if (b < g.tiles2) {  // second problem (workgroup-uniform branch)
     const int tn2 = (int)((g.N2 + GT - 1) / GT);
-    const int64_t ti = b / tn2, tj = b - ti * tn2;
-    if (ti < tn2 && tj > ti) return;
+    int64_t ti, tj;
+    if (g.second_compact) {
+      tile_decode_second(b, tn2, &ti, &tj);
+    } else {
+      ti = b / tn2; tj = b - ti * tn2;
+      if (ti < tn2 && tj > ti) return;
+    }
     GemmArgs h = g;
     h.A = g.A2; h.B = g.B2; h.C = g.C2; h.M = g.M2; h.N = g.N2; h.K = g.K2;
     h.aligned = ((reinterpret_cast<uintptr_t>(g.A2) | reinterpret_cast<uintptr_t>(g.B2)) & 15) == 0 && g.aligned;
@@ -327,33 +338,12 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& g, double (*lds)[2][G
     return;
   }
   b -= g.tiles2;
-  const int64_t xcd = b & 7, loc = b >> 3;
-  const int64_t s = g.s_begin + (loc >> 6) * 8 + xcd;
-  const int within = (int)(loc & 63);
-  if (s >= g.n_super) return;
-  int64_t SI, SJ;
-  if (g.lower) {
-    int64_t sr = s, shift = 0;
-    const int64_t sm = (g.tiles_m + 7) / 8;
-    if (g.col0_first) {  // column SJ = 0 (all SI) first, then the lower triangle of the remaining sm - 1 super rows
-      if (s < sm) { SI = s; SJ = 0; sr = -1; }
-      else { sr = s - sm; shift = 1; }
-    }
-    if (sr >= 0) {
-      // sr = SI (SI+1)/2 + SJ
-      SI = (int64_t)((sqrt(8.0 * (double)sr + 1.0) - 1.0) * 0.5);
-      while (SI * (SI + 1) / 2 > sr) --SI;
-      while ((SI + 1) * (SI + 2) / 2 <= sr) ++SI;
-      SJ = sr - SI * (SI + 1) / 2;
-      SI += shift; SJ += shift;
-    }
-  } else {
-    SI = s / g.super_n;
-    SJ = s - SI * g.super_n;
+  int64_t ti, tj;
+  if (g.bal) {
+    if (!tile_decode_bal(g.tl, b, &ti, &tj)) return;
+  } else if (!tile_decode_super(b, g.lower, g.col0_first, g.tiles_m, g.tiles_n, g.super_n, g.s_begin, g.n_super, &ti, &tj)) {
+    return;
   }
-  const int64_t ti = SI * 8 + (within >> 3), tj = SJ * 8 + (within & 7);
-  if (ti >= g.tiles_m || tj >= g.tiles_n) return;
-  if (g.lower && tj > ti) return;
   const int64_t row0 = ti * GT, col0 = tj * GT;
   if (g.cyc_W > 0 && row0 + GT <= g.cyc_block_rows) {  // tiles that reach into the carried rhs row take all columns
     const int64_t gb = (g.cyc_lb0 + row0 / g.cyc_nb) * g.cyc_W + g.cyc_rank;  // (tiles never straddle blocks: nb % GT == 0)
@@ -400,7 +390,80 @@ struct DiagJob {
   const double* B2 = nullptr;
   double* C2 = nullptr;
   int64_t M2 = 0, N2 = 0, K2 = 0;
+  // first launch of a list cut in two: the second problem that the list's last launch will carry (its blocks are other
+  // work on their XCDs when the tile list is dealt)
+  int64_t next_M2 = 0, next_N2 = 0, next_K2 = 0;
 };
+
+// ---- balanced tile lists (tile_sched.h), cached per context --------------------------------------------------------
+// One entry per (tiles_m, tiles_n, first-column-first, launches, second problem): built on first use, its tables uploaded
+// once into one device block; a sigma sweep or repeated training at one size builds nothing and copies nothing.
+struct TileSchedEntry {
+  TileSched S;
+  const uint32_t* dev[2] = {nullptr, nullptr};
+};
+struct TileSchedCache {
+  std::map<std::array<int64_t, 7>, TileSchedEntry> entries;
+  char* block = nullptr;
+  size_t cap = 0, used = 0;
+};
+
+void tile_sched_cache_free(gdml_ctx* ctx) {
+  if (!ctx->tile_sched) return;
+  if (ctx->tile_sched->block) hipFree(ctx->tile_sched->block);
+  delete ctx->tile_sched;
+  ctx->tile_sched = nullptr;
+}
+
+static int second_blocks(int64_t M2, int64_t N2, bool* compact) {
+  const int64_t tm2 = ceil_div(M2, GT), tn2 = ceil_div(N2, GT);
+  *compact = tm2 >= tn2;
+  return (int)(tm2 * tn2 - (*compact ? tn2 * (tn2 - 1) / 2 : 0));
+}
+
+// *out = null: no balanced form for this shape (the caller keeps the super-tile enumeration)
+static int tile_sched_get(gdml_ctx* ctx, hipStream_t st, int tiles_m, int tiles_n, bool col0_first, int n_launch, int lead2,
+                          int64_t K2, int64_t K, const TileSchedEntry** out) {
+  *out = nullptr;
+  if (!ctx->tile_sched) ctx->tile_sched = new TileSchedCache();
+  TileSchedCache* c = ctx->tile_sched;
+  const std::array<int64_t, 7> key = {tiles_m, tiles_n, col0_first ? 1 : 0, n_launch, lead2, lead2 ? K2 : 0, lead2 ? K : 0};
+  auto it = c->entries.find(key);
+  if (it == c->entries.end()) {
+    TileSchedEntry e;
+    // the second problem's block q sits lead2 - q blocks in front of the list's block 0: XCD label (q - lead2) mod 8
+    double base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int q = 0; q < lead2; ++q) base[((q - lead2) % 8 + 8) % 8] += (double)K2 / (double)K;
+    tile_sched_build(tiles_m, tiles_n, col0_first, n_launch, base, &e.S);
+    if (e.S.ok) {
+      const size_t b0 = (e.S.table[0].size() * 4 + 255) & ~(size_t)255, b1 = (e.S.table[1].size() * 4 + 255) & ~(size_t)255;
+      const size_t block_bytes = (size_t)8 << 20;
+      if (!c->block) {
+        HIP_CHECK(ctx, hipMalloc((void**)&c->block, block_bytes));
+        c->cap = block_bytes;
+      }
+      if (b0 + b1 > c->cap) {
+        e.S.ok = false;
+      } else {
+        if (c->used + b0 + b1 > c->cap) {  // full: nothing in flight may still read the old tables
+          HIP_CHECK(ctx, hipDeviceSynchronize());
+          c->entries.clear();
+          c->used = 0;
+        }
+        char* d = c->block + c->used;
+        c->used += b0 + b1;
+        if (!e.S.table[0].empty()) HIP_CHECK(ctx, hipMemcpyAsync(d, e.S.table[0].data(), e.S.table[0].size() * 4, hipMemcpyHostToDevice, st));
+        if (!e.S.table[1].empty()) HIP_CHECK(ctx, hipMemcpyAsync(d + b0, e.S.table[1].data(), e.S.table[1].size() * 4, hipMemcpyHostToDevice, st));
+        HIP_CHECK(ctx, hipStreamSynchronize(st));  // once per entry: any stream may use it from here on
+        e.dev[0] = reinterpret_cast<const uint32_t*>(d);
+        e.dev[1] = reinterpret_cast<const uint32_t*>(d + b0);
+      }
+    }
+    it = c->entries.emplace(key, std::move(e)).first;
+  }
+  if (it->second.S.ok) *out = &it->second;
+  return GDML_OK;
+}
 
 static int launch_gemm_nt_sub_part(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda,
                                    const double* B, int64_t ldb, double* C, int64_t ldc, int64_t M,
@@ -414,7 +477,8 @@ static int launch_gemm_nt_sub_part(gdml_ctx* ctx, hipStream_t st, const double* 
   g.cyc_W = 0; g.cyc_rank = 0; g.cyc_lb0 = 0; g.cyc_nb = 0; g.cyc_col0 = 0; g.cyc_block_rows = 0;
   g.col0_first = (diag && diag->col0_first) ? 1 : 0;
   g.ready = nullptr; g.ready_target = 0; g.ready_rows = 0;
-  g.A2 = g.B2 = nullptr; g.C2 = nullptr; g.M2 = g.N2 = g.K2 = 0; g.tiles2 = 0;
+  g.A2 = g.B2 = nullptr; g.C2 = nullptr; g.M2 = g.N2 = g.K2 = 0; g.tiles2 = 0; g.second_compact = 0;
+  g.bal = 0; g.tl = TileLaunch();
   if (cyc) { g.cyc_W = cyc->W; g.cyc_rank = cyc->rank; g.cyc_lb0 = cyc->lb0; g.cyc_nb = cyc->nb; g.cyc_col0 = cyc->col0; g.cyc_block_rows = cyc->block_rows; }
   g.aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 &&
               (lda % 2 == 0) && (ldb % 2 == 0);
@@ -426,19 +490,47 @@ static int launch_gemm_nt_sub_part(gdml_ctx* ctx, hipStream_t st, const double* 
   g.s_begin = (int64_t)(f0 * (double)n_super_all);
   g.n_super = (f1 >= 1.0) ? n_super_all : (int64_t)(f1 * (double)n_super_all);
   const bool has_diag = diag && diag->A;
-  if (g.n_super <= g.s_begin) {
-    if (!has_diag) return GDML_OK;
-    g.n_super = g.s_begin;  // empty tile range: the launch still carries the diagonal-block workgroup
+  const bool second = has_diag && diag->A2 && diag->M2 > 0;
+  // lower, non-cyclic launches: the balanced tile list (gemm.balance, default 1); (f0, f1) then only say which launch
+  // of the list this is -- (0, 1) the only one, (0, f) the first of two, (f, 1) the second
+  const TileSchedEntry* te = nullptr;
+  const int tl_i = f0 > 0.0 ? 1 : 0;
+  if (lower && !cyc && !overwrite && ctx_opt(ctx, "gemm.balance", 1) != 0) {
+    const int64_t M2s = second ? diag->M2 : (diag ? diag->next_M2 : 0), N2s = second ? diag->N2 : (diag ? diag->next_N2 : 0);
+    const int64_t K2s = second ? diag->K2 : (diag ? diag->next_K2 : 0);
+    bool compact = false;
+    const int lead2 = (M2s > 0 && N2s > 0) ? second_blocks(M2s, N2s, &compact) : 0;
+    GDML_TRY(tile_sched_get(ctx, st, g.tiles_m, g.tiles_n, g.col0_first != 0, (f0 > 0.0 || f1 < 1.0) ? 2 : 1, compact ? lead2 : 0,
+                            K2s, K, &te));
   }
-  int64_t groups = (g.n_super - g.s_begin + 7) / 8;  // each group of 8 super tiles = 8 XCDs x 64 blocks
-  int64_t blocks = groups * 512;
+  int64_t blocks;
+  if (te) {
+    g.bal = 1;
+    g.tl = te->S.L[tl_i];
+    g.tl.table = te->dev[tl_i];
+    g.s_begin = g.n_super = 0;
+    blocks = te->S.blocks[tl_i];
+    if (blocks == 0 && !has_diag) return GDML_OK;
+  } else {
+    if (g.n_super <= g.s_begin) {
+      if (!has_diag) return GDML_OK;
+      g.n_super = g.s_begin;  // empty tile range: the launch still carries the diagonal-block workgroup
+    }
+    const int64_t groups = (g.n_super - g.s_begin + 7) / 8;  // each group of 8 super tiles = 8 XCDs x 64 blocks
+    blocks = groups * 512;
+  }
   const int slot = (timed && st == (ctx->kt_stream ? ctx->kt_stream : ctx->stream)) ? ktime_begin(ctx) : -1;
   if (has_diag) {
     g.diagA = diag->A; g.diag_nbw = diag->nbw; g.diag_off = diag->off; g.diag_info = ctx->d_info;
     if (diag->ready) { g.ready = diag->ready; g.ready_target = diag->ready_target; g.ready_rows = diag->nbw * 64 / GT; }
-    if (diag->A2 && diag->M2 > 0) {
+    if (second) {
       g.A2 = diag->A2; g.B2 = diag->B2; g.C2 = diag->C2; g.M2 = diag->M2; g.N2 = diag->N2; g.K2 = diag->K2;
       g.tiles2 = (int)(ceil_div(g.M2, GT) * ceil_div(g.N2, GT));
+      if (te) {  // no empty workgroups in front of a balanced list either
+        bool compact = false;
+        const int lead2 = second_blocks(g.M2, g.N2, &compact);
+        if (compact) { g.tiles2 = lead2; g.second_compact = 1; }
+      }
     }
     hipLaunchKernelGGL(gemm_nt_sub_diag_kernel, dim3((unsigned)(blocks + 1 + g.tiles2)), dim3(256), 0, st, g);
   } else if (overwrite)
@@ -446,10 +538,11 @@ static int launch_gemm_nt_sub_part(gdml_ctx* ctx, hipStream_t st, const double* 
   else
     hipLaunchKernelGGL(gemm_nt_sub_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g);
   const double part = (double)(g.n_super - g.s_begin) / (double)n_super_all;  // share of the tile list in this launch
+  // algorithmic flops: a balanced list counts the tiles the launch really holds, the super-tile enumeration its share of the list
+  const double flops = te ? tile_sched_flops(te->S, tl_i, M, K, g.tiles_m, GT)
+                          : part * (lower ? (double)M * (double)(M + 1) * (double)K : 2.0 * (double)M * (double)N * (double)K);
   // the fused launches (trailing update + diagonal-block workgroup) are the dominant kernel: timed under their own name
-  ktime_end(ctx, slot, has_diag ? "gemm_nt_sub_diag" : "gemm_nt_sub",
-            part * (lower ? (double)M * (double)(M + 1) * (double)K : 2.0 * (double)M * (double)N * (double)K) +
-                2.0 * (double)g.M2 * (double)g.N2 * (double)g.K2);
+  ktime_end(ctx, slot, has_diag ? "gemm_nt_sub_diag" : "gemm_nt_sub", flops + 2.0 * (double)g.M2 * (double)g.N2 * (double)g.K2);
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
   return GDML_OK;
@@ -1385,6 +1478,7 @@ int chol_factor_device(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int* inf
       const int block_tiles = (int)((NB / GT) * (NB / GT + 1) / 2);  // lower GT x GT tiles of a diagonal block
       ready_count += block_tiles;
       dj.ready_target = ready_count;
+      dj.next_M2 = n_rows - ta; dj.next_N2 = NB; dj.next_K2 = NB;
       GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, 0.0, fs, true,
                                        &dj));
       double* Xa = A + ta * ld + t0;  // rows below block a (they include b's rows of the outer panel)

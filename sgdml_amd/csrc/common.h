@@ -104,6 +104,8 @@ enum CtxSlot {
   SLOT_COUNT
 };
 
+struct TileSchedCache;  // balanced tile lists of the lower trailing updates and their device tables (chol.hip)
+
 struct gdml_ctx {
   int device = 0;
   int num_cus = 256;  // compute units of the device (grid sizing)
@@ -178,6 +180,7 @@ struct gdml_ctx {
   double* slot[SLOT_COUNT] = {};  // cached work buffers (ctx_slot, CtxSlot)
   int64_t slot_bytes[SLOT_COUNT] = {};
   int* d_info = nullptr;
+  TileSchedCache* tile_sched = nullptr;
 
   // comm
   void* comm = nullptr;  // ncclComm_t
@@ -291,6 +294,7 @@ int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int6
 int chol_bwd_device(gdml_ctx* ctx, const double* L, int64_t n, int64_t ld, double* d_z, double* d_x);
 // X[:, 0:m] <- X L^-T for the n rows of X (cg.hip).  look: 1 left-looking, 0 right-looking, -1 = option nys.trsm_left
 int tall_trsm(gdml_ctx* ctx, const double* L, double* X, int64_t n, int64_t m, int64_t ld, int look = -1);
+void tile_sched_cache_free(gdml_ctx* ctx);
 int ctx_slot(gdml_ctx* ctx, int slot, int64_t bytes, double** out);
 int ctx_slot_release(gdml_ctx* ctx, int slot);
 // ---- block Gram of tall row blocks (block_gram.hip; uncert.hip, loo.hip)
