@@ -10,13 +10,13 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 GramSplit gram_split(int64_t n, int n3) {
   GramSplit g;
   g.n = n; g.n3 = n3;
-  g.ld = (n + 15) / 16 * 16;
+  g.ld = round16(n);
   g.nblk = (n3 + 63) / 64;
   g.npairs = g.nblk * (g.nblk + 1) / 2;
   g.S = (int)((n + 1023) / 1024);
   if (g.S > 32) g.S = 32;
   if (g.S < 1) g.S = 1;
-  g.L = ((g.ld + g.S - 1) / g.S + 15) / 16 * 16;
+  g.L = round16((g.ld + g.S - 1) / g.S);
   g.S = (int)((g.ld + g.L - 1) / g.L);  // no empty split
   return g;
 }

@@ -81,10 +81,11 @@ struct Model {
 //   SLOT_PRECON_GEMV  the fp32 form (precon_form 3) and the fp64 form are two branches of precon_apply_device
 //   SLOT_PRECON_MF    build_f32_form reads its flag back and synchronises before it goes on, and applies no preconditioner;
 //                     precon_apply_mf calls matvec_device, which requests other slots only
-//   SLOT_GRAM_WS/ROWS gdml_uncert_cross, gdml_predict_cov, gdml_predict_cov_few, gdml_loo and gdml_select_points each carve them anew
-//                     (gram_workspace) and call none of the others while they hold them (gdml_predict_cov_few hands a batch beyond
-//                     its limit to gdml_predict_cov BEFORE it carves anything; its inverted diagonal blocks are the fixed part of
-//                     SLOT_GRAM_WS and live for one call); tall_trsm in between requests SLOT_PANEL_TRSM only
+//   SLOT_GRAM_WS/ROWS every caller of gram_workspace (gdml_uncert_cross, cov_run for the four gdml_predict_cov* entries, gdml_loo,
+//                     gdml_evidence_grad, gdml_select_points) carves them anew and calls none of the others while it holds them
+//                     (gdml_predict_cov_few hands a batch beyond its limit to gdml_predict_cov BEFORE it carves anything; its
+//                     inverted diagonal blocks are the fixed part of SLOT_GRAM_WS and live for one call); tall_trsm in between
+//                     requests SLOT_PANEL_TRSM only.  gdml_factor_extend / gdml_factor_remove release both: they were sized for n
 enum CtxSlot {
   SLOT_PREDICT_WS = 0,      // row-split partials of F_x and E (predict_device, predict_fused); workspace of hess_device
   SLOT_MATVEC_OUT = 1,      // forces and energies of this rank's query points (matvec_device)
@@ -99,8 +100,8 @@ enum CtxSlot {
   SLOT_PRECON_MF = 10,      // vectors of the matrix-free preconditioner (precon_apply_mf); "fits on every rank" flag (build_f32_form)
   SLOT_F32_GRAM_ROWS = 11,  // widened row chunk of the rounded factor (build_f32_form)
   SLOT_MATVEC_VREF = 12,    // coefficients back in the reference order (matvec_device, sharded with energy constraints)
-  SLOT_GRAM_WS = 13,        // queries / coefficients, partial Gram tiles, staged output (gram_workspace: uncert.hip, loo.hip, select.hip)
-  SLOT_GRAM_ROWS = 14,      // the (3N x chunk, padded to 128 rows) x K_ld row buffer (gram_workspace: uncert.hip, loo.hip, select.hip)
+  SLOT_GRAM_WS = 13,        // queries / coefficients, partial Gram tiles, staged output (gram_workspace)
+  SLOT_GRAM_ROWS = 14,      // the (3N x chunk, padded to 128 rows) x K_ld row buffer (gram_workspace)
   SLOT_COUNT
 };
 
@@ -229,6 +230,21 @@ static inline int ctx_opt_i(const gdml_ctx* ctx, const char* key, int dflt) { re
     if (rc__ != GDML_OK) return rc__; \
   } while (0)
 
+// The same two for a function that owns buffers until it commits: they leave through a local callable `drop(rc)`, which
+// frees what the call allocated and returns rc (gdml_select_points, gdml_factor_extend, gdml_factor_remove).
+#define DROP_TRY(expr)                      \
+  do {                                      \
+    const int rc_e = (expr);                \
+    if (rc_e != GDML_OK) return drop(rc_e); \
+  } while (0)
+#define DROP_HIP(call)                                                                                              \
+  do {                                                                                                              \
+    const hipError_t e_e = (call);                                                                                  \
+    if (e_e != hipSuccess)                                                                                          \
+      return drop(gdml_fail(ctx, e_e == hipErrorOutOfMemory ? GDML_ERR_OOM : GDML_ERR_HIP, "%s failed: %s (%s:%d)", \
+                            #call, hipGetErrorString(e_e), __FILE__, __LINE__));                                    \
+  } while (0)
+
 // context-tracked allocation helpers (ctx.hip)
 int ctx_alloc(gdml_ctx* ctx, void** p, int64_t bytes);
 int ctx_free(gdml_ctx* ctx, void* p);
@@ -244,6 +260,7 @@ int ktime_collect(gdml_ctx* ctx);
 int phase_end(gdml_ctx* ctx, const char* name);
 
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+static inline int64_t round16(int64_t v) { return (v + 15) / 16 * 16; }  // pitches: rows start on 128-byte boundaries
 
 // ---- device helpers -----------------------------------------------------------------
 // index of the descriptor entry for the unordered atom pair {a,b}, a != b
@@ -297,12 +314,33 @@ int tall_trsm(gdml_ctx* ctx, const double* L, double* X, int64_t n, int64_t m, i
 void tile_sched_cache_free(gdml_ctx* ctx);
 int ctx_slot(gdml_ctx* ctx, int slot, int64_t bytes, double** out);
 int ctx_slot_release(gdml_ctx* ctx, int slot);
-// ---- block Gram of tall row blocks (block_gram.hip; uncert.hip, loo.hip)
+// ---- the resident Cholesky factor and what is computed from it ---------------------------------------------------------------
+// the k-split plan of a block Gram over n columns (block_gram.hip); also the shape a resident factor of n rows must have
 struct GramSplit {
   int n3, nblk, npairs, S;  // rows of an item, its 64-row blocks and lower block pairs, k splits
   int64_t n, ld, L;         // columns, pitch (n rounded up to 16), split length
 };
 GramSplit gram_split(int64_t n, int n3);
+// The contract of the entries that work on the factor in ctx->K, checked in this order: a training set is
+// resident (GDML_ERR_STATE), the factor carries no energy-constraint rows (GDML_ERR_UNSUPPORTED), a factor is resident --
+// need_prepared: the one gdml_uncert_prepare built -- (GDML_ERR_STATE), and it is the square, unsharded 3N M x 3N M factor of
+// the resident training set at pitch round16(3N M) (GDML_ERR_STATE).  Fills g_out from gram_split.  Nothing is allocated and
+// nothing is launched.  The rank test of a caller that has one stays in front of it.  (resident.hip)
+int resident_factor_check(gdml_ctx* ctx, const char* who, bool need_prepared, GramSplit* g_out);
+// Rows 3N j0 .. 3N (j0 + bc) - 1 of L^-T into `rows` (pitch g.ld): zeroed and seeded with E^T from column c0 = the first row
+// index rounded down to the 512-column panel grid of tall_trsm, then solved on the trailing sub-problem from c0, right-looking,
+// on whole 128-row tiles (columns left of c0 are neither written nor read).  The two steps are timed as t_seed / t_solve;
+// with `keep` the true rows (not the pad rows) are also copied to their place in that n x g.ld matrix, inside t_solve.
+int factor_inverse_rows(gdml_ctx* ctx, const GramSplit& g, double* rows, int64_t j0, int64_t bc, const char* t_seed,
+                        const char* t_solve, double* keep = nullptr);
+// log det A = 2 sum log L_ii: a strided gather into d_diag (g.n doubles) and a host sum in index order
+int factor_logdet(gdml_ctx* ctx, const GramSplit& g, double* d_diag, double* logdet_out);
+// The commit of gdml_factor_extend / gdml_factor_remove: Kn (n1 rows, pitch ld1) replaces the resident factor and x1, g1 (M1
+// points) the descriptor tables; the tables derived from the old training set are freed (an assembly builds them again).
+// The stream is idle and every pointer is tracked: nothing here fails half way.
+void factor_commit(gdml_ctx* ctx, double* Kn, int64_t Kn_bytes, int64_t n1, int64_t ld1, double* x1, double* g1, int64_t M1);
+
+// ---- block Gram of tall row blocks (block_gram.hip), the chunking of such blocks and the posterior-covariance chunk (uncert.hip)
 // The solve runs on whole 128-row tiles (zero rows behind the last item): an interior tile of the trailing update and an
 // edge tile round differently (chol.hip: acc = -C first vs C - acc last), and which of the two an item's rows meet must not
 // depend on how the items were cut into chunks.
@@ -322,6 +360,31 @@ int cross_rows_launch(gdml_ctx* ctx, const double* xt, const double* gt, int64_t
 // out = sym(-k_qq) - sum_s partial_s of `items` row blocks whose partial tiles block_gram_launch wrote (uncert.hip; select.hip)
 void cov_reduce_launch(gdml_ctx* ctx, const GramSplit& g, const double* part, const double* nkqq, double* out, int64_t items,
                        int full);
+// Sig_q = (-k_qq) - Z_q Z_q^T, Z_q = (-Kx_q) L^-T for a chunk of queries (uncert.hip; uncert_few.hip, select.hip).
+// CovChunk: the per-chunk work buffers, R | xq | gq | nkqq | out | part, cov_chunk_doubles per query (part only with gram).
+// cov_chunk_carve lays them out from ws for chunks of at most bc queries and returns the first double behind them.
+struct CovChunk {
+  double *R, *xq, *gq, *nkqq, *out, *part;
+};
+int64_t cov_chunk_doubles(const GramSplit& g, int64_t D, bool gram);
+double* cov_chunk_carve(CovChunk* c, double* ws, const GramSplit& g, int64_t D, int64_t bc, bool gram);
+// What tells the users of the chunk step apart: the timer names, and the solve.  solve == nullptr: tall_trsm, right-looking, on
+// rows padded to 128, timed as t_solve.  Otherwise solve(ctx, g, rows, rows_pad, work, fixed) on rows padded to row_pad, which
+// times itself; `fixed` is its part of the workspace (ws_fixed doubles in front of the chunk buffers).
+struct CovPath {
+  const char *t_cross, *t_solve, *t_gram, *phase;
+  int row_pad;
+  int (*solve)(gdml_ctx* ctx, const GramSplit& g, double* rows, int64_t rows_pad, double work, double* fixed);
+};
+// One chunk: [upload R] -> descriptors -> cross_rows_launch -> zero the pad rows -> solve -> block_gram_launch ->
+// cov_reduce_launch into d_out ((bc,3N,3N) with full, else (bc,3N), on the device).  R: bc geometries, on the host unless R_on_device.
+int cov_chunk_step(gdml_ctx* ctx, const GramSplit& g, const CovPath& path, const CovChunk& c, double* rows, double* fixed,
+                   const double* R, bool R_on_device, int bc, const double* lat, const double* lat_inv, int full, double* d_out);
+// the argument and state checks of the four gdml_predict_cov* entries, and their chunk loop (carves the Gram slots)
+int cov_check(gdml_ctx* ctx, const char* who, const double* R, int64_t B, const double* lat, const double* lat_inv,
+              const double* cov_out, GramSplit* g_out);
+int cov_run(gdml_ctx* ctx, const GramSplit& g, const CovPath& path, const double* R, bool on_device, int64_t B, const double* lat,
+            const double* lat_inv, int full, double* cov_out, int64_t ws_fixed = 0);
 void shard_points(const gdml_ctx* ctx, int64_t M, int64_t* p0, int64_t* p1, int64_t* pts_per);
 // Layout of the replicated device vectors of the sharded solvers (Nystroem factor rows, PCG vectors, mat-vec in / out).
 //   no communicator (world <= 1): the reference order, n entries, no padding;

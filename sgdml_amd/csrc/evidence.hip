@@ -7,10 +7,10 @@
 // from which the caller forms d lml / d sig = 1/2 (<A^-1, K'> - a^T K' a / s^2), d lml / d lam = 1/2 (a^T a / s^2 - tr A^-1).
 //
 // Three passes, interleaved chunk by chunk over consecutive training points (rows r0 .. r1 of the system):
-//   1. Z = L^-T, KEPT: the chunk's rows are seeded and solved exactly as in loo.hip (trailing sub-problem from c0 = the
-//      chunk's first column rounded down to the 512-column panel grid, right-looking tall_trsm on whole 128-row tiles) in
-//      the chunk row buffer, and the TRUE rows (not the pad rows behind them) are copied into a second n x K_ld buffer that
-//      lives for the call.  Row r of Z is zero left of column r; columns left of c0 are never written and never read.
+//   1. Z = L^-T, KEPT: the chunk's rows are seeded and solved by factor_inverse_rows, the step of loo.hip (trailing sub-problem
+//      from c0 = the chunk's first column rounded down to the 512-column panel grid, right-looking tall_trsm on whole 128-row
+//      tiles) in the chunk row buffer, and the TRUE rows (not the pad rows behind them) are copied into a second n x K_ld
+//      buffer that lives for the call.  Row r of Z is zero left of column r; columns left of c0 are never written and never read.
 //   2. -A^-1[r0:r1, 0:r1] = -Z[r0:r1, c0:] Z[0:r1, c0:]^T: one launch_gemm_nt_neg into the chunk row buffer.  Rows above the
 //      chunk are zero left of their own diagonal, so the product over k >= c0 is exact without a mask.
 //   3. evidence_contract_kernel: every lower pair of points (i in the chunk, j <= i) contracts its 3N x 3N tile of -A^-1 with
@@ -18,17 +18,6 @@
 // No atomics: a partial per pair, a fixed-order sum per row point on the device and a sum over the points in index order on
 // the host.  The sums stay apart down to the host (tr A^-1 is of order 1 / lam where the others are of order 10).
 #include "common.h"
-
-
-__global__ void __launch_bounds__(256) evidence_seed_kernel(double* __restrict__ rows, int64_t ld, int64_t col0, int64_t nrows) {
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r < nrows) rows[r * ld + col0 + r] = 1.0;
-}
-
-__global__ void __launch_bounds__(256) evidence_diag_kernel(const double* __restrict__ Lf, int64_t ld, int64_t n, double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = Lf[i * ld + i];
-}
 
 // ---- contraction ---------------------------------------------------------------------------------------------------------
 // For one pair of points (i, j), one permutation p, d = x_i - P_p x_j, r = sqrt(5) |d|, e = exp(-r / sig) the block of K is
@@ -275,20 +264,11 @@ static int evidence_run(gdml_ctx* ctx, const GramSplit& g, double* Z, const doub
   phase_begin(ctx);
   for (int64_t j0 = 0; j0 < M; j0 += bc_max) {
     const int64_t bc = M - j0 < bc_max ? M - j0 : bc_max;
-    const int64_t nrows = bc * n3, rows_pad = pad_rows128(nrows);
-    const int64_t first = j0 * n3, c0 = first / 512 * 512, r1 = first + nrows;
-    // pass 1: seed and solve in the chunk buffer (loo.hip), then keep the true rows
-    int slot = ktime_begin(ctx);
-    HIP_CHECK(ctx, hipMemset2DAsync(rows + c0, ld * 8, 0, (ld - c0) * 8, rows_pad, st));
-    hipLaunchKernelGGL(evidence_seed_kernel, dim3((unsigned)ceil_div(nrows, 256)), dim3(256), 0, st, rows, ld, first, nrows);
-    ctx->launch_counter++;
-    ktime_end(ctx, slot, "evidence_seed", (double)rows_pad * (double)(ld - c0) * 8.0);
-    slot = ktime_begin(ctx);
-    GDML_TRY(tall_trsm(ctx, ctx->K + c0 * ld + c0, rows + c0, rows_pad, n - c0, ld, 0));
-    HIP_CHECK(ctx, hipMemcpy2DAsync(Z + first * ld + c0, ld * 8, rows + c0, ld * 8, (ld - c0) * 8, nrows, hipMemcpyDeviceToDevice, st));
-    ktime_end(ctx, slot, "evidence_solve", (double)(n - c0) * (double)(n - c0) * (double)nrows);
+    const int64_t nrows = bc * n3, first = j0 * n3, c0 = first / 512 * 512, r1 = first + nrows;
+    // pass 1: seed and solve in the chunk buffer, and keep the true rows
+    GDML_TRY(factor_inverse_rows(ctx, g, rows, j0, bc, "evidence_seed", "evidence_solve", Z));
     // pass 2: rows of -A^-1 up to the chunk's own diagonal blocks, over the chunk buffer
-    slot = ktime_begin(ctx);
+    int slot = ktime_begin(ctx);
     GDML_TRY(launch_gemm_nt_neg(ctx, st, Z + first * ld + c0, ld, Z + c0, ld, rows, ld, nrows, r1, ld - c0));
     ktime_end(ctx, slot, "evidence_inv", 2.0 * (double)nrows * (double)r1 * (double)(ld - c0));
     // pass 3
@@ -309,14 +289,11 @@ static int evidence_run(gdml_ctx* ctx, const GramSplit& g, double* Z, const doub
     if (e != hipSuccess) return gdml_fail(ctx, GDML_ERR_HIP, "gdml_evidence_grad launch: %s", hipGetErrorString(e));
   }
   GDML_TRY(phase_end(ctx, "evidence"));
-  // log det A = 2 sum log L_ii: the gather and the host sum of gdml_loo (the same bits)
-  std::vector<double> diag((size_t)n), pts((size_t)(3 * M));
-  hipLaunchKernelGGL(evidence_diag_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, ctx->K, ld, n, d_diag);
-  HIP_CHECK(ctx, hipMemcpyAsync(diag.data(), d_diag, n * 8, hipMemcpyDeviceToHost, st));
+  GDML_TRY(factor_logdet(ctx, g, d_diag, &terms_out[4]));
+  std::vector<double> pts((size_t)(3 * M));
   HIP_CHECK(ctx, hipMemcpyAsync(pts.data(), d_pts, 3 * M * 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(ctx, hipStreamSynchronize(st));
-  double ld_sum = 0.0, tr = 0.0, ik = 0.0, aka = 0.0, aa = 0.0;
-  for (int64_t i = 0; i < n; ++i) ld_sum += log(diag[i]);
+  double tr = 0.0, ik = 0.0, aka = 0.0, aa = 0.0;
   for (int64_t i = 0; i < M; ++i) {  // the tiles hold -A^-1
     ik -= pts[3 * i];
     aka += pts[3 * i + 1];
@@ -327,7 +304,6 @@ static int evidence_run(gdml_ctx* ctx, const GramSplit& g, double* Z, const doub
   terms_out[1] = ik;
   terms_out[2] = aka;
   terms_out[3] = aa;
-  terms_out[4] = 2.0 * ld_sum;
   return GDML_OK;
 }
 
@@ -337,15 +313,9 @@ extern "C" int gdml_evidence_grad(gdml_ctx* ctx, const double* alphas, int64_t n
   if (!alphas || !terms_out) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_evidence_grad: alphas or terms_out is NULL");
   if (ctx->world > 1)
     return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_evidence_grad: the factor of a multi-rank context is distributed");
-  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_evidence_grad: call gdml_train_upload first");
-  if (ctx->K && ctx->K_factored && ctx->K_use_E)
-    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_evidence_grad: the resident factor carries energy-constraint rows");
-  if (!ctx->K || !ctx->K_factored)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_evidence_grad: no Cholesky factor resident (gdml_uncert_prepare or gdml_chol_factor)");
-  const int64_t M = ctx->ts.M, n3 = 3 * ctx->ts.N;
-  const GramSplit g = gram_split(M * n3, (int)n3);
-  if (ctx->K_rows != M * n3 || ctx->K_cols != ctx->K_rows || ctx->K_ld != g.ld || ctx->K_sharded)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_evidence_grad: the resident factor does not belong to the resident training set");
+  GramSplit g;
+  GDML_TRY(resident_factor_check(ctx, "gdml_evidence_grad", false, &g));
+  const int64_t M = ctx->ts.M, n3 = g.n3;
   if (n != M * n3)
     return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_evidence_grad: n (%lld) is not 3N M = %lld", (long long)n, (long long)(M * n3));
   HIP_CHECK(ctx, hipSetDevice(ctx->device));

@@ -80,11 +80,11 @@ __global__ void __launch_bounds__(256) extend_store_lower_kernel(const double* _
   for (int64_t c = threadIdx.x; c <= r; c += 256) dst[r * ld + c] = S[r * lds + c];
 }
 
+// (gram_split's S = min(32, ceil(n / 1024)) does not fall as n grows: the plan for n1 columns covers every chunk's n_cur / 16 * 16)
 static int64_t extend_ws_doubles(int64_t n1, int64_t bc, int64_t n3) {
-  const int64_t mc = bc * n3, nblk = (mc + 63) / 64, npairs = nblk * (nblk + 1) / 2;
-  int64_t S = (n1 + 1023) / 1024;  // gram_split never plans more splits for n <= n1
-  if (S > 32) S = 32;
-  return bc * n3 * n3 + npairs * S * 4096 + mc * ((mc + 15) / 16 * 16);
+  const int64_t mc = bc * n3;
+  const GramSplit g = gram_split(n1, (int)mc);
+  return bc * n3 * n3 + (int64_t)g.npairs * g.S * 4096 + mc * round16(mc);
 }
 
 extern "C" int gdml_factor_extend(gdml_ctx* ctx, const double* R_desc_new, const double* R_d_desc_new, int64_t b, int* info) {
@@ -95,19 +95,12 @@ extern "C" int gdml_factor_extend(gdml_ctx* ctx, const double* R_desc_new, const
     return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_factor_extend: R_desc_new or R_d_desc_new is NULL");
   if (comm_active(ctx) && ctx->world > 1)
     return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_factor_extend: the factor of a multi-rank context is distributed");
-  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_factor_extend: call gdml_train_upload first");
-  if (ctx->K && ctx->K_factored && ctx->K_use_E)
-    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_factor_extend: the resident factor carries energy-constraint rows");
-  if (!ctx->uncert_ready || !ctx->K || !ctx->K_factored)
-    return gdml_fail(ctx, GDML_ERR_STATE,
-                     "gdml_factor_extend: no factor prepared (gdml_uncert_prepare; an assembly since then overwrote it)");
+  GramSplit g0;
+  GDML_TRY(resident_factor_check(ctx, "gdml_factor_extend", true, &g0));
   TrainSet& ts = ctx->ts;
-  const int64_t M0 = ts.M, n3 = 3 * (int64_t)ts.N, D = ts.D;
-  const int64_t n0 = M0 * n3, ld0 = (n0 + 15) / 16 * 16;
-  if (ctx->K_rows != n0 || ctx->K_cols != n0 || ctx->K_ld != ld0 || ctx->K_sharded)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_factor_extend: the resident factor does not belong to the resident training set");
+  const int64_t M0 = ts.M, n3 = g0.n3, D = ts.D, n0 = g0.n, ld0 = g0.ld;
   if (b == 0) return GDML_OK;
-  const int64_t n1 = n0 + b * n3, ld1 = (n1 + 15) / 16 * 16;
+  const int64_t n1 = n0 + b * n3, ld1 = round16(n1);
   if (n1 > INT32_MAX) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_factor_extend: %lld rows exceed the factorisation's range", (long long)n1);
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -125,42 +118,30 @@ extern "C" int gdml_factor_extend(gdml_ctx* ctx, const double* R_desc_new, const
     if (Kn) (void)ctx_free(ctx, Kn);
     return rc;
   };
-#define EXT_TRY(expr)                         \
-  do {                                        \
-    const int rc_e = (expr);                  \
-    if (rc_e != GDML_OK) return drop(rc_e);   \
-  } while (0)
-#define EXT_HIP(call)                                                                                               \
-  do {                                                                                                              \
-    const hipError_t e_e = (call);                                                                                  \
-    if (e_e != hipSuccess)                                                                                          \
-      return drop(gdml_fail(ctx, e_e == hipErrorOutOfMemory ? GDML_ERR_OOM : GDML_ERR_HIP, "%s failed: %s (%s:%d)", \
-                            #call, hipGetErrorString(e_e), __FILE__, __LINE__));                                    \
-  } while (0)
 
   // the matrix with up to 127 pad rows behind it: the solve runs on whole 128-row tiles (pad_rows128)
   const int64_t Kn_bytes = (n1 + 127) * ld1 * 8;
-  EXT_TRY(ctx_alloc(ctx, (void**)&Kn, Kn_bytes));
-  EXT_TRY(ctx_alloc(ctx, (void**)&x1, (M0 + b) * D * 8));
-  EXT_TRY(ctx_alloc(ctx, (void**)&g1, (M0 + b) * D * 24));
+  DROP_TRY(ctx_alloc(ctx, (void**)&Kn, Kn_bytes));
+  DROP_TRY(ctx_alloc(ctx, (void**)&x1, (M0 + b) * D * 8));
+  DROP_TRY(ctx_alloc(ctx, (void**)&g1, (M0 + b) * D * 24));
   // chunk length: the option's cap, the point count, then halved while the work buffers exceed 90 % of free memory
   int64_t bc = ctx_opt_i(ctx, "chol.extend_chunk", 64);
   if (bc < 1) bc = 1;
   if (bc > b) bc = b;
   size_t mem_free = 0, mem_total = 0;
-  EXT_HIP(hipMemGetInfo(&mem_free, &mem_total));
+  DROP_HIP(hipMemGetInfo(&mem_free, &mem_total));
   while (bc > 1 && extend_ws_doubles(n1, bc, n3) * 8 > (int64_t)mem_free / 10 * 9) bc = (bc + 1) / 2;
-  EXT_TRY(ctx_alloc(ctx, (void**)&ws, extend_ws_doubles(n1, bc, n3) * 8));
-  const int64_t mc_max = bc * n3, lds = (mc_max + 15) / 16 * 16;
+  DROP_TRY(ctx_alloc(ctx, (void**)&ws, extend_ws_doubles(n1, bc, n3) * 8));
+  const int64_t mc_max = bc * n3, lds = round16(mc_max);
   double* const Sb = ws;                      // Schur complement of a chunk, pitch lds (32-byte aligned rows: first)
   double* const kqq = Sb + mc_max * lds;      // the cross-kernel's k_qq output (the same blocks arrive as columns of D)
   double* const part = kqq + bc * n3 * n3;
 
   phase_begin(ctx);
-  EXT_HIP(hipMemcpyAsync(x1, ts.x, M0 * D * 8, hipMemcpyDeviceToDevice, st));
-  EXT_HIP(hipMemcpyAsync(g1, ts.g, M0 * D * 24, hipMemcpyDeviceToDevice, st));
-  EXT_HIP(hipMemcpyAsync(x1 + M0 * D, R_desc_new, b * D * 8, hipMemcpyHostToDevice, st));
-  EXT_HIP(hipMemcpyAsync(g1 + M0 * D * 3, R_d_desc_new, b * D * 24, hipMemcpyHostToDevice, st));
+  DROP_HIP(hipMemcpyAsync(x1, ts.x, M0 * D * 8, hipMemcpyDeviceToDevice, st));
+  DROP_HIP(hipMemcpyAsync(g1, ts.g, M0 * D * 24, hipMemcpyDeviceToDevice, st));
+  DROP_HIP(hipMemcpyAsync(x1 + M0 * D, R_desc_new, b * D * 8, hipMemcpyHostToDevice, st));
+  DROP_HIP(hipMemcpyAsync(g1 + M0 * D * 3, R_d_desc_new, b * D * 24, hipMemcpyHostToDevice, st));
   int slot = ktime_begin(ctx);
   {
     int64_t grid = (n0 + 1) / 2;
@@ -174,20 +155,20 @@ extern "C" int gdml_factor_extend(gdml_ctx* ctx, const double* R_desc_new, const
   for (int64_t p0 = 0; p0 < b; p0 += bc) {
     const int64_t c = b - p0 < bc ? b - p0 : bc, mc = c * n3, rows_pad = pad_rows128(mc);
     double* const rows = Kn + n_cur * ld1;
-    if (rows_pad > mc) EXT_HIP(hipMemsetAsync(rows + mc * ld1, 0, (rows_pad - mc) * ld1 * 8, st));
+    if (rows_pad > mc) DROP_HIP(hipMemsetAsync(rows + mc * ld1, 0, (rows_pad - mc) * ld1 * 8, st));
     // [C | D] = -Kx of the chunk's points against the old points, the earlier chunks and the chunk itself
-    EXT_TRY(cross_rows_launch(ctx, x1, g1, M_cur + c, x1 + M_cur * D, g1 + M_cur * D * 3, (int)c, rows, ld1, kqq, -1.0, ctx->K_sig,
+    DROP_TRY(cross_rows_launch(ctx, x1, g1, M_cur + c, x1 + M_cur * D, g1 + M_cur * D * 3, (int)c, rows, ld1, kqq, -1.0, ctx->K_sig,
                               "extend_cross"));
     // W = C L'^-T over the n_cur finished rows, right-looking (few rows, long factor: uncert.hip)
     slot = ktime_begin(ctx);
-    EXT_TRY(tall_trsm(ctx, Kn, rows, rows_pad, n_cur, ld1, 0));
+    DROP_TRY(tall_trsm(ctx, Kn, rows, rows_pad, n_cur, ld1, 0));
     ktime_end(ctx, slot, "extend_solve", (double)n_cur * (double)n_cur * (double)mc);
     // S = D + lam I - W W^T
     slot = ktime_begin(ctx);
     SchurArgs a;
     a.part = part; a.W = rows; a.S = Sb; a.ld = ld1; a.lds = lds; a.n16 = n_cur / 16 * 16; a.ncur = n_cur;
     a.mc = (int)mc; a.nsplit = 0; a.lam = ctx->K_lam;
-    EXT_HIP(hipMemsetAsync(Sb, 0, mc * lds * 8, st));  // (the factorisation loads whole diagonal blocks: no stale upper triangle)
+    DROP_HIP(hipMemsetAsync(Sb, 0, mc * lds * 8, st));  // (the factorisation loads whole diagonal blocks: no stale upper triangle)
     const int nblk = (int)((mc + 63) / 64), npairs = nblk * (nblk + 1) / 2;
     if (a.n16 > 0) {
       const GramSplit g = gram_split(a.n16, (int)mc);
@@ -197,10 +178,10 @@ extern "C" int gdml_factor_extend(gdml_ctx* ctx, const double* R_desc_new, const
     hipLaunchKernelGGL(schur_reduce_kernel, dim3((unsigned)npairs), dim3(256), 0, st, a);
     ctx->launch_counter++;
     ktime_end(ctx, slot, "extend_schur", (double)mc * (double)mc * (double)n_cur);
-    EXT_HIP(hipGetLastError());
+    DROP_HIP(hipGetLastError());
     slot = ktime_begin(ctx);
     int inf = 0;
-    EXT_TRY(chol_factor_device(ctx, Sb, mc, lds, &inf));
+    DROP_TRY(chol_factor_device(ctx, Sb, mc, lds, &inf));
     if (inf != 0) {
       if (info) *info = (int)(n_cur + inf);
       return drop(gdml_fail(ctx, GDML_ERR_NOT_PD, "gdml_factor_extend: %lld-th leading minor of the extended matrix is not positive definite",
@@ -209,38 +190,15 @@ extern "C" int gdml_factor_extend(gdml_ctx* ctx, const double* R_desc_new, const
     hipLaunchKernelGGL(extend_store_lower_kernel, dim3((unsigned)mc), dim3(256), 0, st, Sb, lds, rows + n_cur, ld1);
     ctx->launch_counter++;
     ktime_end(ctx, slot, "extend_chol", (double)mc * (double)mc * (double)mc / 3.0);
-    EXT_HIP(hipGetLastError());
+    DROP_HIP(hipGetLastError());
     n_cur += mc;
     M_cur += c;
   }
-  EXT_TRY(phase_end(ctx, "extend"));
-  EXT_HIP(hipStreamSynchronize(st));
-#undef EXT_TRY
-#undef EXT_HIP
+  DROP_TRY(phase_end(ctx, "extend"));
+  DROP_HIP(hipStreamSynchronize(st));
 
-  // ---- commit: nothing below fails half way (ctx_free of a tracked pointer on an idle stream)
+  // ---- commit
   (void)ctx_free(ctx, ws);
-  (void)ctx_free(ctx, ctx->K);
-  ctx->K = Kn;
-  ctx->K_bytes = Kn_bytes;
-  ctx->K_rows = ctx->K_cols = ctx->K_rows_global = n1;
-  ctx->K_ld = ld1;
-  ctx->K_extra = 0;
-  ctx->K_rhs_row = false;
-  ctx->K_factored = true;
-  ctx->precon = nullptr;
-  // the training set: the dense tables derived from the old one are built again when an assembly next asks for them
-  (void)ctx_free(ctx, ts.x);
-  (void)ctx_free(ctx, ts.g);
-  (void)ctx_free(ctx, ts.XF);
-  (void)ctx_free(ctx, ts.GD);
-  (void)ctx_free(ctx, ts.TS);
-  (void)ctx_free(ctx, ts.p2);
-  (void)ctx_free(ctx, ts.p2_TP);
-  ts.XF = ts.GD = ts.TS = ts.p2_TP = nullptr;
-  ts.p2 = nullptr;
-  ts.x = x1;
-  ts.g = g1;
-  ts.M = M0 + b;
+  factor_commit(ctx, Kn, Kn_bytes, n1, ld1, x1, g1, M0 + b);
   return GDML_OK;
 }

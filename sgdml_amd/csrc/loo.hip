@@ -4,7 +4,7 @@
 // Conventions: A = -K + lam I = L L^T resident in ctx->K (lower triangle, row-major, pitch K_ld), n = 3N M,
 // a = A^-1 y = -alphas, E_j the n x 3N selector of training point j's rows.  With G_j = E_j^T A^-1 E_j (Rasmussen &
 // Williams 5.4.2, block form):
-//   Z_j = E_j^T L^-T                 rows 3N j .. 3N j + 3N - 1 of L^-T: zero left of column 3N j   (tall_trsm of cg.hip)
+//   Z_j = E_j^T L^-T                 rows 3N j .. 3N j + 3N - 1 of L^-T: zero left of column 3N j   (factor_inverse_rows)
 //   G_j = Z_j Z_j^T                                                                                 (block_gram.hip) 
 //   r_j = G_j^-1 a_j,  C_j = G_j^-1                                                                 (loo_block_kernel)
 // r_j is the force error at x_j of the model trained without point j, C_j the predictive covariance of that left-out
@@ -20,17 +20,6 @@
 #include "common.h"
 
 #define LOO_LDS_MAX_N3 128
-
-// unit entries of Z's right-hand side E_j^T: row r of the chunk is coordinate r of the chunk's points
-__global__ void __launch_bounds__(256) loo_seed_kernel(double* __restrict__ rows, int64_t ld, int64_t col0, int64_t nrows) {
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r < nrows) rows[r * ld + col0 + r] = 1.0;
-}
-
-__global__ void __launch_bounds__(256) loo_diag_kernel(const double* __restrict__ Lf, int64_t ld, int64_t n, double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = Lf[i * ld + i];
-}
 
 // ---- block solve ---------------------------------------------------------------------------------------------------------
 // One workgroup per training point.  G_j (lower triangle; pitch gp, odd: a column walk meets every LDS bank) is summed from
@@ -182,16 +171,9 @@ extern "C" int gdml_loo(gdml_ctx* ctx, const double* alphas, int64_t n, int cov_
   if (cov_mode != 0 && !cov_out) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_loo: cov_out is NULL");
   if (ctx->world > 1)
     return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_loo: the factor of a multi-rank context is distributed");
-  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_loo: call gdml_train_upload first");
-  if (ctx->K && ctx->K_factored && ctx->K_use_E)
-    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_loo: the resident factor carries energy-constraint rows");
-  if (!ctx->K || !ctx->K_factored)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_loo: no Cholesky factor resident (gdml_uncert_prepare or gdml_chol_factor)");
-  const int64_t M = ctx->ts.M, n3 = 3 * ctx->ts.N;
-  const GramSplit g = gram_split(M * n3, (int)n3);
-  const int64_t ld = g.ld;
-  if (ctx->K_rows != M * n3 || ctx->K_cols != ctx->K_rows || ctx->K_ld != ld || ctx->K_sharded)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_loo: the resident factor does not belong to the resident training set");
+  GramSplit g;
+  GDML_TRY(resident_factor_check(ctx, "gdml_loo", false, &g));
+  const int64_t M = ctx->ts.M, n3 = g.n3;
   if (n != M * n3) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_loo: n (%lld) is not 3N M = %lld", (long long)n, (long long)(M * n3));
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
   LooPlan p;
@@ -205,22 +187,13 @@ extern "C" int gdml_loo(gdml_ctx* ctx, const double* alphas, int64_t n, int cov_
   phase_begin(ctx);
   for (int64_t j0 = 0; j0 < M; j0 += p.bc) {
     const int64_t bc = M - j0 < p.bc ? M - j0 : p.bc;
-    const int64_t rows = bc * n3, rows_pad = pad_rows128(rows);
-    const int64_t first = j0 * n3, c0 = first / 512 * 512;
-    // seed: E_j^T from column c0 on (columns left of c0 are not part of the sub-problem and are never read)
-    int slot = ktime_begin(ctx);
-    HIP_CHECK(ctx, hipMemset2DAsync(p.rows + c0, ld * 8, 0, (ld - c0) * 8, rows_pad, st));
-    hipLaunchKernelGGL(loo_seed_kernel, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, p.rows, ld, first, rows);
-    ctx->launch_counter++;
-    ktime_end(ctx, slot, "loo_seed", (double)rows_pad * (double)(ld - c0) * 8.0);
-    // Z = E^T L^-T on the trailing sub-problem, right-looking (few rows, long factor: uncert.hip)
-    slot = ktime_begin(ctx);
-    GDML_TRY(tall_trsm(ctx, ctx->K + c0 * ld + c0, p.rows + c0, rows_pad, n - c0, ld, 0));
-    ktime_end(ctx, slot, "loo_solve", (double)(n - c0) * (double)(n - c0) * (double)rows);
+    const int64_t first = j0 * n3;
+    // Z = E^T L^-T on the trailing sub-problem
+    GDML_TRY(factor_inverse_rows(ctx, g, p.rows, j0, bc, "loo_seed", "loo_solve"));
     // G_j = Z_j Z_j^T: point j0 + p is zero left of its first column (j0 + p) 3N
-    slot = ktime_begin(ctx);
+    int slot = ktime_begin(ctx);
     block_gram_launch(ctx, g, p.rows, p.part, bc, false, first, n3);
-    ktime_end(ctx, slot, "loo_gram", 2.0 * (double)n3 * (double)n3 * ((double)ld * bc - (double)n3 * (j0 * bc + bc * (bc - 1) / 2)));
+    ktime_end(ctx, slot, "loo_gram", 2.0 * (double)n3 * (double)n3 * ((double)g.ld * bc - (double)n3 * (j0 * bc + bc * (bc - 1) / 2)));
     LooBlockArgs b;
     b.part = p.part; b.alphas = p.alphas; b.gscr = p.gscr; b.resid = p.resid; b.cov = cov_mode ? p.out : nullptr;
     b.flags = p.flags; b.L = g.L; b.j0 = j0; b.n3 = g.n3; b.gp = p.gp; b.npairs = g.npairs; b.S = g.S; b.cov_mode = cov_mode;
@@ -239,17 +212,11 @@ extern "C" int gdml_loo(gdml_ctx* ctx, const double* alphas, int64_t n, int cov_
     }
   }
   GDML_TRY(phase_end(ctx, "loo"));
-  // log det A = 2 sum log L_ii: a strided copy and a host sum in index order
-  std::vector<double> diag((size_t)n);
+  GDML_TRY(factor_logdet(ctx, g, p.diag, logdet_out));
   std::vector<int> flags((size_t)M);
-  hipLaunchKernelGGL(loo_diag_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, ctx->K, ld, n, p.diag);
-  HIP_CHECK(ctx, hipMemcpyAsync(diag.data(), p.diag, n * 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(ctx, hipMemcpyAsync(flags.data(), p.flags, M * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_CHECK(ctx, hipMemcpyAsync(resid_out, p.resid, n * 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(ctx, hipStreamSynchronize(st));
-  double ld_sum = 0.0;
-  for (int64_t i = 0; i < n; ++i) ld_sum += log(diag[i]);
-  *logdet_out = 2.0 * ld_sum;
   for (int64_t j = 0; j < M; ++j)
     if (flags[j]) {
       if (info) *info = (int)(j + 1);

@@ -311,8 +311,6 @@ __global__ void __launch_bounds__(256) remove_apply_kernel(RemoveApplyArgs a) {
   }
 }
 
-static inline int64_t rm_round16(int64_t v) { return (v + 15) / 16 * 16; }
-
 extern "C" int gdml_factor_remove(gdml_ctx* ctx, const int64_t* idx, int64_t b, int* info) {
   if (!ctx) return GDML_ERR_INVALID;
   if (info) *info = 0;
@@ -320,17 +318,10 @@ extern "C" int gdml_factor_remove(gdml_ctx* ctx, const int64_t* idx, int64_t b, 
   if (b > 0 && !idx) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_factor_remove: idx is NULL");
   if (comm_active(ctx) && ctx->world > 1)
     return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_factor_remove: the factor of a multi-rank context is distributed");
-  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_factor_remove: call gdml_train_upload first");
-  if (ctx->K && ctx->K_factored && ctx->K_use_E)
-    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_factor_remove: the resident factor carries energy-constraint rows");
-  if (!ctx->uncert_ready || !ctx->K || !ctx->K_factored)
-    return gdml_fail(ctx, GDML_ERR_STATE,
-                     "gdml_factor_remove: no factor prepared (gdml_uncert_prepare; an assembly since then overwrote it)");
+  GramSplit g0;
+  GDML_TRY(resident_factor_check(ctx, "gdml_factor_remove", true, &g0));
   TrainSet& ts = ctx->ts;
-  const int64_t M0 = ts.M, n3 = 3 * (int64_t)ts.N, D = ts.D;
-  const int64_t n0 = M0 * n3, ld0 = rm_round16(n0);
-  if (ctx->K_rows != n0 || ctx->K_cols != n0 || ctx->K_ld != ld0 || ctx->K_sharded)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_factor_remove: the resident factor does not belong to the resident training set");
+  const int64_t M0 = ts.M, n3 = g0.n3, D = ts.D, ld0 = g0.ld;
   if (b == 0) return GDML_OK;
   if (b >= M0) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_factor_remove: %lld of %lld points: nothing would be left", (long long)b, (long long)M0);
   std::vector<char> gone((size_t)M0, 0);
@@ -340,7 +331,7 @@ extern "C" int gdml_factor_remove(gdml_ctx* ctx, const int64_t* idx, int64_t b, 
     if (gone[(size_t)idx[i]]) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_factor_remove: index %lld occurs twice", (long long)idx[i]);
     gone[(size_t)idx[i]] = 1;
   }
-  const int64_t M1 = M0 - b, n1 = M1 * n3, ld1 = rm_round16(n1), m = b * n3;
+  const int64_t M1 = M0 - b, n1 = M1 * n3, ld1 = round16(n1), m = b * n3;
   std::vector<int32_t> map((size_t)M0);  // [0, M1): old index of kept point p; [M1, M0): removed points, ascending
   {
     int64_t pk = 0, pr = M1;
@@ -351,7 +342,7 @@ extern "C" int gdml_factor_remove(gdml_ctx* ctx, const int64_t* idx, int64_t b, 
   if (chunk < 1) chunk = 1;
   int64_t w = chunk * n3 < RM_W ? chunk * n3 : RM_W;
   if (w > m) w = m;
-  const int64_t wp = rm_round16(w), nsl = (m + w - 1) / w, ldv = nsl * wp;
+  const int64_t wp = round16(w), nsl = (m + w - 1) / w, ldv = nsl * wp;
 
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -369,27 +360,15 @@ extern "C" int gdml_factor_remove(gdml_ctx* ctx, const int64_t* idx, int64_t b, 
     if (Kn) (void)ctx_free(ctx, Kn);
     return rc;
   };
-#define RM_TRY(expr)                        \
-  do {                                      \
-    const int rc_e = (expr);                \
-    if (rc_e != GDML_OK) return drop(rc_e); \
-  } while (0)
-#define RM_HIP(call)                                                                                                \
-  do {                                                                                                              \
-    const hipError_t e_e = (call);                                                                                  \
-    if (e_e != hipSuccess)                                                                                          \
-      return drop(gdml_fail(ctx, e_e == hipErrorOutOfMemory ? GDML_ERR_OOM : GDML_ERR_HIP, "%s failed: %s (%s:%d)", \
-                            #call, hipGetErrorString(e_e), __FILE__, __LINE__));                                    \
-  } while (0)
 
   // the matrix with 127 pad rows behind it (gdml_factor_extend solves its new rows there on whole 128-row tiles)
   const int64_t Kn_bytes = (n1 + 127) * ld1 * 8;
-  RM_TRY(ctx_alloc(ctx, (void**)&Kn, Kn_bytes));
-  RM_TRY(ctx_alloc(ctx, (void**)&x1, M1 * D * 8));
-  RM_TRY(ctx_alloc(ctx, (void**)&g1, M1 * D * 24));
+  DROP_TRY(ctx_alloc(ctx, (void**)&Kn, Kn_bytes));
+  DROP_TRY(ctx_alloc(ctx, (void**)&x1, M1 * D * 8));
+  DROP_TRY(ctx_alloc(ctx, (void**)&g1, M1 * D * 24));
   // work buffer: V (n1 x ldv) | U (64 x wp) | T (64 x 64) | sgn (64) | the point map (M0 int32)
   const int64_t ws_doubles = n1 * ldv + 64 * wp + 4096 + 64 + (M0 + 1) / 2;
-  RM_TRY(ctx_alloc(ctx, (void**)&ws, ws_doubles * 8));
+  DROP_TRY(ctx_alloc(ctx, (void**)&ws, ws_doubles * 8));
   double* const V = ws;
   double* const Ub = V + n1 * ldv;
   double* const Tb = Ub + 64 * wp;
@@ -397,20 +376,20 @@ extern "C" int gdml_factor_remove(gdml_ctx* ctx, const int64_t* idx, int64_t b, 
   int32_t* const d_map = reinterpret_cast<int32_t*>(sgb + 64);
   const int lds_panel = (int)((2 * 64 * 65 + 64 * (wp + 4) + 128) * 8);
   const int lds_apply = (int)((64 * (wp + 4) + 64 * 68 + 64) * 8);
-  RM_HIP(hipFuncSetAttribute((const void*)remove_panel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_panel));
-  RM_HIP(hipFuncSetAttribute((const void*)remove_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_apply));
+  DROP_HIP(hipFuncSetAttribute((const void*)remove_panel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_panel));
+  DROP_HIP(hipFuncSetAttribute((const void*)remove_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_apply));
 
   phase_begin(ctx);
-  RM_HIP(hipMemcpyAsync(d_map, map.data(), M0 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  RM_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
-  RM_HIP(hipMemsetAsync(Kn + n1 * ld1, 0, 127 * ld1 * 8, st));
+  DROP_HIP(hipMemcpyAsync(d_map, map.data(), M0 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  DROP_HIP(hipMemsetAsync(ctx->d_info, 0, sizeof(int), st));
+  DROP_HIP(hipMemsetAsync(Kn + n1 * ld1, 0, 127 * ld1 * 8, st));
   // the kept points' descriptors and Jacobians, one copy per run of consecutive kept points
   for (int64_t p = 0; p < M1;) {
     int64_t q = p + 1;
     while (q < M1 && map[(size_t)q] == map[(size_t)q - 1] + 1) ++q;
     const int64_t o = map[(size_t)p];
-    RM_HIP(hipMemcpyAsync(x1 + p * D, ts.x + o * D, (q - p) * D * 8, hipMemcpyDeviceToDevice, st));
-    RM_HIP(hipMemcpyAsync(g1 + p * D * 3, ts.g + o * D * 3, (q - p) * D * 24, hipMemcpyDeviceToDevice, st));
+    DROP_HIP(hipMemcpyAsync(x1 + p * D, ts.x + o * D, (q - p) * D * 8, hipMemcpyDeviceToDevice, st));
+    DROP_HIP(hipMemcpyAsync(g1 + p * D * 3, ts.g + o * D * 3, (q - p) * D * 24, hipMemcpyDeviceToDevice, st));
     p = q;
   }
   int slot = ktime_begin(ctx);
@@ -425,7 +404,7 @@ extern "C" int gdml_factor_remove(gdml_ctx* ctx, const int64_t* idx, int64_t b, 
     ctx->launch_counter++;
   }
   ktime_end(ctx, slot, "remove_compact", ((double)n1 * (double)(n1 + 1) + 2.0 * (double)n1 * (double)ldv) * 8.0);  // bytes read + written
-  RM_HIP(hipGetLastError());
+  DROP_HIP(hipGetLastError());
 
   for (int64_t g = nsl - 1; g >= 0; --g) {
     // rows above the first kept column behind the slice's first removed point are zero in the slice
@@ -452,43 +431,20 @@ extern "C" int gdml_factor_remove(gdml_ctx* ctx, const int64_t* idx, int64_t b, 
         ktime_end(ctx, slot, "remove_apply", (double)below * (256.0 * (double)wp + 5120.0));  // two 64 x wp products, the triangle of T
       }
     }
-    RM_HIP(hipGetLastError());
-    if (ctx->profiling) RM_TRY(ktime_collect(ctx));  // (a sweep is up to 2000 timed launches: their events go back to the pool)
+    DROP_HIP(hipGetLastError());
+    if (ctx->profiling) DROP_TRY(ktime_collect(ctx));  // (a sweep is up to 2000 timed launches: their events go back to the pool)
   }
   int flag = 0;
-  RM_HIP(hipMemcpyAsync(&flag, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, st));
-  RM_TRY(phase_end(ctx, "remove"));
-  RM_HIP(hipStreamSynchronize(st));
+  DROP_HIP(hipMemcpyAsync(&flag, ctx->d_info, sizeof(int), hipMemcpyDeviceToHost, st));
+  DROP_TRY(phase_end(ctx, "remove"));
+  DROP_HIP(hipStreamSynchronize(st));
   if (flag != 0) {
     if (info) *info = flag;
     return drop(gdml_fail(ctx, GDML_ERR_NOT_PD, "gdml_factor_remove: column %d of the reduced factor has no positive finite diagonal entry", flag));
   }
-#undef RM_TRY
-#undef RM_HIP
 
-  // ---- commit: nothing below fails half way (ctx_free of a tracked pointer on an idle stream)
+  // ---- commit
   (void)ctx_free(ctx, ws);
-  (void)ctx_free(ctx, ctx->K);
-  ctx->K = Kn;
-  ctx->K_bytes = Kn_bytes;
-  ctx->K_rows = ctx->K_cols = ctx->K_rows_global = n1;
-  ctx->K_ld = ld1;
-  ctx->K_extra = 0;
-  ctx->K_rhs_row = false;
-  ctx->K_factored = true;
-  ctx->precon = nullptr;
-  // the training set: the dense tables derived from the old one are built again when an assembly next asks for them
-  (void)ctx_free(ctx, ts.x);
-  (void)ctx_free(ctx, ts.g);
-  (void)ctx_free(ctx, ts.XF);
-  (void)ctx_free(ctx, ts.GD);
-  (void)ctx_free(ctx, ts.TS);
-  (void)ctx_free(ctx, ts.p2);
-  (void)ctx_free(ctx, ts.p2_TP);
-  ts.XF = ts.GD = ts.TS = ts.p2_TP = nullptr;
-  ts.p2 = nullptr;
-  ts.x = x1;
-  ts.g = g1;
-  ts.M = M1;
+  factor_commit(ctx, Kn, Kn_bytes, n1, ld1, x1, g1, M1);
   return GDML_OK;
 }

@@ -217,8 +217,6 @@ __global__ void __launch_bounds__(256) select_downdate_kernel(double* __restrict
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-static inline int64_t round16(int64_t v) { return (v + 15) / 16 * 16; }
-
 // doubles the joint sweep retains for a pool of B candidates and n_select > 1 picks (W, Sig, descriptors, the block columns V,
 // the partial tiles of the column, G, scratch of the GLOBAL score form, gains / flags)
 static int64_t select_retained_doubles(const GramSplit& g, int64_t D, int64_t B, int64_t n_select, bool lds) {
@@ -253,16 +251,9 @@ extern "C" int gdml_select_points(gdml_ctx* ctx, const double* R, int64_t B, con
   *n_selected_out = 0;
   if (comm_active(ctx) && ctx->world > 1)
     return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_select_points: the factor of a multi-rank context is distributed");
-  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_select_points: call gdml_train_upload first");
-  if (ctx->K && ctx->K_factored && ctx->K_use_E)
-    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_select_points: the resident factor carries energy-constraint rows");
-  if (!ctx->uncert_ready || !ctx->K || !ctx->K_factored)
-    return gdml_fail(ctx, GDML_ERR_STATE,
-                     "gdml_select_points: no factor prepared (gdml_uncert_prepare; an assembly since then overwrote it)");
+  GramSplit g;
+  GDML_TRY(resident_factor_check(ctx, "gdml_select_points", true, &g));
   const TrainSet& ts = ctx->ts;
-  const GramSplit g = gram_split(ts.M * 3 * ts.N, 3 * ts.N);
-  if (ctx->K_rows != g.n || ctx->K_cols != g.n || ctx->K_ld != g.ld || ctx->K_sharded)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_select_points: the resident factor does not belong to the resident training set");
   if (B == 0) return GDML_OK;
   if (B * 2 > INT32_MAX) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_select_points: a pool of %lld candidates exceeds the cross kernel's range", (long long)B);
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -287,24 +278,12 @@ extern "C" int gdml_select_points(gdml_ctx* ctx, const double* R, int64_t B, con
     }
     return rc;
   };
-#define SEL_TRY(expr)                         \
-  do {                                        \
-    const int rc_e = (expr);                  \
-    if (rc_e != GDML_OK) return drop(rc_e);   \
-  } while (0)
-#define SEL_HIP(call)                                                                                               \
-  do {                                                                                                              \
-    const hipError_t e_e = (call);                                                                                  \
-    if (e_e != hipSuccess)                                                                                          \
-      return drop(gdml_fail(ctx, e_e == hipErrorOutOfMemory ? GDML_ERR_OOM : GDML_ERR_HIP, "%s failed: %s (%s:%d)", \
-                            #call, hipGetErrorString(e_e), __FILE__, __LINE__));                                    \
-  } while (0)
 
-  const int64_t small_A = n3 + 4 * D + 2 * n3 * n3 + (int64_t)g.npairs * g.S * 4096 + gscr_item;  // doubles per candidate of a chunk
+  const int64_t small_A = cov_chunk_doubles(g, D, true) + gscr_item;  // doubles per candidate of a chunk
   if (joint) {
     // budget: option chol.select_mem_budget (bytes; tests), else 90 % of what is free plus the two Gram slots, which are carved anew
     size_t mem_free = 0, mem_total = 0;
-    SEL_HIP(hipMemGetInfo(&mem_free, &mem_total));
+    DROP_HIP(hipMemGetInfo(&mem_free, &mem_total));
     double budget = ctx_opt(ctx, "chol.select_mem_budget", 0.0);
     if (!(budget > 0.0))
       budget = 0.9 * (double)((int64_t)mem_free + ctx->slot_bytes[SLOT_GRAM_WS] + ctx->slot_bytes[SLOT_GRAM_ROWS]);
@@ -322,14 +301,14 @@ extern "C" int gdml_select_points(gdml_ctx* ctx, const double* R, int64_t B, con
                             "largest pool that fits: %lld",
                             (long long)B, need(B) / 1048576.0, budget / 1048576.0, (long long)lo));
     }
-    SEL_TRY(ctx_slot_release(ctx, SLOT_GRAM_WS));
-    SEL_TRY(ctx_slot_release(ctx, SLOT_GRAM_ROWS));
-    SEL_TRY(ctx_alloc(ctx, (void**)&Wb, pad_rows128(m_pool) * g.ld * 8));
+    DROP_TRY(ctx_slot_release(ctx, SLOT_GRAM_WS));
+    DROP_TRY(ctx_slot_release(ctx, SLOT_GRAM_ROWS));
+    DROP_TRY(ctx_alloc(ctx, (void**)&Wb, pad_rows128(m_pool) * g.ld * 8));
   }
   const int64_t nv = n_select > 1 ? n_select - 1 : 0;
   const int64_t nrb = (m_pool + 63) / 64;
   const int64_t ws_doubles = joint ? select_retained_doubles(g, D, B, n_select, lds) - pad_rows128(m_pool) * g.ld : 3 * (B + 2) + 16;
-  SEL_TRY(ctx_alloc(ctx, (void**)&ws, ws_doubles * 8));
+  DROP_TRY(ctx_alloc(ctx, (void**)&ws, ws_doubles * 8));
   double* const d_gain = ws;                                   // (B + 1): the last entry takes the pivot launch's gain
   int* const d_flags = (int*)(d_gain + B + 2);                 // (B)
   int* const d_picked = (int*)(d_gain + B + 2 + (B + 2) / 2 + 1);  // (B)
@@ -340,53 +319,39 @@ extern "C" int gdml_select_points(gdml_ctx* ctx, const double* R, int64_t B, con
   double* const cpart = Vb + nv * m_pool * ldc;
   double* const Gf = cpart + (joint ? nrb * g.nblk * g.S * 4096 : 0);
   double* const gscr_B = Gf + (joint ? n3 * n3 : 0);
-  SEL_HIP(hipMemsetAsync(d_gain, 0, (3 * (B + 2) + 16) * 8, st));
+  DROP_HIP(hipMemsetAsync(d_gain, 0, (3 * (B + 2) + 16) * 8, st));
 
   if (lds_bytes > 64 * 1024)
-    SEL_HIP(hipFuncSetAttribute((const void*)select_score_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    DROP_HIP(hipFuncSetAttribute((const void*)select_score_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
   ScoreArgs sa;
   sa.flags = d_flags; sa.gain = d_gain; sa.n3 = (int)n3; sa.gp = gp; sa.lam = lam; sa.n3_log_lam = (double)n3 * log(lam);
 
   // ---- stage A: W, Sig^(0) and the initial gains, chunk by chunk (the sequence of gdml_predict_cov)
   int64_t bcA = 0;
   double *rowsA = nullptr, *wsA = nullptr;
-  SEL_TRY(gram_workspace(ctx, g, "chol.select_chunk", B, small_A, 0, &bcA, &rowsA, &wsA));
-  double* const a_R = wsA;
-  double* const a_xq = a_R + bcA * n3;
-  double* const a_gq = a_xq + bcA * D;
-  double* const a_nkqq = a_gq + 3 * bcA * D;
-  double* const a_out = a_nkqq + bcA * n3 * n3;
-  double* const a_part = a_out + bcA * n3 * n3;
-  double* const a_gscr = a_part + bcA * (int64_t)g.npairs * g.S * 4096;
+  DROP_TRY(gram_workspace(ctx, g, "chol.select_chunk", B, small_A, 0, &bcA, &rowsA, &wsA));
+  static const CovPath path = {"select_cross", "select_solve", "select_gram", "select", 128, nullptr};
+  CovChunk a;
+  double* const a_gscr = cov_chunk_carve(&a, wsA, g, D, bcA, true);
   phase_begin(ctx);
   for (int64_t b0 = 0; b0 < B; b0 += bcA) {
     const int bc = (int)(B - b0 < bcA ? B - b0 : bcA);
-    SEL_HIP(hipMemcpyAsync(a_R, R + b0 * n3, bc * n3 * 8, hipMemcpyHostToDevice, st));
-    SEL_TRY(desc_device(ctx, a_R, bc, ts.N, lat, lat_inv, a_xq, a_gq));
-    SEL_TRY(cross_rows_launch(ctx, ts.x, ts.g, ts.M, a_xq, a_gq, bc, rowsA, g.ld, a_nkqq, -1.0, sig, "select_cross"));
-    const int64_t rows = (int64_t)bc * n3, rows_pad = pad_rows128(rows);
-    if (rows_pad > rows) SEL_HIP(hipMemsetAsync(rowsA + rows * g.ld, 0, (rows_pad - rows) * g.ld * 8, st));
-    int slot = ktime_begin(ctx);
-    SEL_TRY(tall_trsm(ctx, ctx->K, rowsA, rows_pad, g.n, g.ld, 0));
-    ktime_end(ctx, slot, "select_solve", (double)g.n * (double)g.n * (double)rows);
-    slot = ktime_begin(ctx);
-    block_gram_launch(ctx, g, rowsA, a_part, bc, false, 0, 0);
-    cov_reduce_launch(ctx, g, a_part, a_nkqq, a_out, bc, 1);
-    ktime_end(ctx, slot, "select_gram", 2.0 * (double)g.ld * (double)n3 * n3 * bc);
-    sa.Sig = a_out; sa.gscr = a_gscr; sa.picked = nullptr; sa.Gout = nullptr; sa.q0 = b0;
-    slot = ktime_begin(ctx);
+    const int64_t rows = (int64_t)bc * n3;
+    DROP_TRY(cov_chunk_step(ctx, g, path, a, rowsA, nullptr, R + b0 * n3, false, bc, lat, lat_inv, 1, a.out));
+    sa.Sig = a.out; sa.gscr = a_gscr; sa.picked = nullptr; sa.Gout = nullptr; sa.q0 = b0;
+    const int slot = ktime_begin(ctx);
     score_launch(ctx, sa, bc, lds, lds_bytes);
     ktime_end(ctx, slot, "select_score", (double)bc * (double)n3 * n3 * n3 / 3.0);
-    SEL_HIP(hipGetLastError());
+    DROP_HIP(hipGetLastError());
     if (joint) {
-      SEL_HIP(hipMemcpyAsync(Wb + b0 * n3 * g.ld, rowsA, rows * g.ld * 8, hipMemcpyDeviceToDevice, st));
-      SEL_HIP(hipMemcpyAsync(Sig + b0 * n3 * n3, a_out, rows * n3 * 8, hipMemcpyDeviceToDevice, st));
-      SEL_HIP(hipMemcpyAsync(xq_all + b0 * D, a_xq, bc * D * 8, hipMemcpyDeviceToDevice, st));
-      SEL_HIP(hipMemcpyAsync(gq_all + 3 * b0 * D, a_gq, bc * D * 24, hipMemcpyDeviceToDevice, st));
+      DROP_HIP(hipMemcpyAsync(Wb + b0 * n3 * g.ld, rowsA, rows * g.ld * 8, hipMemcpyDeviceToDevice, st));
+      DROP_HIP(hipMemcpyAsync(Sig + b0 * n3 * n3, a.out, rows * n3 * 8, hipMemcpyDeviceToDevice, st));
+      DROP_HIP(hipMemcpyAsync(xq_all + b0 * D, a.xq, bc * D * 8, hipMemcpyDeviceToDevice, st));
+      DROP_HIP(hipMemcpyAsync(gq_all + 3 * b0 * D, a.gq, bc * D * 24, hipMemcpyDeviceToDevice, st));
     }
   }
   if (joint && pad_rows128(m_pool) > m_pool)
-    SEL_HIP(hipMemsetAsync(Wb + m_pool * g.ld, 0, (pad_rows128(m_pool) - m_pool) * g.ld * 8, st));
+    DROP_HIP(hipMemsetAsync(Wb + m_pool * g.ld, 0, (pad_rows128(m_pool) - m_pool) * g.ld * 8, st));
 
   // ---- stage B: pick, condition, score again
   std::vector<double> gain((size_t)B);
@@ -399,11 +364,11 @@ extern "C" int gdml_select_points(gdml_ctx* ctx, const double* R, int64_t B, con
       const int slot = ktime_begin(ctx);
       score_launch(ctx, sa, B, lds, lds_bytes);
       ktime_end(ctx, slot, "select_score", (double)(B - t) * (double)n3 * n3 * n3 / 3.0);
-      SEL_HIP(hipGetLastError());
+      DROP_HIP(hipGetLastError());
     }
-    SEL_HIP(hipMemcpyAsync(gain.data(), d_gain, B * 8, hipMemcpyDeviceToHost, st));
-    SEL_HIP(hipMemcpyAsync(flags.data(), d_flags, B * sizeof(int), hipMemcpyDeviceToHost, st));
-    SEL_HIP(hipStreamSynchronize(st));
+    DROP_HIP(hipMemcpyAsync(gain.data(), d_gain, B * 8, hipMemcpyDeviceToHost, st));
+    DROP_HIP(hipMemcpyAsync(flags.data(), d_flags, B * sizeof(int), hipMemcpyDeviceToHost, st));
+    DROP_HIP(hipStreamSynchronize(st));
     for (int64_t q = 0; q < B; ++q)
       if (flags[q] && !picked[q]) {
         if (info) *info = (int)(q + 1);
@@ -425,7 +390,7 @@ extern "C" int gdml_select_points(gdml_ctx* ctx, const double* R, int64_t B, con
     // the picked candidate's block column V_t
     double* const Vt = Vb + t * m_pool * ldc;
     const int64_t qrow0 = best * n3;
-    SEL_TRY(cross_rows_launch(ctx, xq_all + best * D, gq_all + 3 * best * D, 1, xq_all, gq_all, (int)B, Vt, ldc, nullptr, -1.0, sig,
+    DROP_TRY(cross_rows_launch(ctx, xq_all + best * D, gq_all + 3 * best * D, 1, xq_all, gq_all, (int)B, Vt, ldc, nullptr, -1.0, sig,
                               "select_cross"));
     int slot = ktime_begin(ctx);
     ColumnArgs ca;
@@ -434,14 +399,14 @@ extern "C" int gdml_select_points(gdml_ctx* ctx, const double* R, int64_t B, con
     hipLaunchKernelGGL(select_column_kernel, dim3((unsigned)ceil_div(ca.units, 4)), dim3(256), 0, st, ca);
     ctx->launch_counter++;
     ktime_end(ctx, slot, "select_column", (double)m_pool * (double)g.ld * 8.0 * g.nblk);  // bytes of W read, nblk times
-    SEL_HIP(hipGetLastError());
+    DROP_HIP(hipGetLastError());
     // G of the picked candidate: the score kernel on its Sig once more, the factor stored
     sa.Sig = Sig + best * n3 * n3; sa.gscr = gscr_B; sa.picked = nullptr; sa.Gout = Gf; sa.q0 = B;
     slot = ktime_begin(ctx);
     score_launch(ctx, sa, 1, lds, lds_bytes);
     ktime_end(ctx, slot, "select_score", (double)n3 * n3 * n3 / 3.0);
-    SEL_HIP(hipGetLastError());
-    SEL_HIP(hipMemcpyAsync(d_picked + best, &one, sizeof(int), hipMemcpyHostToDevice, st));
+    DROP_HIP(hipGetLastError());
+    DROP_HIP(hipMemcpyAsync(d_picked + best, &one, sizeof(int), hipMemcpyHostToDevice, st));
     slot = ktime_begin(ctx);
     CombineArgs cb;
     cb.part = cpart; cb.V = Vb; cb.Vt = Vt; cb.m_pool = m_pool; cb.qrow0 = qrow0; cb.total = m_pool * n3;
@@ -451,11 +416,9 @@ extern "C" int gdml_select_points(gdml_ctx* ctx, const double* R, int64_t B, con
     hipLaunchKernelGGL(select_downdate_kernel, dim3((unsigned)B), dim3(256), 0, st, Sig, Vt, d_picked, (int)n3, (int)ldc);
     ctx->launch_counter += 3;
     ktime_end(ctx, slot, "select_update", (double)m_pool * (double)n3 * (2.0 * n3 * (t + 1) + (double)n3));
-    SEL_HIP(hipGetLastError());
+    DROP_HIP(hipGetLastError());
   }
-  SEL_TRY(phase_end(ctx, "select"));
-#undef SEL_TRY
-#undef SEL_HIP
+  DROP_TRY(phase_end(ctx, path.phase));
   *n_selected_out = k;
   return drop(GDML_OK);
 }

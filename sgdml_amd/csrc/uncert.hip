@@ -183,12 +183,6 @@ int cross_rows_launch(gdml_ctx* ctx, const double* xt, const double* gt, int64_t
   return rc;
 }
 
-// the same against the resident training set
-static int cross_launch(gdml_ctx* ctx, const double* xq, const double* gq, int bc, double* rows, int64_t ld, double* kqq,
-                        double sgn, double sig) {
-  return cross_rows_launch(ctx, ctx->ts.x, ctx->ts.g, ctx->ts.M, xq, gq, bc, rows, ld, kqq, sgn, sig, "uncert_cross");
-}
-
 // ---- Gram step ---------------------------------------------------------------------------------------------------------
 // Sig_q = (-k_qq) - Z_q Z_q^T: the partial tiles of Z_q Z_q^T come from block_gram_launch (block_gram.hip; a query's rows have
 // no zero prefix, so first = 0), cov_reduce_kernel sums them in the order s = 0 .. S - 1.  The diag_only form runs the same
@@ -236,34 +230,24 @@ static int uncert_check_queries(gdml_ctx* ctx, const char* who, const double* R,
   if (B < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: B < 0", who);
   if ((lat == nullptr) != (lat_inv == nullptr))
     return gdml_fail(ctx, GDML_ERR_INVALID, "lattice and inverse must both be given or both NULL");
-  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "%s: call gdml_train_upload first", who);
   return GDML_OK;
 }
 
-// Work buffers of one batch chunk (the chunk length: option predict.cov_chunk).
-struct UncertPlan {
-  GramSplit g;
-  int N, D;
-  int64_t bc;
-  double *R, *xq, *gq, *nkqq, *part, *out, *rows;
-};
+// Work buffers of one batch chunk
+int64_t cov_chunk_doubles(const GramSplit& g, int64_t D, bool gram) {
+  const int64_t n3 = g.n3;
+  return n3 + 4 * D + 2 * n3 * n3 + (gram ? (int64_t)g.npairs * g.S * 4096 : 0);
+}
 
-static int uncert_plan(gdml_ctx* ctx, int64_t B, bool need_gram, UncertPlan* p) {
-  const TrainSet& ts = ctx->ts;
-  p->N = ts.N; p->D = ts.D;
-  p->g = gram_split(ts.M * 3 * ts.N, 3 * ts.N);
-  const int64_t n3 = p->g.n3;
-  const int64_t small = n3 + 4 * (int64_t)p->D + 2 * n3 * n3 + (need_gram ? (int64_t)p->g.npairs * p->g.S * 4096 : 0);
-  double* ws;
-  GDML_TRY(gram_workspace(ctx, p->g, "predict.cov_chunk", B, small, 0, &p->bc, &p->rows, &ws));
-  const int64_t bc = p->bc;
-  p->R = ws;
-  p->xq = p->R + bc * n3;
-  p->gq = p->xq + bc * p->D;
-  p->nkqq = p->gq + 3 * bc * p->D;
-  p->out = p->nkqq + bc * n3 * n3;
-  p->part = p->out + bc * n3 * n3;
-  return GDML_OK;
+double* cov_chunk_carve(CovChunk* c, double* ws, const GramSplit& g, int64_t D, int64_t bc, bool gram) {
+  const int64_t n3 = g.n3;
+  c->R = ws;
+  c->xq = c->R + bc * n3;
+  c->gq = c->xq + bc * D;
+  c->nkqq = c->gq + 3 * bc * D;
+  c->out = c->nkqq + bc * n3 * n3;
+  c->part = c->out + bc * n3 * n3;
+  return c->part + (gram ? bc * (int64_t)g.npairs * g.S * 4096 : 0);
 }
 
 extern "C" int gdml_uncert_prepare(gdml_ctx* ctx, double sig, double lam, int* info) {
@@ -302,21 +286,27 @@ extern "C" int gdml_uncert_cross(gdml_ctx* ctx, const double* R, int64_t B, cons
                                  double* Kx_out, double* kqq_out) {
   if (!ctx) return GDML_ERR_INVALID;
   GDML_TRY(uncert_check_queries(ctx, "gdml_uncert_cross", R, B, lat, lat_inv));
+  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_uncert_cross: call gdml_train_upload first");
   if (ctx->K_sig <= 0 && !(ctx->model.sig > 0))
     return gdml_fail(ctx, GDML_ERR_STATE, "gdml_uncert_cross: no length scale known (gdml_uncert_prepare or a model upload sets it)");
   if (B == 0) return GDML_OK;
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const double sig = ctx->uncert_ready || ctx->K_sig > 0 ? ctx->K_sig : ctx->model.sig;
-  UncertPlan p;
-  GDML_TRY(uncert_plan(ctx, B, false, &p));
-  const int64_t n3 = p.g.n3, n = p.g.n, ld = p.g.ld;
-  for (int64_t b0 = 0; b0 < B; b0 += p.bc) {
-    const int bc = (int)(B - b0 < p.bc ? B - b0 : p.bc);
+  const TrainSet& ts = ctx->ts;
+  const GramSplit g = gram_split(ts.M * 3 * ts.N, 3 * ts.N);
+  const int64_t n3 = g.n3, n = g.n, ld = g.ld;
+  int64_t bc_max;
+  double *rows, *ws;
+  GDML_TRY(gram_workspace(ctx, g, "predict.cov_chunk", B, cov_chunk_doubles(g, ts.D, false), 0, &bc_max, &rows, &ws));
+  CovChunk p;
+  cov_chunk_carve(&p, ws, g, ts.D, bc_max, false);
+  for (int64_t b0 = 0; b0 < B; b0 += bc_max) {
+    const int bc = (int)(B - b0 < bc_max ? B - b0 : bc_max);
     HIP_CHECK(ctx, hipMemcpyAsync(p.R, R + b0 * n3, bc * n3 * 8, hipMemcpyHostToDevice, ctx->stream));
-    GDML_TRY(desc_device(ctx, p.R, bc, p.N, lat, lat_inv, p.xq, p.gq));
-    GDML_TRY(cross_launch(ctx, p.xq, p.gq, bc, p.rows, ld, p.nkqq, 1.0, sig));
+    GDML_TRY(desc_device(ctx, p.R, bc, ts.N, lat, lat_inv, p.xq, p.gq));
+    GDML_TRY(cross_rows_launch(ctx, ts.x, ts.g, ts.M, p.xq, p.gq, bc, rows, ld, p.nkqq, 1.0, sig, "uncert_cross"));
     if (Kx_out)
-      HIP_CHECK(ctx, hipMemcpy2DAsync(Kx_out + b0 * n3 * n, n * 8, p.rows, ld * 8, n * 8, bc * n3,
+      HIP_CHECK(ctx, hipMemcpy2DAsync(Kx_out + b0 * n3 * n, n * 8, rows, ld * 8, n * 8, bc * n3,
                                       hipMemcpyDeviceToHost, ctx->stream));
     if (kqq_out)
       HIP_CHECK(ctx, hipMemcpyAsync(kqq_out + b0 * n3 * n3, p.nkqq, bc * n3 * n3 * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -325,56 +315,73 @@ extern "C" int gdml_uncert_cross(gdml_ctx* ctx, const double* R, int64_t B, cons
   return GDML_OK;
 }
 
-static int cov_common(gdml_ctx* ctx, const double* R, bool on_device, int64_t B, const double* lat, const double* lat_inv,
-                      int full, double* cov_out) {
-  GDML_TRY(uncert_check_queries(ctx, "gdml_predict_cov", R, B, lat, lat_inv));
-  if (!cov_out) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_cov: cov_out is NULL");
-  if (ctx->K && ctx->K_factored && ctx->K_use_E)
-    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "gdml_predict_cov: the resident factor carries energy-constraint rows");
-  if (!ctx->uncert_ready || !ctx->K || !ctx->K_factored)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_predict_cov: no factor prepared (gdml_uncert_prepare; an assembly since then overwrote it)");
-  if (B == 0) return GDML_OK;
+int cov_chunk_step(gdml_ctx* ctx, const GramSplit& g, const CovPath& path, const CovChunk& c, double* rows, double* fixed,
+                   const double* R, bool R_on_device, int bc, const double* lat, const double* lat_inv, int full, double* d_out) {
+  const TrainSet& ts = ctx->ts;
+  const int64_t n3 = g.n3;
+  if (!R_on_device) {
+    HIP_CHECK(ctx, hipMemcpyAsync(c.R, R, bc * n3 * 8, hipMemcpyHostToDevice, ctx->stream));
+    R = c.R;
+  }
+  GDML_TRY(desc_device(ctx, R, bc, ts.N, lat, lat_inv, c.xq, c.gq));
+  GDML_TRY(cross_rows_launch(ctx, ts.x, ts.g, ts.M, c.xq, c.gq, bc, rows, g.ld, c.nkqq, -1.0, ctx->K_sig, path.t_cross));
+  // Z = (-Kx) L^-T on whole row tiles (the row buffer holds whole 128-row tiles)
+  const int64_t r = (int64_t)bc * n3, r_pad = (r + path.row_pad - 1) / path.row_pad * path.row_pad;
+  if (r_pad > r) HIP_CHECK(ctx, hipMemsetAsync(rows + r * g.ld, 0, (r_pad - r) * g.ld * 8, ctx->stream));
+  const double work = (double)g.n * (double)g.n * (double)r;
+  if (path.solve) {
+    GDML_TRY(path.solve(ctx, g, rows, r_pad, work, fixed));
+  } else {
+    // Right-looking: the rows are few and the factor is long, so every 512-column step updates the whole remaining width in
+    // one launch that fills the chip (the left-looking form of the Nystroem build would run 4 tiles deep products per 128 rows)
+    const int slot = ktime_begin(ctx);
+    GDML_TRY(tall_trsm(ctx, ctx->K, rows, r_pad, g.n, g.ld, 0));
+    ktime_end(ctx, slot, path.t_solve, work);
+  }
+  const int slot = ktime_begin(ctx);
+  block_gram_launch(ctx, g, rows, c.part, bc, !full, 0, 0);
+  cov_reduce_launch(ctx, g, c.part, c.nkqq, d_out, bc, full);
+  ktime_end(ctx, slot, path.t_gram, 2.0 * (double)g.ld * (full ? (double)n3 * n3 : (double)n3) * bc);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? GDML_OK : gdml_fail(ctx, GDML_ERR_HIP, "cov_gram launch: %s", hipGetErrorString(e));
+}
+
+int cov_check(gdml_ctx* ctx, const char* who, const double* R, int64_t B, const double* lat, const double* lat_inv,
+              const double* cov_out, GramSplit* g_out) {
+  GDML_TRY(uncert_check_queries(ctx, who, R, B, lat, lat_inv));
+  if (!cov_out) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: cov_out is NULL", who);
+  return resident_factor_check(ctx, who, true, g_out);
+}
+
+int cov_run(gdml_ctx* ctx, const GramSplit& g, const CovPath& path, const double* R, bool on_device, int64_t B, const double* lat,
+            const double* lat_inv, int full, double* cov_out, int64_t ws_fixed) {
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  UncertPlan p;
-  GDML_TRY(uncert_plan(ctx, B, true, &p));
-  const GramSplit& g = p.g;
-  if (ctx->K_rows != g.n || ctx->K_ld != g.ld)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_predict_cov: the resident factor does not belong to the resident training set");
-  const int64_t n3 = g.n3, per_out = full ? n3 * n3 : n3;
+  const int64_t n3 = g.n3, D = ctx->ts.D, per_out = full ? n3 * n3 : n3;
+  int64_t bc_max;
+  double *rows, *ws;
+  GDML_TRY(gram_workspace(ctx, g, "predict.cov_chunk", B, cov_chunk_doubles(g, D, true), ws_fixed, &bc_max, &rows, &ws));
+  CovChunk c;
+  cov_chunk_carve(&c, ws + ws_fixed, g, D, bc_max, true);
   phase_begin(ctx);
-  for (int64_t b0 = 0; b0 < B; b0 += p.bc) {
-    const int bc = (int)(B - b0 < p.bc ? B - b0 : p.bc);
-    const double* d_R = R + b0 * n3;
+  for (int64_t b0 = 0; b0 < B; b0 += bc_max) {
+    const int bc = (int)(B - b0 < bc_max ? B - b0 : bc_max);
+    double* d_out = on_device ? cov_out + b0 * per_out : c.out;
+    GDML_TRY(cov_chunk_step(ctx, g, path, c, rows, ws, R + b0 * n3, on_device, bc, lat, lat_inv, full, d_out));
     if (!on_device) {
-      HIP_CHECK(ctx, hipMemcpyAsync(p.R, R + b0 * n3, bc * n3 * 8, hipMemcpyHostToDevice, ctx->stream));
-      d_R = p.R;
-    }
-    GDML_TRY(desc_device(ctx, d_R, bc, p.N, lat, lat_inv, p.xq, p.gq));
-    GDML_TRY(cross_launch(ctx, p.xq, p.gq, bc, p.rows, g.ld, p.nkqq, -1.0, ctx->K_sig));
-    // Z = (-Kx) L^-T.  Right-looking: the rows are few and the factor is long, so every 512-column step updates the whole
-    // remaining width in one launch that fills the chip (the left-looking form of the Nystroem build would run 4 tiles deep
-    // products per 128 rows)
-    const int64_t rows = (int64_t)bc * n3, rows_pad = pad_rows128(rows);
-    if (rows_pad > rows)
-      HIP_CHECK(ctx, hipMemsetAsync(p.rows + rows * g.ld, 0, (rows_pad - rows) * g.ld * 8, ctx->stream));
-    int slot = ktime_begin(ctx);
-    GDML_TRY(tall_trsm(ctx, ctx->K, p.rows, rows_pad, g.n, g.ld, 0));
-    ktime_end(ctx, slot, "uncert_solve", (double)g.n * (double)g.n * (double)n3 * bc);
-    slot = ktime_begin(ctx);
-    block_gram_launch(ctx, g, p.rows, p.part, bc, !full, 0, 0);
-    double* d_out = on_device ? cov_out + b0 * per_out : p.out;
-    const int64_t total = bc * per_out;
-    cov_reduce_launch(ctx, g, p.part, p.nkqq, d_out, bc, full);
-    ktime_end(ctx, slot, "uncert_gram", 2.0 * (double)g.ld * (full ? (double)n3 * n3 : (double)n3) * bc);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gdml_fail(ctx, GDML_ERR_HIP, "cov_gram launch: %s", hipGetErrorString(e));
-    if (!on_device) {
-      HIP_CHECK(ctx, hipMemcpyAsync(cov_out + b0 * per_out, p.out, total * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_CHECK(ctx, hipMemcpyAsync(cov_out + b0 * per_out, c.out, bc * per_out * 8, hipMemcpyDeviceToHost, ctx->stream));
       HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
   }
-  GDML_TRY(phase_end(ctx, "uncert"));
-  return GDML_OK;
+  return phase_end(ctx, path.phase);
+}
+
+static int cov_common(gdml_ctx* ctx, const double* R, bool on_device, int64_t B, const double* lat, const double* lat_inv,
+                      int full, double* cov_out) {
+  static const CovPath path = {"uncert_cross", "uncert_solve", "uncert_gram", "uncert", 128, nullptr};
+  GramSplit g;
+  GDML_TRY(cov_check(ctx, "gdml_predict_cov", R, B, lat, lat_inv, cov_out, &g));
+  if (B == 0) return GDML_OK;
+  return cov_run(ctx, g, path, R, on_device, B, lat, lat_inv, full, cov_out);
 }
 
 extern "C" int gdml_predict_cov(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv, int full,

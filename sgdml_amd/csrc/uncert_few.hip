@@ -191,8 +191,11 @@ __global__ void __launch_bounds__(256) few_update_kernel(FewArgs a) {
   }
 }
 
-// X <- X L^-T for the r_pad (a multiple of 64, at most FEW_ROWS) rows of X; inv: ceil(n / 64) * 4096 doubles of workspace
-static int few_solve(gdml_ctx* ctx, const double* L, double* X, int64_t r_pad, int64_t n, int64_t ld, double* inv, double work) {
+// X <- X L^-T for the r_pad (a multiple of 64, at most FEW_ROWS) rows of X against the resident factor; inv: ceil(n / 64) * 4096
+// doubles of workspace (the solve of a CovPath)
+static int few_solve(gdml_ctx* ctx, const GramSplit& g, double* X, int64_t r_pad, double work, double* inv) {
+  const double* L = ctx->K;
+  const int64_t n = g.n, ld = g.ld;
   const bool split = ctx_opt_i(ctx, "predict.cov_few_split_timers", 0) != 0;
   int slot = ktime_begin(ctx);
   hipLaunchKernelGGL(few_inv_kernel, dim3((unsigned)ceil_div(n, 64)), dim3(64), 0, ctx->stream, L, ld, n, inv);
@@ -228,69 +231,16 @@ static int few_solve(gdml_ctx* ctx, const double* L, double* X, int64_t r_pad, i
 
 static int few_common(gdml_ctx* ctx, const double* R, bool on_device, int64_t B, const double* lat, const double* lat_inv, int full,
                       double* cov_out) {
-  const char* who = "gdml_predict_cov_few";
-  if (!R) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: R is NULL", who);
-  if (B < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: B < 0", who);
-  if ((lat == nullptr) != (lat_inv == nullptr))
-    return gdml_fail(ctx, GDML_ERR_INVALID, "lattice and inverse must both be given or both NULL");
-  if (!ctx->ts.x) return gdml_fail(ctx, GDML_ERR_STATE, "%s: call gdml_train_upload first", who);
-  if (!cov_out) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: cov_out is NULL", who);
-  if (ctx->K && ctx->K_factored && ctx->K_use_E)
-    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "%s: the resident factor carries energy-constraint rows", who);
-  if (!ctx->uncert_ready || !ctx->K || !ctx->K_factored)
-    return gdml_fail(ctx, GDML_ERR_STATE, "%s: no factor prepared (gdml_uncert_prepare; an assembly since then overwrote it)", who);
+  static const CovPath path = {"few_cross", "few_solve", "few_gram", "uncert_few", 64, few_solve};
+  GramSplit g;
+  GDML_TRY(cov_check(ctx, "gdml_predict_cov_few", R, B, lat, lat_inv, cov_out, &g));
   if (B == 0) return GDML_OK;
-  const TrainSet& ts = ctx->ts;
-  const int64_t n3 = 3 * (int64_t)ts.N;
   int limit = ctx_opt_i(ctx, "predict.cov_few_rows", FEW_ROWS);
   if (limit > FEW_ROWS) limit = FEW_ROWS;
-  if (B * n3 > limit)  // the batched path itself, with its bits
+  if (B * g.n3 > limit)  // the batched path itself, with its bits
     return on_device ? gdml_predict_cov_dev(ctx, R, B, lat, lat_inv, full, cov_out)
                      : gdml_predict_cov(ctx, R, B, lat, lat_inv, full, cov_out);
-  HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const GramSplit g = gram_split(ts.M * n3, (int)n3);
-  if (ctx->K_rows != g.n || ctx->K_ld != g.ld)
-    return gdml_fail(ctx, GDML_ERR_STATE, "%s: the resident factor does not belong to the resident training set", who);
-  const int64_t D = ts.D, ninv = (int64_t)ceil_div(g.n, 64) * 4096;
-  const int64_t small = n3 + 4 * D + 2 * n3 * n3 + (int64_t)g.npairs * g.S * 4096;
-  int64_t bc_max;
-  double *rows, *ws;
-  GDML_TRY(gram_workspace(ctx, g, "predict.cov_chunk", B, small, ninv, &bc_max, &rows, &ws));
-  double* const inv = ws;
-  double* const dR = inv + ninv;
-  double* const xq = dR + bc_max * n3;
-  double* const gq = xq + bc_max * D;
-  double* const nkqq = gq + 3 * bc_max * D;
-  double* const out = nkqq + bc_max * n3 * n3;
-  double* const part = out + bc_max * n3 * n3;
-  const int64_t per_out = full ? n3 * n3 : n3;
-  phase_begin(ctx);
-  for (int64_t b0 = 0; b0 < B; b0 += bc_max) {
-    const int bc = (int)(B - b0 < bc_max ? B - b0 : bc_max);
-    const double* d_R = R + b0 * n3;
-    if (!on_device) {
-      HIP_CHECK(ctx, hipMemcpyAsync(dR, R + b0 * n3, bc * n3 * 8, hipMemcpyHostToDevice, ctx->stream));
-      d_R = dR;
-    }
-    GDML_TRY(desc_device(ctx, d_R, bc, ts.N, lat, lat_inv, xq, gq));
-    GDML_TRY(cross_rows_launch(ctx, ts.x, ts.g, ts.M, xq, gq, bc, rows, g.ld, nkqq, -1.0, ctx->K_sig, "few_cross"));
-    const int64_t r = (int64_t)bc * n3, r_pad = (r + 63) / 64 * 64;  // (the row buffer holds whole 128-row tiles)
-    if (r_pad > r) HIP_CHECK(ctx, hipMemsetAsync(rows + r * g.ld, 0, (r_pad - r) * g.ld * 8, ctx->stream));
-    GDML_TRY(few_solve(ctx, ctx->K, rows, r_pad, g.n, g.ld, inv, (double)g.n * (double)g.n * (double)n3 * bc));
-    const int slot = ktime_begin(ctx);
-    block_gram_launch(ctx, g, rows, part, bc, !full, 0, 0);
-    double* d_out = on_device ? cov_out + b0 * per_out : out;
-    cov_reduce_launch(ctx, g, part, nkqq, d_out, bc, full);
-    ktime_end(ctx, slot, "few_gram", 2.0 * (double)g.ld * (full ? (double)n3 * n3 : (double)n3) * bc);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gdml_fail(ctx, GDML_ERR_HIP, "cov_gram launch: %s", hipGetErrorString(e));
-    if (!on_device) {
-      HIP_CHECK(ctx, hipMemcpyAsync(cov_out + b0 * per_out, out, bc * per_out * 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-  }
-  GDML_TRY(phase_end(ctx, "uncert_few"));
-  return GDML_OK;
+  return cov_run(ctx, g, path, R, on_device, B, lat, lat_inv, full, cov_out, (int64_t)ceil_div(g.n, 64) * 4096);
 }
 
 extern "C" int gdml_predict_cov_few(gdml_ctx* ctx, const double* R, int64_t B, const double* lat, const double* lat_inv, int full,
