@@ -176,6 +176,10 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *                         gdml_predict_cov; values above GDML_COV_FEW_ROWS count as GDML_COV_FEW_ROWS
  *   predict.cov_few_split_timers (0)  1: under gdml_profile the two per-step kernels of gdml_predict_cov_few are timed one by one
  *                         ("few_diag", "few_upd") instead of the whole solve ("few_solve"); the events slow the solve down
+ *   predict.md_fused (1)          gdml_md_run with 1-8 replicas of a molecule with D <= 256: one launch per step (0: the general
+ *                         route of three pieces per step)
+ *   predict.md_chunk_frames (0)   most recorded frames gdml_md_run queues between two synchronisations (0 = as many as fit into
+ *                         64 MiB); the results do not depend on it
  *   chol.loo_chunk (64)            training points per pass of gdml_loo (their rows of L^-T are 3N n doubles each; fewer when free
  *                         memory is short).  The results do not depend on it
  *   chol.extend_chunk (64)         points per pass of gdml_factor_extend (their 3N rows are assembled, solved and factored together;
@@ -310,6 +314,62 @@ int gdml_predict(gdml_ctx* ctx, const double* R, int64_t B, const double* lat,
  * pointers (hipMalloc'd by the caller or gdml_dev_alloc); nothing crosses PCIe. */
 int gdml_predict_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat,
                      const double* lat_inv, double* E_dev, double* F_dev);
+
+/* Molecular dynamics on the device: B independent replicas of the model's molecule advance n_steps with positions,
+ * velocities and forces resident in device memory; the host sees the recorded frames only.  The reference has no
+ * counterpart (its users drive GDMLPredict.predict from ASE, one host round trip per step).
+ * With a_i = f_scale F'_i / mass[atom(i)] (F' the library's unscaled force, f_scale = std times the caller's unit factor):
+ *   thermostat 0 (NVE, velocity Verlet):  v += dt/2 a(F);  r += dt v;  F = predictor(r);  v += dt/2 a(F)
+ *   thermostat 1 (Langevin, BAOAB):       v += dt/2 a(F);  r += dt/2 v;  v = c1 v + c2 sqrt(kT / m) xi;  r += dt/2 v;
+ *                                         F = predictor(r);  v += dt/2 a(F)       c1 = exp(-gamma dt), c2 = sqrt(1 - c1^2)
+ * Noise: xi are standard normals from a counter-based Philox4x32-10 stream.  Key = (low, high) 32 bits of seed, counter =
+ *   (step low, step high, replica, block); the four 32-bit outputs x0..x3 of a block give the normals of coordinates
+ *   4 block .. 4 block + 3 through two Box-Muller pairs, u = (x + 0.5) 2^-32: (sqrt(-2 ln u0) cos 2 pi u1, ... sin 2 pi u1)
+ *   from (x0, x1) and likewise from (x2, x3).  A value depends on (seed, absolute step, replica, coordinate) only -- not on
+ *   B, the grid, chunking or record_every.  The step index of the first step is step0, so a continued run (R, V from the end
+ *   of the last one, step0 advanced by its n_steps) draws the continuation of the stream.
+ *   gdml_md_noise returns exactly the xi (B,n3) that a Langevin step of index `step` consumes (tests pin the stream with it).
+ * Two routes, the same arithmetic of a step on both:
+ *   single launch (the shapes of predict.fused: D <= 256, B <= 8; option predict.md_fused): ONE kernel per step, modelled on
+ *     the single-launch predictor -- its row loop, row split and reduction order.  The state of step t is read from one half
+ *     of a ping-pong buffer; every workgroup of a replica redoes the kick, drift and noise to hold r(t+1); the replica's last
+ *     workgroup (ticket) sums the partials in a fixed order, back-projects F(t+1), finishes the velocity, sums the kinetic
+ *     energy and writes step t + 1 to the other half and to the frame slot.  The forces of the start geometry come from the
+ *     same kernel.  No persistent kernel, no waiting between workgroups, no graph, no host polling;
+ *   general (every other shape gdml_predict accepts): an elementwise kernel (kick, drift, noise), the device prediction path
+ *     exactly as gdml_predict_dev runs it (same route selection, same kernels) and a second elementwise kernel (kick,
+ *     kinetic energy of each replica, frame write).
+ *   Steps are plain launches queued back to back on the context's stream.  The host synchronises once per chunk of frames
+ *   (at most 64 MiB of frames and 4096 steps; option predict.md_chunk_frames).  The kinetic energy is summed by one fixed
+ *   tree on both routes.
+ * Frame k is the state after step (k + 1) record_every, n_rec = n_steps / record_every: R_rec, V_rec, F_rec (n_rec,B,3N), each
+ *   may be NULL; E_rec (n_rec,B) = E' UNSCALED like gdml_predict, Ekin_rec (n_rec,B) = sum m v^2 / 2.  R and V (B,3N) hold the
+ *   start on entry and the end state on return.  lat / lat_inv: minimum image exactly as the predictor applies it; positions
+ *   are never wrapped.  first_bad_step (B): absolute index of the first step at which a coordinate, velocity, force or energy
+ *   of that replica stopped being finite, -1 = none; checked at every chunk end, the run stops with the chunk.
+ * Bit-identical: on the general route E_rec and F_rec of a frame are what gdml_predict_dev returns for that frame's R_rec
+ *   (same B; on the single-launch route they agree with gdml_predict to its tolerance); on both routes the same call
+ *   repeated; n steps followed by n steps from the end state with step0 + n against 2n steps; any record_every; any chunk size.
+ * fp64 throughout, fixed summation orders, no atomics.  A model must be uploaded (GDML_ERR_STATE; no training-set mode).
+ * GDML_ERR_INVALID before any launch, message in gdml_last_error (ctx may be NULL for these checks; the text then is that
+ *   of gdml_last_error(NULL)): n_steps < 0, record_every < 1, a mass <= 0, dt <= 0, gamma < 0, kT < 0, exactly one of lat /
+ *   lat_inv, a thermostat other than 0 or 1, step0 < 0, N different from the model's. */
+typedef struct gdml_md_params {
+  int64_t B;
+  int N;
+  double dt;
+  const double* mass;    /* (N) */
+  double f_scale;        /* acceleration = f_scale * F' / mass */
+  const double* lat;
+  const double* lat_inv; /* both or neither */
+  int thermostat;        /* 0 none, 1 Langevin (BAOAB) */
+  double gamma, kT;
+  uint64_t seed;
+  int64_t step0;
+} gdml_md_params;
+int gdml_md_run(gdml_ctx* ctx, const gdml_md_params* params, double* R, double* V, int64_t n_steps, int64_t record_every,
+                double* R_rec, double* V_rec, double* F_rec, double* E_rec, double* Ekin_rec, int64_t* first_bad_step);
+int gdml_md_noise(uint64_t seed, int64_t step, int64_t B, int n3, double* xi_out, gdml_ctx* ctx);
 
 /* Strain derivative (virial) of B geometries: what pressure, NPT dynamics, cell relaxation and equation-of-state scans of a
  * periodic model need, and what its forces cannot give (with minimum-image pair vectors sum_i f_i (x) r_i is not the strain

@@ -17,6 +17,15 @@ _vp = C.c_void_p
 PCG_CB = C.CFUNCTYPE(C.c_int, C.c_int64, C.c_double, _vp)
 HOST_COLL_CB = C.CFUNCTYPE(C.c_int, _dp, C.c_int64, _vp)  # gdml_host_allreduce / gdml_host_allgather
 
+
+
+class MDParams(C.Structure):
+    """gdml_md_params (include/gdml_hip.h)."""
+    _fields_ = [('B', C.c_int64), ('N', C.c_int), ('dt', C.c_double), ('mass', _vp), ('f_scale', C.c_double), ('lat', _vp),
+                ('lat_inv', _vp), ('thermostat', C.c_int), ('gamma', C.c_double), ('kT', C.c_double), ('seed', C.c_uint64),
+                ('step0', C.c_int64)]
+
+
 # name -> (restype, argtypes).  Must list every symbol declared in include/gdml_hip.h.
 SIGNATURES = {
     'gdml_abi_version': (C.c_int, []),
@@ -47,6 +56,8 @@ SIGNATURES = {
     'gdml_set_alphas': (C.c_int, [_vp, _vp, _vp]),
     'gdml_predict': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     'gdml_predict_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
+    'gdml_md_run': (C.c_int, [_vp, C.POINTER(MDParams), _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_md_noise': (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int, _vp, _vp]),
     'gdml_predict_virial': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_virial_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
@@ -544,6 +555,42 @@ class Context(object):
             self._check(self._lib.gdml_predict(self._h, _ptr(R[b0:b1]), b1 - b0, _ptr(lat), _ptr(lat_inv), _ptr(Ec),
                                                _ptr(F[b0:b1])))
         return E, F
+
+    def md_run(self, R, V, mass, dt, n_steps, record_every=1, f_scale=1.0, thermostat=0, gamma=0.0, kT=0.0, seed=0, step0=0,
+               lat_and_inv=None, record=('R',)):
+        """gdml_md_run: B replicas (R, V: (B,3N)) advance n_steps on the device.  Returns a dict with the end state 'R_end',
+        'V_end', the frames 'E' (n_rec,B; unscaled E'), 'Ekin' (n_rec,B) and those of 'R', 'V', 'F' (n_rec,B,3N) named in
+        `record`, and 'first_bad_step' (B; -1 = every value stayed finite)."""
+        n3 = 3 * self.model_n_atoms
+        R = np.array(R, dtype=np.float64).reshape(-1, n3)  # copies: the call overwrites them with the end state
+        V = np.array(V, dtype=np.float64).reshape(-1, n3)
+        if V.shape != R.shape:
+            raise ValueError('R and V differ in shape: {} and {}'.format(R.shape, V.shape))
+        B = R.shape[0]
+        mass = f64(mass).ravel()
+        if mass.size != self.model_n_atoms:
+            raise ValueError('{} masses for {} atoms'.format(mass.size, self.model_n_atoms))
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        n_steps, record_every = int(n_steps), int(record_every)
+        n_rec = n_steps // record_every if (n_steps > 0 and record_every > 0) else 0
+        rec = {k: (np.empty((n_rec, B, n3)) if k in record else None) for k in ('R', 'V', 'F')}
+        E, Ek = np.empty((n_rec, B)), np.empty((n_rec, B))
+        bad = np.full(B, -1, dtype=np.int64)
+        prm = MDParams(B, self.model_n_atoms, float(dt), _ptr(mass), float(f_scale), _ptr(lat), _ptr(lat_inv), int(thermostat),
+                       float(gamma), float(kT), int(seed), int(step0))
+        self._check(self._lib.gdml_md_run(self._h, C.byref(prm), _ptr(R), _ptr(V), n_steps, record_every, _ptr(rec['R']),
+                                          _ptr(rec['V']), _ptr(rec['F']), _ptr(E), _ptr(Ek), _ptr(bad)))
+        out = {k: v for k, v in rec.items() if v is not None}
+        out.update(R_end=R, V_end=V, E=E, Ekin=Ek, first_bad_step=bad)
+        return out
+
+    def md_noise(self, seed, step, B, n3):
+        """gdml_md_noise: the standard normals (B,n3) a Langevin step of absolute index `step` consumes."""
+        xi = np.empty((int(B), int(n3)))
+        self._check(self._lib.gdml_md_noise(int(seed), int(step), int(B), int(n3), _ptr(xi), self._h))
+        return xi
 
     def predict_virial(self, R, lat_and_inv=None):
         """Unscaled E' (B,), F (B,3N) and strain derivative W = dE'/d eps (B,3,3) of geometries R (B,3N) (gdml_predict_virial);

@@ -1,0 +1,641 @@
+// On-device molecular dynamics (gdml_md_run, gdml_md_noise; include/gdml_hip.h has the equations): positions, velocities
+// and forces of B independent replicas stay in device memory for the whole run, the host sees recorded frames only.
+//
+// Two routes, the same arithmetic of a step on both, plain launches queued on the context's stream, stream order being the only
+// dependency between steps:
+//   single launch (D <= 256, at most 8 replicas): md_step_kernel, one kernel per step (see there)
+//   general (every other shape), three pieces per step:
+//     md_pre_kernel   half kick, drift (Langevin: half drift, Ornstein-Uhlenbeck step with Philox noise, half drift)
+//     gdml_predict_dev on the new positions -- the library's device prediction path as it is (its route selection, its kernels)
+//     md_post_kernel  second half kick, kinetic energy of each replica by a fixed tree, frame write on a recording step
+// The host synchronises once per chunk of frames (bounded in bytes and in queued steps), copies the chunk out and reads the
+// per-replica "first non-finite step" flags.  fp64 throughout, no atomics on floating-point values: results do not depend on
+// chunking, on record_every or on how a run is cut into continued runs.
+#include <math.h>
+
+#include "common.h"
+
+// ---- Philox4x32-10 (Salmon et al., SC'11), key = (seed lo, seed hi), counter = (step lo, step hi, replica, block) -------------
+struct Philox4 {
+  uint32_t v[4];
+};
+
+__host__ __device__ static inline Philox4 philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2,
+                                                        uint32_t c3) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    const uint32_t n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    const uint32_t n3 = (uint32_t)p0;
+    c0 = n0;
+    c1 = n1;
+    c2 = n2;
+    c3 = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  Philox4 o;
+  o.v[0] = c0;
+  o.v[1] = c1;
+  o.v[2] = c2;
+  o.v[3] = c3;
+  return o;
+}
+
+// standard normal of coordinate `coord` of replica `rep` at absolute step `step`: block = coord / 4, the block's outputs
+// (x0, x1) and (x2, x3) are two Box-Muller pairs, u = (x + 0.5) 2^-32 in (0, 1)
+__device__ static inline double md_normal(uint64_t seed, uint64_t step, uint32_t rep, int64_t coord) {
+  const Philox4 o = philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step, (uint32_t)(step >> 32), rep,
+                                  (uint32_t)(coord >> 2));
+  const int j = (int)(coord & 3);
+  const double u0 = ((double)o.v[j & 2] + 0.5) * 2.3283064365386963e-10;
+  const double u1 = ((double)o.v[(j & 2) + 1] + 0.5) * 2.3283064365386963e-10;
+  const double rad = sqrt(-2.0 * log(u0));
+  const double ang = 6.283185307179586 * u1;
+  return (j & 1) ? rad * sin(ang) : rad * cos(ang);
+}
+
+struct MdConst {
+  int64_t B;
+  int n3;
+  double dt, f_scale, c1, c2, kT;
+  int thermostat;
+  uint64_t seed;
+};
+
+// first half of step `step` for coordinate k of replica b (the same arithmetic on both routes): half kick, drift, and with the
+// thermostat the Ornstein-Uhlenbeck step between two half drifts
+__device__ __forceinline__ void md_first_half(const MdConst& C, double m, double f, int64_t step, int64_t b, int64_t k, double& r,
+                                              double& v) {
+  v = v + 0.5 * C.dt * (C.f_scale * f / m);
+  if (C.thermostat) {
+    r = r + 0.5 * C.dt * v;
+    const double xi = md_normal(C.seed, (uint64_t)step, (uint32_t)b, k);
+    v = C.c1 * v + C.c2 * sqrt(C.kT / m) * xi;
+    r = r + 0.5 * C.dt * v;
+  } else {
+    r = r + C.dt * v;
+  }
+}
+
+// one thread per coordinate: first half of step `step` (absolute index)
+__global__ void __launch_bounds__(256) md_pre_kernel(MdConst C, const double* __restrict__ mass, double* __restrict__ R,
+                                                     double* __restrict__ V, const double* __restrict__ F,
+                                                     int64_t* __restrict__ bad, int64_t step) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= C.B * C.n3) return;
+  const int64_t b = i / C.n3;
+  const int64_t k = i - b * C.n3;
+  double v = V[i], r = R[i];
+  md_first_half(C, mass[k / 3], F[i], step, b, k, r, v);
+  R[i] = r;
+  V[i] = v;
+  // every thread of a replica that finds the flag unset writes the same value: no ordering needed
+  if (!(isfinite(r) && isfinite(v)) && bad[b] < 0) bad[b] = step;
+}
+
+struct MdFrame {
+  double *R, *V, *F, *E, *Ekin;  // slot of the frame to write in the chunk buffers (null: not recorded)
+  int on;
+};
+
+// one workgroup per replica: second half kick, kinetic energy (per-thread partial sums in index order, then a fixed tree),
+// non-finite check of the new forces, frame write
+__global__ void __launch_bounds__(256) md_post_kernel(MdConst C, const double* __restrict__ mass, const double* __restrict__ R,
+                                                      double* __restrict__ V, const double* __restrict__ F,
+                                                      const double* __restrict__ E, double* __restrict__ Ekin,
+                                                      int64_t* __restrict__ bad, int64_t step, MdFrame fr) {
+  __shared__ double red[256];
+  __shared__ int nonfinite;
+  const int64_t b = blockIdx.x;
+  const int64_t o = b * C.n3;
+  const int t = threadIdx.x;
+  if (t == 0) nonfinite = 0;
+  __syncthreads();
+  double ek = 0.0;
+  int nf = 0;
+  for (int k = t; k < C.n3; k += 256) {
+    const double m = mass[k / 3];
+    const double f = F[o + k];
+    const double v = V[o + k] + 0.5 * C.dt * (C.f_scale * f / m);
+    V[o + k] = v;
+    ek += 0.5 * m * v * v;
+    nf |= !(isfinite(v) && isfinite(f));
+    if (fr.on) {
+      if (fr.R) fr.R[o + k] = R[o + k];
+      if (fr.V) fr.V[o + k] = v;
+      if (fr.F) fr.F[o + k] = f;
+    }
+  }
+  red[t] = ek;
+  if (nf) nonfinite = 1;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) red[t] += red[t + s];
+    __syncthreads();
+  }
+  if (t == 0) {
+    const double e = E[b];
+    Ekin[b] = red[0];
+    if ((nonfinite || !isfinite(e)) && bad[b] < 0) bad[b] = step;
+    if (fr.on) {
+      fr.E[b] = e;
+      fr.Ekin[b] = red[0];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Single-launch step for the shapes of the single-launch predictor (D <= 256, B <= 8 replicas): ONE kernel per step, modelled
+// on predict_fused_kernel (predict.hip) -- the same row loop, row split, partial sums and back-projection order -- except that
+//   - the state (R, V, F) of step t comes from device memory (one half of a ping-pong buffer), not from the kernel arguments;
+//   - every workgroup of a replica redoes the cheap first half of the step (md_first_half) to hold r_{t+1} in LDS.
+// grid = (row shares, replicas).  The LAST workgroup of a replica to finish (ticket) sums that replica's partials in a fixed
+// order, forms F_{t+1} = J^T F_x, finishes the velocity, sums the kinetic energy by the tree of md_post_kernel and writes
+// R, V, F, E', E_kin of step t + 1 to the other half of the state buffer (and to the frame slot on a recording step).  No
+// workgroup reads what another workgroup of the same launch writes; stream order is the only dependency between steps.
+// init: no kick and no drift -- the forces of the start geometry by the same arithmetic, so that a continued run starts from
+// the bits the run it continues ended with.
+// ------------------------------------------------------------------------------------------
+#define MD_STEP_MAX_Q 8
+#define MD_STEP_MAX_COORDS 72  // 3 N for D = N (N - 1) / 2 <= 256: N <= 23
+struct MdStepArgs {
+  const double* xp;
+  const double* jap;
+  const double* aE;
+  int64_t MP;
+  int D, N;
+  double sig;
+  int rows_per_wave, init;
+  double* part;       // (B, n_wg, D + 1) workgroup partials: F_x, then E
+  unsigned* counter;  // [q] workgroups of replica q that have finished
+  Lattice L;
+  MdConst C;
+  const double* mass;
+  const double *inR, *inV, *inF;
+  double *outR, *outV, *outF, *outE, *outEk;
+  int64_t* bad;
+  int64_t step;
+  MdFrame fr;
+};
+
+// r_i - r_j (minimum image with a lattice, as desc.hip and predict_fused_kernel form it) from the LDS copy of one replica
+__device__ __forceinline__ void md_pair_diff(const double* r, const Lattice& L, int i, int j, double (&d)[3]) {
+  double d0 = r[3 * i] - r[3 * j], d1 = r[3 * i + 1] - r[3 * j + 1], d2 = r[3 * i + 2] - r[3 * j + 2];
+  if (L.use) {
+    const double c0 = rint(L.inv[0] * d0 + L.inv[1] * d1 + L.inv[2] * d2);
+    const double c1 = rint(L.inv[3] * d0 + L.inv[4] * d1 + L.inv[5] * d2);
+    const double c2 = rint(L.inv[6] * d0 + L.inv[7] * d1 + L.inv[8] * d2);
+    d0 -= L.lat[0] * c0 + L.lat[1] * c1 + L.lat[2] * c2;
+    d1 -= L.lat[3] * c0 + L.lat[4] * c1 + L.lat[5] * c2;
+    d2 -= L.lat[6] * c0 + L.lat[7] * c1 + L.lat[8] * c2;
+  }
+  d[0] = d0; d[1] = d1; d[2] = d2;
+}
+__device__ __forceinline__ void md_pair_of(int k, int& i, int& j) {  // k = i (i - 1) / 2 + j, i > j
+  i = (int)((1.0 + sqrt(1.0 + 8.0 * (double)k)) * 0.5);
+  while (i * (i - 1) / 2 > k) --i;
+  while ((i + 1) * i / 2 <= k) ++i;
+  j = k - i * (i - 1) / 2;
+}
+
+template <int KPL>
+__global__ void __launch_bounds__(256) md_step_kernel(MdStepArgs A) {
+  __shared__ double s_fx[4][KPL * 64];  // per-wavefront F_x; reused by the replica's last workgroup: [0] = its summed F_x
+  __shared__ double s_E[4];
+  __shared__ double s_g[KPL * 64 * 3];
+  __shared__ double s_r[MD_STEP_MAX_COORDS], s_v[MD_STEP_MAX_COORDS];
+  __shared__ double s_red[256];
+  __shared__ double s_Eq;
+  __shared__ unsigned s_ticket;
+  __shared__ int s_nonfinite;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int D = A.D, N = A.N, n3 = 3 * N;
+  const int q = (int)blockIdx.y;  // a workgroup serves ONE replica
+  const double sig = A.sig, inv_sig = 1.0 / sig;
+  const double sqrt5 = 2.23606797749978969641;
+  const double fact = 5.0 / (3.0 * sig * sig * sig);
+  const double dscale = 5.0 / sig;
+  const double inv_3sig = 1.0 / (3.0 * sig);
+
+  // ---- first half of the step, redone by every workgroup of the replica: r_{t+1} and the half-kicked velocity into LDS
+  if (tid < n3) {
+    const int64_t o = (int64_t)q * n3 + tid;
+    double r = A.inR[o], v = A.inV[o];
+    if (!A.init) md_first_half(A.C, A.mass[tid / 3], A.inF[o], A.step, q, tid, r, v);
+    s_r[tid] = r;
+    s_v[tid] = v;
+  }
+  if (tid == 0) s_nonfinite = 0;
+  __syncthreads();
+
+  // ---- descriptor of r_{t+1} (same arithmetic as desc_kernel)
+  double x[KPL], Fx[KPL], E = 0.0;
+#pragma unroll
+  for (int t = 0; t < KPL; ++t) {
+    const int k = lane + 64 * t;
+    double v = 0.0;
+    if (k < D) {
+      int i, j;
+      md_pair_of(k, i, j);
+      double d[3];
+      md_pair_diff(s_r, A.L, i, j, d);
+      v = 1.0 / sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    }
+    x[t] = v;
+    Fx[t] = 0.0;
+  }
+
+  // ---- this wavefront's table rows (the row loop of predict_fused_kernel)
+  const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t r0 = gw * A.rows_per_wave;
+  const int64_t r1 = (r0 + A.rows_per_wave < A.MP) ? r0 + A.rows_per_wave : A.MP;
+  const bool has_aE = A.aE != nullptr;
+  auto load_row = [&](int64_t r, double (&X)[KPL], double (&JA)[KPL], double& ae) {
+#pragma unroll
+    for (int t = 0; t < KPL; ++t) {
+      const int k = lane + 64 * t;
+      const int kc = k < D ? k : D - 1;
+      const double xv = __hip_atomic_load(A.xp + r * D + kc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      const double jv = __hip_atomic_load(A.jap + r * D + kc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      X[t] = (k < D) ? xv : 0.0;
+      JA[t] = (k < D) ? jv : 0.0;
+    }
+    ae = has_aE ? __hip_atomic_load(A.aE + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 0.0;
+  };
+  auto row = [&](const double (&X)[KPL], const double (&JA)[KPL], double ae) {
+    double d[KPL];
+    double s2 = 0.0, sa = 0.0;
+#pragma unroll
+    for (int t = 0; t < KPL; ++t) {
+      d[t] = x[t] - X[t];
+      s2 += d[t] * d[t];
+      sa += d[t] * JA[t];
+    }
+    s2 = wave_sum(s2);
+    sa = wave_sum(sa);
+    const double nrm = sqrt5 * sqrt(s2);
+    const double ex = exp(-nrm * inv_sig);
+    const double b = fact * ex;
+    const double b2 = b * (nrm + sig);
+    double w1 = dscale * sa * b;
+    E += sa * b2;
+    if (has_aE) {
+      w1 += ae * b2;
+      E += ae * (1.0 + (nrm * inv_sig) * (1.0 + nrm * inv_3sig)) * ex;
+    }
+#pragma unroll
+    for (int t = 0; t < KPL; ++t) Fx[t] += w1 * d[t] - b2 * JA[t];
+  };
+  if (r0 < r1) {
+    double X0[KPL], JA0[KPL], X1[KPL], JA1[KPL], ae0, ae1;
+    int64_t r = r0;
+    load_row(r, X0, JA0, ae0);
+    for (; r + 1 < r1; r += 2) {
+      load_row(r + 1, X1, JA1, ae1);
+      row(X0, JA0, ae0);
+      load_row(r + 2 < r1 ? r + 2 : r1 - 1, X0, JA0, ae0);
+      row(X1, JA1, ae1);
+    }
+    if (r < r1) row(X0, JA0, ae0);
+  }
+
+  // ---- the workgroup's four wavefronts -> one partial (padding lanes hold zeros)
+#pragma unroll
+  for (int t = 0; t < KPL; ++t) s_fx[wave][lane + 64 * t] = Fx[t];
+  if (lane == 0) s_E[wave] = E;
+  __syncthreads();
+  const int n_wg = (int)gridDim.x;
+  double* my_part = A.part + ((int64_t)q * n_wg + blockIdx.x) * (D + 1);
+  for (int k = tid; k < D; k += 256) my_part[k] = (s_fx[0][k] + s_fx[1][k]) + (s_fx[2][k] + s_fx[3][k]);
+  if (tid == 0) my_part[D] = (s_E[0] + s_E[1]) + (s_E[2] + s_E[3]);
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) s_ticket = atomicAdd(A.counter + q, 1u);
+  __syncthreads();
+  if (s_ticket != gridDim.x - 1) return;
+
+  // ---- the replica's last workgroup: every partial of this replica is visible
+  __threadfence();
+  double* fxs = &s_fx[0][0];
+  const double* qpart = A.part + (int64_t)q * n_wg * (D + 1);
+  for (int k = tid; k < D + 1; k += 256) {
+    double s = 0.0;
+    for (int w0 = 0; w0 < n_wg; w0 += 8) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int w = w0 + u < n_wg ? w0 + u : n_wg - 1;
+        v[u] = __hip_atomic_load(qpart + (int64_t)w * (D + 1) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (w0 + u < n_wg) s += v[u];
+    }
+    if (k < D) fxs[k] = s;
+    else s_Eq = s;
+  }
+  for (int k = tid; k < D; k += 256) {  // Jacobian entries (r_i - r_j) / d^3  (desc.py:193-205)
+    int i, j;
+    md_pair_of(k, i, j);
+    double d[3];
+    md_pair_diff(s_r, A.L, i, j, d);
+    const double dist = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    const double inv3 = 1.0 / (dist * dist * dist);
+    s_g[k * 3 + 0] = d[0] * inv3;
+    s_g[k * 3 + 1] = d[1] * inv3;
+    s_g[k * 3 + 2] = d[2] * inv3;
+  }
+  __syncthreads();
+  double ek = 0.0;
+  if (tid < n3) {  // F = J_x^T F_x in the order of predict_epilogue_kernel, then the second half kick
+    const int t = tid, a = t / 3, al = t - 3 * a;
+    double f = 0.0;
+    for (int m = 0; m < N; ++m) {
+      if (m == a) continue;
+      const int k = pair_idx(a, m);
+      const double v = s_g[k * 3 + al] * fxs[k];
+      f += (a < m) ? v : -v;
+    }
+    const double m = A.mass[a];
+    const double r = s_r[t];
+    const double v = A.init ? s_v[t] : s_v[t] + 0.5 * A.C.dt * (A.C.f_scale * f / m);
+    ek = 0.5 * m * v * v;
+    const int64_t o = (int64_t)q * n3 + t;
+    A.outR[o] = r;
+    A.outV[o] = v;
+    A.outF[o] = f;
+    if (!(isfinite(r) && isfinite(v) && isfinite(f))) s_nonfinite = 1;
+    if (A.fr.on) {
+      if (A.fr.R) A.fr.R[o] = r;
+      if (A.fr.V) A.fr.V[o] = v;
+      if (A.fr.F) A.fr.F[o] = f;
+    }
+  }
+  s_red[tid] = ek;  // the tree of md_post_kernel: the same kinetic energy bit for bit
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) s_red[tid] += s_red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double e = s_Eq;
+    A.outE[q] = e;
+    A.outEk[q] = s_red[0];
+    if ((s_nonfinite || !isfinite(e)) && A.bad[q] < 0) A.bad[q] = A.step;
+    if (A.fr.on) {
+      A.fr.E[q] = e;
+      A.fr.Ekin[q] = s_red[0];
+    }
+    A.counter[q] = 0u;  // the next launch on the stream finds it reset
+  }
+}
+
+__global__ void __launch_bounds__(256) md_noise_kernel(uint64_t seed, uint64_t step, int64_t B, int n3, double* __restrict__ xi) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * n3) return;
+  const int64_t b = i / n3;
+  xi[i] = md_normal(seed, step, (uint32_t)b, i - b * n3);
+}
+
+__global__ void __launch_bounds__(256) md_fill_i64_kernel(int64_t* p, int64_t n, int64_t v) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+// argument checks shared by every route; ctx may be NULL (the message then goes where gdml_ctx_create's goes)
+static int md_check(gdml_ctx* ctx, const gdml_md_params* p, const double* R, const double* V, int64_t n_steps,
+                    int64_t record_every) {
+  if (!p) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: params is NULL");
+  if (n_steps < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: n_steps < 0");
+  if (record_every < 1) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: record_every < 1");
+  if (p->B < 0 || p->B > 0x7fffffffLL) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: B out of range");
+  if (p->N < 1 || p->N > GDML_MAX_ATOMS) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: N out of range");
+  if (!(p->dt > 0.0) || !isfinite(p->dt)) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: dt must be positive and finite");
+  if (!isfinite(p->f_scale)) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: f_scale is not finite");
+  if (!p->mass) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: mass is NULL");
+  for (int a = 0; a < p->N; ++a)
+    if (!(p->mass[a] > 0.0) || !isfinite(p->mass[a]))
+      return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: mass of atom %d must be positive and finite", a);
+  if ((p->lat == nullptr) != (p->lat_inv == nullptr))
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: lattice and inverse must both be given or both NULL");
+  if (p->thermostat != 0 && p->thermostat != 1)
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: thermostat must be 0 (none) or 1 (Langevin)");
+  if (!(p->gamma >= 0.0) || !isfinite(p->gamma)) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: gamma < 0");
+  if (!(p->kT >= 0.0) || !isfinite(p->kT)) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: kT < 0");
+  if (p->step0 < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: step0 < 0");
+  if (!R || !V) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: R or V is NULL");
+  return GDML_OK;
+}
+
+// most bytes of frames, and most steps, queued between two synchronisations
+static constexpr int64_t MD_CHUNK_BYTES = 64ll << 20;
+static constexpr int64_t MD_CHUNK_STEPS = 4096;
+
+extern "C" int gdml_md_run(gdml_ctx* ctx, const gdml_md_params* p, double* R, double* V, int64_t n_steps, int64_t record_every,
+                           double* R_rec, double* V_rec, double* F_rec, double* E_rec, double* Ekin_rec,
+                           int64_t* first_bad_step) {
+  GDML_TRY(md_check(ctx, p, R, V, n_steps, record_every));
+  if (!ctx) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: ctx is NULL");
+  Model& md = ctx->model;
+  if (!md.xp) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_md_run: upload a model first");
+  if (md.N != p->N) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_run: N = %d but the model has %d atoms", p->N, md.N);
+  const int64_t B = p->B;
+  const int n3 = 3 * p->N;
+  if (first_bad_step)
+    for (int64_t b = 0; b < B; ++b) first_bad_step[b] = -1;
+  if (B == 0) return GDML_OK;
+  HIP_CHECK(ctx, hipSetDevice(ctx->device));
+
+  const int64_t nc = B * n3;
+  const int64_t n_rec = n_steps / record_every;
+  const int n_vec = (R_rec ? 1 : 0) + (V_rec ? 1 : 0) + (F_rec ? 1 : 0);
+  const int64_t frame_bytes = (n_vec * nc + 2 * B) * 8;
+  int64_t chunk_frames = MD_CHUNK_BYTES / frame_bytes;
+  const int64_t opt = (int64_t)ctx_opt(ctx, "predict.md_chunk_frames", 0.0);
+  if (opt > 0 && opt < chunk_frames) chunk_frames = opt;
+  if (chunk_frames < 1) chunk_frames = 1;
+  if (chunk_frames > n_rec) chunk_frames = n_rec;  // 0: nothing is recorded (n_steps < record_every)
+
+  // the single-launch step serves the shapes of the single-launch predictor
+  const int D = md.D;
+  const bool fused = B <= MD_STEP_MAX_Q && D >= 1 && D <= 256 && n3 <= MD_STEP_MAX_COORDS && !ctx->profiling &&
+                     ctx_opt_i(ctx, "predict.md_fused", 1) != 0;
+  const int64_t MP = md.M * md.P;
+  int rows = ctx_opt_i(ctx, "predict.fused_rows", 16);  // the row split of predict_fused: at most 4 x 256 wavefronts
+  if (rows < 2) rows = 2;
+  while ((MP + rows - 1) / rows > 1024) rows *= 2;
+  const int n_wg = (int)(((MP + rows - 1) / rows + 3) / 4);
+
+  // one allocation: mass | two halves of the state (R | V | F | E | Ekin each; the general route works in the first) | bad |
+  // frames of a chunk (R, V, F as requested, E, Ekin) | workgroup partials and tickets of the single-launch step
+  const int64_t n_half = 3 * nc + 2 * B;
+  const int64_t n_state = p->N + 2 * n_half + B;
+  const int64_t n_frames = chunk_frames * (n_vec * nc + 2 * B);
+  const int64_t n_part = fused ? (int64_t)B * n_wg * (D + 1) + MD_STEP_MAX_Q : 0;
+  double* buf = nullptr;
+  GDML_TRY(ctx_alloc(ctx, (void**)&buf, (n_state + n_frames + n_part) * 8));
+  auto drop = [&](int rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)ctx_free(ctx, buf);
+    return rc;
+  };
+  double* d_mass = buf;
+  double* half[2] = {d_mass + p->N, d_mass + p->N + n_half};
+  int cur = 0;  // the half that holds the current state
+  double* d_R = half[0];
+  double* d_V = d_R + nc;
+  double* d_F = d_V + nc;
+  double* d_E = d_F + nc;
+  double* d_Ek = d_E + B;
+  int64_t* d_bad = (int64_t*)(half[1] + n_half);
+  double* fp = half[1] + n_half + B;
+  double* c_R = R_rec ? fp : nullptr;
+  if (R_rec) fp += chunk_frames * nc;
+  double* c_V = V_rec ? fp : nullptr;
+  if (V_rec) fp += chunk_frames * nc;
+  double* c_F = F_rec ? fp : nullptr;
+  if (F_rec) fp += chunk_frames * nc;
+  double* c_E = fp;
+  double* c_Ek = c_E + chunk_frames * B;
+  double* d_part = c_Ek + chunk_frames * B;
+  unsigned* d_counter = (unsigned*)(d_part + (int64_t)B * n_wg * (D + 1));
+
+  hipStream_t st = ctx->stream;
+  DROP_HIP(hipMemcpyAsync(d_mass, p->mass, (size_t)p->N * 8, hipMemcpyHostToDevice, st));
+  DROP_HIP(hipMemcpyAsync(d_R, R, (size_t)nc * 8, hipMemcpyHostToDevice, st));
+  DROP_HIP(hipMemcpyAsync(d_V, V, (size_t)nc * 8, hipMemcpyHostToDevice, st));
+  md_fill_i64_kernel<<<ceil_div(B, 256), 256, 0, st>>>(d_bad, B, -1);
+  if (fused) DROP_HIP(hipMemsetAsync(d_counter, 0, MD_STEP_MAX_Q * 8, st));
+  // the caller's arrays are pageable: the copies above have to be through before they may change
+  DROP_HIP(hipStreamSynchronize(st));
+
+  MdConst C;
+  C.B = B;
+  C.n3 = n3;
+  C.dt = p->dt;
+  C.f_scale = p->f_scale;
+  C.thermostat = p->thermostat;
+  C.c1 = exp(-p->gamma * p->dt);
+  C.c2 = sqrt(1.0 - C.c1 * C.c1);
+  C.kT = p->kT;
+  C.seed = p->seed;
+
+  MdStepArgs S;
+  memset(&S, 0, sizeof(S));
+  if (fused) {
+    S.xp = md.xp; S.jap = md.jap; S.aE = md.has_aE ? md.aE : nullptr;
+    S.MP = MP; S.D = D; S.N = p->N; S.sig = md.sig; S.rows_per_wave = rows;
+    S.part = d_part; S.counter = d_counter; S.C = C; S.mass = d_mass; S.bad = d_bad;
+    if (p->lat && p->lat_inv) {
+      memcpy(S.L.lat, p->lat, sizeof(S.L.lat));
+      memcpy(S.L.inv, p->lat_inv, sizeof(S.L.inv));
+      S.L.use = 1;
+    }
+  }
+  int KPL = 1;
+  while (KPL * 64 < D) KPL <<= 1;
+  // one single-launch step from the current half of the state into the other one
+  auto launch_step = [&](int init, int64_t step, const MdFrame& fr) {
+    const double* in = half[cur];
+    double* out = half[cur ^ 1];
+    S.init = init; S.step = step; S.fr = fr;
+    S.inR = in; S.inV = in + nc; S.inF = in + 2 * nc;
+    S.outR = out; S.outV = out + nc; S.outF = out + 2 * nc; S.outE = out + 3 * nc; S.outEk = out + 3 * nc + B;
+    const dim3 grid((unsigned)n_wg, (unsigned)B);
+    switch (KPL) {
+      case 1: hipLaunchKernelGGL(md_step_kernel<1>, grid, dim3(256), 0, st, S); break;
+      case 2: hipLaunchKernelGGL(md_step_kernel<2>, grid, dim3(256), 0, st, S); break;
+      default: hipLaunchKernelGGL(md_step_kernel<4>, grid, dim3(256), 0, st, S); break;
+    }
+    cur ^= 1;
+  };
+
+  // forces of the start geometry (a continued run recomputes them from R_end by the same arithmetic: the same bits as the run
+  // it continues)
+  if (n_steps > 0) {
+    if (fused) {
+      launch_step(1, p->step0, MdFrame{});
+    } else {
+      ctx->phase_pending.clear();
+      DROP_TRY(gdml_predict_dev(ctx, d_R, B, p->lat, p->lat_inv, d_E, d_F));
+    }
+  }
+
+  std::vector<int64_t> h_bad((size_t)B);
+  const int pre_grid = ceil_div(nc, 256);
+  int64_t t = 0, frames_done = 0;
+  while (t < n_steps) {
+    int64_t in_chunk = 0, steps = 0;
+    while (t < n_steps && steps < MD_CHUNK_STEPS && (chunk_frames == 0 || in_chunk < chunk_frames)) {
+      const int64_t step = p->step0 + t;
+      if (!fused) {
+        md_pre_kernel<<<pre_grid, 256, 0, st>>>(C, d_mass, d_R, d_V, d_F, d_bad, step);
+        // the timer of the previous step's prediction is dropped unread: reading it would wait for that step on the host
+        ctx->phase_pending.clear();
+        DROP_TRY(gdml_predict_dev(ctx, d_R, B, p->lat, p->lat_inv, d_E, d_F));
+      }
+      ++t;
+      ++steps;
+      MdFrame fr = {};
+      if (t % record_every == 0) {
+        fr.on = 1;
+        fr.R = c_R ? c_R + in_chunk * nc : nullptr;
+        fr.V = c_V ? c_V + in_chunk * nc : nullptr;
+        fr.F = c_F ? c_F + in_chunk * nc : nullptr;
+        fr.E = c_E + in_chunk * B;
+        fr.Ekin = c_Ek + in_chunk * B;
+        ++in_chunk;
+      }
+      if (fused)
+        launch_step(0, step, fr);
+      else
+        md_post_kernel<<<(unsigned)B, 256, 0, st>>>(C, d_mass, d_R, d_V, d_F, d_E, d_Ek, d_bad, step, fr);
+    }
+    DROP_HIP(hipGetLastError());
+    if (in_chunk > 0) {
+      const int64_t f0 = frames_done;
+      if (R_rec) DROP_HIP(hipMemcpyAsync(R_rec + f0 * nc, c_R, (size_t)(in_chunk * nc) * 8, hipMemcpyDeviceToHost, st));
+      if (V_rec) DROP_HIP(hipMemcpyAsync(V_rec + f0 * nc, c_V, (size_t)(in_chunk * nc) * 8, hipMemcpyDeviceToHost, st));
+      if (F_rec) DROP_HIP(hipMemcpyAsync(F_rec + f0 * nc, c_F, (size_t)(in_chunk * nc) * 8, hipMemcpyDeviceToHost, st));
+      if (E_rec) DROP_HIP(hipMemcpyAsync(E_rec + f0 * B, c_E, (size_t)(in_chunk * B) * 8, hipMemcpyDeviceToHost, st));
+      if (Ekin_rec) DROP_HIP(hipMemcpyAsync(Ekin_rec + f0 * B, c_Ek, (size_t)(in_chunk * B) * 8, hipMemcpyDeviceToHost, st));
+      frames_done += in_chunk;
+    }
+    DROP_HIP(hipMemcpyAsync(h_bad.data(), d_bad, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    DROP_HIP(hipStreamSynchronize(st));
+    bool any_bad = false;
+    for (int64_t b = 0; b < B; ++b) any_bad |= h_bad[(size_t)b] >= 0;
+    if (any_bad) break;  // the caller reads first_bad_step; frames up to this chunk are written
+  }
+  DROP_HIP(hipMemcpyAsync(R, half[cur], (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(hipMemcpyAsync(V, half[cur] + nc, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(hipStreamSynchronize(st));
+  if (first_bad_step && n_steps > 0) memcpy(first_bad_step, h_bad.data(), (size_t)B * 8);
+  return drop(GDML_OK);
+}
+
+extern "C" int gdml_md_noise(uint64_t seed, int64_t step, int64_t B, int n3, double* xi_out, gdml_ctx* ctx) {
+  if (step < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_noise: step < 0");
+  if (B < 0 || B > 0x7fffffffLL || n3 < 1) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_noise: B or n3 out of range");
+  if (!xi_out) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_noise: xi_out is NULL");
+  if (!ctx) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_md_noise: ctx is NULL");
+  if (B == 0) return GDML_OK;
+  HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const int64_t n = B * n3;
+  double* d = nullptr;
+  GDML_TRY(ctx_alloc(ctx, (void**)&d, n * 8));
+  auto drop = [&](int rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)ctx_free(ctx, d);
+    return rc;
+  };
+  md_noise_kernel<<<ceil_div(n, 256), 256, 0, ctx->stream>>>(seed, (uint64_t)step, B, n3, d);
+  DROP_HIP(hipGetLastError());
+  DROP_HIP(hipMemcpyAsync(xi_out, d, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  DROP_HIP(hipStreamSynchronize(ctx->stream));
+  return drop(GDML_OK);
+}

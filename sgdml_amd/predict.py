@@ -379,6 +379,70 @@ class GDMLPredict(object):
             W = np.ascontiguousarray(W.reshape(-1, 9)[:, [0, 4, 8, 5, 2, 1]])
         return E, F, W
 
+    # ---- molecular dynamics on the device (gdml_md_run, csrc/md.hip)
+
+    def run_md(self, R0, V0, masses, dt, n_steps, record_every=1, thermostat=None, gamma=0.0, kT=0.0, seed=0, step0=0,
+               lattice=None, f_unit=1.0, record=('R', 'E')):
+        """Advance B independent replicas of the molecule for n_steps on the device: velocity Verlet (thermostat=None) or
+        Langevin BAOAB (thermostat='langevin', friction gamma, temperature kT in the units of mass * velocity^2).  R0, V0:
+        (B,3N) or (3N,); masses (N,); accelerations are f_unit * F / mass with F the forces of predict().  seed and the
+        absolute step counter step0 fix the noise (a run continued from R_end, V_end with step0 = step_end draws the
+        continuation of the stream and equals the uninterrupted run bit for bit).  lattice: as in predict().
+        record: which of 'R', 'V', 'F', 'E' to return for every record_every-th step.  Returns a dict: those of 'R', 'V', 'F'
+        (n_rec,B,3N; F scaled by std), 'E_pot' (n_rec,B; E std + c as predict() scales it) and 'E_kin' (n_rec,B), the end
+        state 'R_end', 'V_end' (B,3N) and 'step_end' = step0 + n_steps.  Runs on the predictor's first device.
+        ValueError for non-finite or misshapen input before anything is launched; FloatingPointError naming replica and step
+        when a trajectory stops being finite."""
+        n3 = 3 * self.n_atoms
+        R0 = np.asarray(R0, dtype=np.float64)
+        V0 = np.asarray(V0, dtype=np.float64)
+        if R0.ndim == 1:
+            R0 = R0[None, :]
+        if V0.ndim == 1:
+            V0 = V0[None, :]
+        if R0.ndim == 3:
+            R0 = R0.reshape(R0.shape[0], -1)
+        if V0.ndim == 3:
+            V0 = V0.reshape(V0.shape[0], -1)
+        if R0.ndim != 2 or R0.shape[1] != n3:
+            raise ValueError('R0 must be (B, {}) for this model, got shape {}'.format(n3, R0.shape))
+        if V0.shape != R0.shape:
+            raise ValueError('V0 must have the shape of R0 {}, got {}'.format(R0.shape, V0.shape))
+        masses = np.asarray(masses, dtype=np.float64)
+        if masses.shape != (self.n_atoms,):
+            raise ValueError('masses must be ({},), got shape {}'.format(self.n_atoms, masses.shape))
+        if not (np.isfinite(R0).all() and np.isfinite(V0).all() and np.isfinite(masses).all()):
+            raise ValueError('R0, V0 and masses must be finite')
+        for name, val in (('dt', dt), ('gamma', gamma), ('kT', kT), ('f_unit', f_unit)):
+            if not np.isfinite(val):
+                raise ValueError('{} must be finite'.format(name))
+        if thermostat not in (None, 'langevin'):
+            raise ValueError("thermostat must be None or 'langevin', got {!r}".format(thermostat))
+        record = (record,) if isinstance(record, str) else tuple(record)
+        for k in record:
+            if k not in ('R', 'V', 'F', 'E'):
+                raise ValueError("record names an unknown field {!r} (known: 'R', 'V', 'F', 'E')".format(k))
+        seed, step0 = int(seed), int(step0)
+        if not 0 <= seed < 2**64:
+            raise ValueError('seed must fit into 64 unsigned bits')
+        lat_and_inv = self._lat_and_inv(lattice)
+        out = self._ctx.md_run(R0, V0, masses, dt, n_steps, record_every, f_scale=self.std * float(f_unit),
+                               thermostat=0 if thermostat is None else 1, gamma=gamma, kT=kT, seed=seed, step0=step0,
+                               lat_and_inv=lat_and_inv, record=record)
+        bad = out.pop('first_bad_step')
+        if (bad >= 0).any():
+            b = int(np.argmax(bad >= 0))
+            raise FloatingPointError('replica {} stopped being finite at step {}'.format(b, int(bad[b])))
+        if 'F' in out:
+            out['F'] *= self.std
+        E = out.pop('E')
+        E *= self.std
+        E += self.c
+        out['E_pot'] = E
+        out['E_kin'] = out.pop('Ekin')
+        out['step_end'] = step0 + int(n_steps)
+        return out
+
     # ---- posterior force covariance (csrc/uncert.hip)
 
     def prepare_uncertainty(self, R_train, F_train=None):
