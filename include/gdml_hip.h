@@ -178,8 +178,10 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *                         ("few_diag", "few_upd") instead of the whole solve ("few_solve"); the events slow the solve down
  *   predict.md_fused (1)          gdml_md_run with 1-8 replicas of a molecule with D <= 256: one launch per step (0: the general
  *                         route of three pieces per step)
- *   predict.md_chunk_frames (0)   most recorded frames gdml_md_run queues between two synchronisations (0 = as many as fit into
- *                         64 MiB); the results do not depend on it
+ *   predict.md_chunk_frames (0)   most recorded frames gdml_md_run and gdml_pimd_run queue between two synchronisations (0 = as
+ *                         many as fit into 64 MiB); the results do not depend on it
+ *   predict.pimd_tile (0)         coordinates per workgroup of gdml_pimd_run's first kernel: 0 = 64 up to 64 beads and 32 beyond,
+ *                         32 = always 32.  The results do not depend on it
  *   chol.loo_chunk (64)            training points per pass of gdml_loo (their rows of L^-T are 3N n doubles each; fewer when free
  *                         memory is short).  The results do not depend on it
  *   chol.extend_chunk (64)         points per pass of gdml_factor_extend (their 3N rows are assembled, solved and factored together;
@@ -370,6 +372,68 @@ typedef struct gdml_md_params {
 int gdml_md_run(gdml_ctx* ctx, const gdml_md_params* params, double* R, double* V, int64_t n_steps, int64_t record_every,
                 double* R_rec, double* V_rec, double* F_rec, double* E_rec, double* Ekin_rec, int64_t* first_bad_step);
 int gdml_md_noise(uint64_t seed, int64_t step, int64_t B, int n3, double* xi_out, gdml_ctx* ctx);
+
+/* Path-integral molecular dynamics on the device: B independent ring polymers of P = beads replicas of the model's molecule
+ * (nuclear quantum effects), state (B,P,3N) resident in device memory like gdml_md_run's.  The reference has no counterpart
+ * (its users drive i-PI or ASE, one host round trip per bead and step).
+ * Hamiltonian, sampled at the bead temperature P kT with omega_P = P kT / hbar (hbar in the caller's units):
+ *   H_P = sum_j [ m v_j^2 / 2 + m omega_P^2 (r_j - r_{j+1})^2 / 2 + f_unit E(r_j) ],   r_{P+1} = r_1
+ *   every bead feels the full physical force, a_j = f_scale F'(r_j) / mass[atom], exactly as in gdml_md_run.
+ * Normal modes: the orthonormal real DFT over the bead index, C[j][k], j, k = 0 .. P-1,
+ *   k = 0: 1 / sqrt P;   0 < 2k < P: sqrt(2/P) cos(2 pi j k / P);   2k = P: (-1)^j / sqrt P;   2k > P: sqrt(2/P) sin(2 pi j k / P)
+ *   with frequencies omega_k = 2 omega_P sin(k pi / P).  C is built on the host in fp64 and uploaded once per call; the
+ *   transform is a dense P x P product per coordinate summed in index order (no FFT: a fixed order keeps runs reproducible);
+ *   the internal modes (k > 0, columns that sum to zero) are formed from r_j - r_0 and v_j - v_0, so that nothing cancels
+ *   against |r| and a collapsed ring (all beads equal) has internal modes that are exactly zero and stays collapsed under RPMD.
+ *   gdml_pimd_modes returns the matrix and frequencies a run uses; it needs neither a context nor a device.
+ * One step of absolute index s (BAOAB with the drift replaced by the exact free ring-polymer flow):
+ *   v_j += dt/2 a_j;   (q~, v~) = C^T (r, v);   flow;   (r, v) = C (q~, v~);   F = predictor(all B P geometries);   v_j += dt/2 a_j
+ *   flow over tau:  q~' = cos(w_k tau) q~ + sin(w_k tau) / w_k v~,  v~' = -w_k sin(w_k tau) q~ + cos(w_k tau) v~  (w_k = 0: q~' = q~ + tau v~)
+ *   thermostat 0 (RPMD, microcanonical): one flow with tau = dt, no noise
+ *   thermostat 1 (PILE-L): flow dt/2;  v~ = c1_k v~ + c2_k sqrt(P kT / m) xi;  flow dt/2;   c1_k = exp(-gamma_k dt), c2_k = sqrt(1 - c1_k^2),
+ *     gamma_0 = gamma_centroid (0: the centroid is not thermostatted, T-RPMD), gamma_k = pile_lambda 2 omega_k for k > 0
+ *     (pile_lambda = 1: Ceriotti, Parrinello, Markland, Manolopoulos, J. Chem. Phys. 133, 124104 (2010)).
+ * Noise: xi of (ring b, mode k, coordinate c) at step s is gdml_md_run's stream with the replica index b P + k -- drawn in
+ *   mode space, a function of (seed, absolute step, ring, mode, coordinate) and of P only.  With P = 1 it is gdml_md_run's.
+ * Three pieces per step, stream order the only dependency: a kernel whose workgroups each own all beads of a tile of
+ *   coordinates of one ring (kick, transform, flow, thermostat, transform back in LDS; 32 P W bytes for a tile of W = 64
+ *   coordinates, W = 32 beyond 64 beads; option predict.pimd_tile = 32 selects the narrow tile for any P, same bits), the
+ *   device prediction path as gdml_predict_dev runs it for B P geometries, and a kernel with one workgroup per ring (kick,
+ *   centroid, ring quantities, frame write).  Chunks as in gdml_md_run (64 MiB of frames, 4096 steps, predict.md_chunk_frames).
+ * R and V (B,P,3N) hold the start on entry and the end state on return.  Frame k is the state after step (k + 1) record_every:
+ *   R_rec, V_rec, F_rec (n_rec,B,P,3N), E_rec (n_rec,B,P) = E' of every bead UNSCALED, Rc_rec (n_rec,B,3N) = the bead average
+ *   r_c; each may be NULL.  ring_rec (n_rec,B,5), every sum in a fixed order (per-thread partial sums in index order, then
+ *   gdml_md_run's 256-slot tree; no floating-point atomics):
+ *     [0] E_pot    = (1/P) sum_j E'(r_j)                                   UNSCALED like gdml_predict
+ *     [1] E_kin    = sum_j sum m v_j^2 / 2                                 (equipartition: 3N P  P kT / 2)
+ *     [2] E_spring = sum_j sum m omega_P^2 (r_j - r_{j+1})^2 / 2
+ *     [3] K_cv     = (3N/2) kT - f_scale / (2P) sum_j (r_j - r_c) . F'_j   centroid-virial kinetic-energy estimator
+ *     [4] K_prim   = (3N P / 2) kT - E_spring / P                          primitive estimator
+ * lat / lat_inv: the predictor's minimum image only; beads are never wrapped.  first_bad_step (B): as in gdml_md_run, per ring;
+ *   a ring whose E_kin, E_spring or virial sum overflows counts as non-finite too.
+ * Bit-identical: E_rec and F_rec of a frame are what gdml_predict_dev returns for that frame's R_rec as B P geometries; the
+ *   same call repeated; n + n continued steps (step0 advanced) against 2n; any record_every, chunk size and tile width.
+ * GDML_ERR_INVALID before any launch (ctx may be NULL for these checks): everything gdml_md_run rejects (gamma_centroid < 0
+ *   in gamma's place), beads outside 1 .. 128, hbar <= 0 or not finite, kT <= 0 with beads > 1, pile_lambda <= 0,
+ *   B beads >= 2^31. */
+typedef struct gdml_pimd_params {
+  int64_t B;
+  int N;
+  int beads;
+  double dt;
+  const double* mass;    /* (N) */
+  double f_scale;        /* acceleration = f_scale * F' / mass */
+  const double* lat;
+  const double* lat_inv; /* both or neither */
+  int thermostat;        /* 0 none (RPMD), 1 PILE-L */
+  double gamma_centroid, pile_lambda, kT, hbar;
+  uint64_t seed;
+  int64_t step0;
+} gdml_pimd_params;      /* 112 bytes */
+int gdml_pimd_run(gdml_ctx* ctx, const gdml_pimd_params* params, double* R, double* V, int64_t n_steps, int64_t record_every,
+                  double* R_rec, double* V_rec, double* F_rec, double* E_rec, double* Rc_rec, double* ring_rec,
+                  int64_t* first_bad_step);
+int gdml_pimd_modes(int beads, double kT, double hbar, double* C /* (P,P) row j, column k */, double* omega /* (P) */);
 
 /* Strain derivative (virial) of B geometries: what pressure, NPT dynamics, cell relaxation and equation-of-state scans of a
  * periodic model need, and what its forces cannot give (with minimum-image pair vectors sum_i f_i (x) r_i is not the strain

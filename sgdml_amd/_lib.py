@@ -26,6 +26,13 @@ class MDParams(C.Structure):
                 ('step0', C.c_int64)]
 
 
+class PIMDParams(C.Structure):
+    """gdml_pimd_params (include/gdml_hip.h)."""
+    _fields_ = [('B', C.c_int64), ('N', C.c_int), ('beads', C.c_int), ('dt', C.c_double), ('mass', _vp), ('f_scale', C.c_double),
+                ('lat', _vp), ('lat_inv', _vp), ('thermostat', C.c_int), ('gamma_centroid', C.c_double),
+                ('pile_lambda', C.c_double), ('kT', C.c_double), ('hbar', C.c_double), ('seed', C.c_uint64), ('step0', C.c_int64)]
+
+
 # name -> (restype, argtypes).  Must list every symbol declared in include/gdml_hip.h.
 SIGNATURES = {
     'gdml_abi_version': (C.c_int, []),
@@ -58,6 +65,8 @@ SIGNATURES = {
     'gdml_predict_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     'gdml_md_run': (C.c_int, [_vp, C.POINTER(MDParams), _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gdml_md_noise': (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int, _vp, _vp]),
+    'gdml_pimd_run': (C.c_int, [_vp, C.POINTER(PIMDParams), _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_pimd_modes': (C.c_int, [C.c_int, C.c_double, C.c_double, _vp, _vp]),
     'gdml_predict_virial': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_virial_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
@@ -591,6 +600,50 @@ class Context(object):
         xi = np.empty((int(B), int(n3)))
         self._check(self._lib.gdml_md_noise(int(seed), int(step), int(B), int(n3), _ptr(xi), self._h))
         return xi
+
+    def pimd_run(self, R, V, mass, dt, n_steps, beads, kT, hbar, record_every=1, f_scale=1.0, thermostat=0, gamma_centroid=0.0,
+                 pile_lambda=1.0, seed=0, step0=0, lat_and_inv=None, record=('Rc', 'E')):
+        """gdml_pimd_run: B rings of `beads` beads (R, V: (B,P,3N)) advance n_steps on the device.  Returns a dict with the end
+        state 'R_end', 'V_end', the frames 'ring' (n_rec,B,5: E_pot unscaled, E_kin, E_spring, K_cv, K_prim), those of 'R', 'V',
+        'F' (n_rec,B,P,3N), 'E' (n_rec,B,P; unscaled E') and 'Rc' (n_rec,B,3N) named in `record`, and 'first_bad_step' (B)."""
+        n3, P = 3 * self.model_n_atoms, int(beads)
+        if P < 1:
+            raise ValueError('beads must be at least 1, got {}'.format(beads))
+        R = np.array(R, dtype=np.float64).reshape(-1, P, n3)  # copies: the call overwrites them with the end state
+        V = np.array(V, dtype=np.float64).reshape(-1, P, n3)
+        if V.shape != R.shape:
+            raise ValueError('R and V differ in shape: {} and {}'.format(R.shape, V.shape))
+        B = R.shape[0]
+        mass = f64(mass).ravel()
+        if mass.size != self.model_n_atoms:
+            raise ValueError('{} masses for {} atoms'.format(mass.size, self.model_n_atoms))
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        n_steps, record_every = int(n_steps), int(record_every)
+        n_rec = n_steps // record_every if (n_steps > 0 and record_every > 0) else 0
+        shapes = {'R': (n_rec, B, P, n3), 'V': (n_rec, B, P, n3), 'F': (n_rec, B, P, n3), 'E': (n_rec, B, P), 'Rc': (n_rec, B, n3)}
+        rec = {k: (np.empty(shp) if k in record else None) for k, shp in shapes.items()}
+        ring = np.empty((n_rec, B, 5))
+        bad = np.full(B, -1, dtype=np.int64)
+        prm = PIMDParams(B, self.model_n_atoms, P, float(dt), _ptr(mass), float(f_scale), _ptr(lat), _ptr(lat_inv),
+                         int(thermostat), float(gamma_centroid), float(pile_lambda), float(kT), float(hbar), int(seed), int(step0))
+        self._check(self._lib.gdml_pimd_run(self._h, C.byref(prm), _ptr(R), _ptr(V), n_steps, record_every, _ptr(rec['R']),
+                                            _ptr(rec['V']), _ptr(rec['F']), _ptr(rec['E']), _ptr(rec['Rc']), _ptr(ring),
+                                            _ptr(bad)))
+        out = {k: v for k, v in rec.items() if v is not None}
+        out.update(R_end=R, V_end=V, ring=ring, first_bad_step=bad)
+        return out
+
+    @staticmethod
+    def pimd_modes(beads, kT, hbar):
+        """gdml_pimd_modes: the normal-mode matrix C (P,P; row = bead j, column = mode k) and the mode frequencies (P,) a ring
+        of `beads` beads uses.  Host only: no context, no device."""
+        lib, P = load(), int(beads)
+        Cm, omega = np.empty((max(P, 0), max(P, 0))), np.empty(max(P, 0))
+        if lib.gdml_pimd_modes(P, float(kT), float(hbar), _ptr(Cm), _ptr(omega)) != GDML_OK:
+            raise ValueError(lib.gdml_last_error(None).decode())
+        return Cm, omega
 
     def predict_virial(self, R, lat_and_inv=None):
         """Unscaled E' (B,), F (B,3N) and strain derivative W = dE'/d eps (B,3,3) of geometries R (B,3N) (gdml_predict_virial);

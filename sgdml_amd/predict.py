@@ -443,6 +443,79 @@ class GDMLPredict(object):
         out['step_end'] = step0 + int(n_steps)
         return out
 
+    # ---- path-integral molecular dynamics on the device (gdml_pimd_run, csrc/md.hip)
+
+    def run_pimd(self, R0, V0, masses, dt, n_steps, beads, kT, hbar, record_every=1, thermostat=None, gamma_centroid=0.0,
+                 pile_lambda=1.0, seed=0, step0=0, lattice=None, f_unit=1.0, record=('Rc', 'E')):
+        """Advance B independent ring polymers of `beads` beads for n_steps on the device (nuclear quantum effects): ring-polymer
+        MD with the exact free-ring flow (thermostat=None) or the same with the PILE-L thermostat in normal-mode space
+        (thermostat='pile': friction pile_lambda * 2 omega_k on the internal modes, gamma_centroid on the centroid, 0 leaving
+        it unthermostatted).  kT is the physical temperature in units of mass * velocity^2 (the beads are sampled at
+        beads * kT), hbar Planck's constant over 2 pi in the caller's units.  R0, V0: (B,P,3N), or (B,3N) / (3N,) for a
+        collapsed ring (every bead starts there); masses (N,); accelerations are f_unit * F / mass.  seed, step0, lattice,
+        record_every: as in run_md().  record: which of 'R', 'V', 'F', 'E' (per bead) and 'Rc' (centroids) to return.
+        Returns a dict: those of 'R', 'V', 'F' (n_rec,B,P,3N; F scaled by std), 'E' (n_rec,B,P; E std + c), 'Rc' (n_rec,B,3N);
+        always 'E_pot' (n_rec,B; the bead average, E std + c), 'E_kin', 'E_spring', 'K_cv', 'K_prim' (n_rec,B; the
+        centroid-virial and primitive kinetic-energy estimators, in the caller's kinetic units), the end state 'R_end', 'V_end'
+        (B,P,3N) and 'step_end'.  Runs on the predictor's first device.  ValueError for non-finite or misshapen input before
+        anything is launched; FloatingPointError naming ring and step when a trajectory stops being finite."""
+        n3 = 3 * self.n_atoms
+        if isinstance(beads, bool) or int(beads) != beads or not 1 <= int(beads) <= 128:
+            raise ValueError('beads must be an integer from 1 to 128, got {!r}'.format(beads))
+        P = int(beads)
+
+        def ring(A, name):
+            A = np.asarray(A, dtype=np.float64)
+            if A.ndim == 1:
+                A = A[None, :]
+            if A.ndim == 2 and A.shape[1] == n3:  # a collapsed ring: every bead starts here
+                A = np.repeat(A[:, None, :], P, axis=1)
+            if A.ndim != 3 or A.shape[1:] != (P, n3):
+                raise ValueError('{} must be (B, {}, {}), (B, {}) or ({},) for this model, got shape {}'.format(
+                    name, P, n3, n3, n3, A.shape))
+            return np.ascontiguousarray(A)
+
+        R0, V0 = ring(R0, 'R0'), ring(V0, 'V0')
+        if V0.shape != R0.shape:
+            raise ValueError('V0 must have the shape of R0 {}, got {}'.format(R0.shape, V0.shape))
+        masses = np.asarray(masses, dtype=np.float64)
+        if masses.shape != (self.n_atoms,):
+            raise ValueError('masses must be ({},), got shape {}'.format(self.n_atoms, masses.shape))
+        if not (np.isfinite(R0).all() and np.isfinite(V0).all() and np.isfinite(masses).all()):
+            raise ValueError('R0, V0 and masses must be finite')
+        for name, val in (('dt', dt), ('gamma_centroid', gamma_centroid), ('pile_lambda', pile_lambda), ('kT', kT), ('hbar', hbar),
+                          ('f_unit', f_unit)):
+            if not np.isfinite(val):
+                raise ValueError('{} must be finite'.format(name))
+        if thermostat not in (None, 'pile'):
+            raise ValueError("thermostat must be None or 'pile', got {!r}".format(thermostat))
+        record = (record,) if isinstance(record, str) else tuple(record)
+        for k in record:
+            if k not in ('R', 'V', 'F', 'E', 'Rc'):
+                raise ValueError("record names an unknown field {!r} (known: 'R', 'V', 'F', 'E', 'Rc')".format(k))
+        seed, step0 = int(seed), int(step0)
+        if not 0 <= seed < 2**64:
+            raise ValueError('seed must fit into 64 unsigned bits')
+        lat_and_inv = self._lat_and_inv(lattice)
+        out = self._ctx.pimd_run(R0, V0, masses, dt, n_steps, P, kT, hbar, record_every, f_scale=self.std * float(f_unit),
+                                 thermostat=0 if thermostat is None else 1, gamma_centroid=gamma_centroid,
+                                 pile_lambda=pile_lambda, seed=seed, step0=step0, lat_and_inv=lat_and_inv, record=record)
+        bad = out.pop('first_bad_step')
+        if (bad >= 0).any():
+            b = int(np.argmax(bad >= 0))
+            raise FloatingPointError('ring {} stopped being finite at step {}'.format(b, int(bad[b])))
+        if 'F' in out:
+            out['F'] *= self.std
+        if 'E' in out:
+            out['E'] *= self.std
+            out['E'] += self.c
+        q = out.pop('ring')
+        out['E_pot'] = q[:, :, 0] * self.std + self.c
+        for i, k in enumerate(('E_kin', 'E_spring', 'K_cv', 'K_prim')):
+            out[k] = np.ascontiguousarray(q[:, :, i + 1])
+        out['step_end'] = step0 + int(n_steps)
+        return out
+
     # ---- posterior force covariance (csrc/uncert.hip)
 
     def prepare_uncertainty(self, R_train, F_train=None):

@@ -1,0 +1,295 @@
+"""Path-integral MD on the GPU (gdml_pimd_run, csrc/md.hip; GDMLPredict.run_pimd): against the NumPy restatement
+(tests/_pimd_ref.py), recorded frames against predict(), determinism, restart, record_every, chunking and tile width bit for
+bit, the one-bead ring against run_md, independent rings, conservation laws and error paths.
+
+Common settings: kT = 0.05, hbar = 2 P kT dt (omega_max dt = 1: the spring rotation is a real rotation, a wrong transform
+cannot hide behind omega dt << 1), centroid friction 0.5, unequal masses linspace(1, 2, N) (a tile of 64 coordinates is no
+multiple of 3: the atom of a coordinate has to come from its global index)."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import _md_ref as mr  # noqa: E402
+import _pimd_ref as pr  # noqa: E402
+from sgdml_amd.predict import GDMLPredict  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+KT = 0.05
+PILE = dict(thermostat='pile', gamma_centroid=0.5, seed=77)
+THERMO = {'nve': {}, 'pile': PILE}
+FIELDS = ('R', 'V', 'E') + pr.RING
+ALL = ('R', 'V', 'F', 'E', 'Rc')
+# (fixture, beads, rings, steps).  n100_m3 has 300 coordinates: several tiles and a ragged last one
+CASES = [('n6_p1', 3, 2, 30), ('n6_p1', 4, 2, 30), ('n5_p4', 2, 2, 30), ('n10_p2_pbc', 2, 2, 30), ('cfg1_n21_m100', 8, 1, 30),
+         ('cfg1_n21_m100', 16, 1, 10), ('n100_m3', 4, 1, 30)]
+
+
+def _setup(name, P, B, unit_masses=False):
+    model, R0, V0 = pr.start(name, B, P)
+    N = R0.shape[2] // 3
+    masses = np.ones(N) if unit_masses else np.linspace(1.0, 2.0, N)
+    ring = dict(beads=P, kT=KT, hbar=2 * P * KT * mr.DT[name])
+    return model, R0, V0, masses, ring
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name, P, B, n, thermo, unit_masses=False):
+    """Restated trajectory and its sensitivity to the predictor's agreed error: the largest deviation, per field, of a second
+    restated run whose forces carry independent noise of 1e-10 max|F| (tests/test_md_gpu.py's rule).  Computed once per
+    session, only read."""
+    model, R0, V0, masses, ring = _setup(name, P, B, unit_masses)
+    kw = dict(ring, **THERMO[thermo])
+    clean = pr.run(mr.force_fn(model), R0, V0, masses, mr.DT[name], n, **kw)
+    noisy = pr.run(mr.force_fn(model, rel_noise=1e-10, seed=1), R0, V0, masses, mr.DT[name], n, **kw)
+    dev = {k: np.abs(clean[k] - noisy[k]).max() for k in FIELDS}
+    for a in clean.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return clean, dev
+
+
+def _same(a, b, keys=None):
+    keys = keys or [k for k in a if isinstance(a[k], np.ndarray)]
+    return all(np.array_equal(a[k], b[k]) for k in keys) and a['step_end'] == b['step_end']
+
+
+# ---- 1. against the restatement
+
+@pytest.mark.parametrize('thermo', ['nve', 'pile'])
+@pytest.mark.parametrize('name,P,B,n', CASES)
+def test_trajectory_matches_restatement(name, P, B, n, thermo):
+    """R, V, per-bead E and the five ring quantities of every frame.  Tolerance: ten times the restatement's own sensitivity
+    to force errors of 1e-10 max|F|."""
+    clean, dev = _reference(name, P, B, n, thermo)
+    model, R0, V0, masses, ring = _setup(name, P, B)
+    pred = GDMLPredict(model)
+    out = pred.run_pimd(R0, V0, masses, mr.DT[name], n, record=ALL, **dict(ring, **THERMO[thermo]))
+    assert out['step_end'] == n and out['R'].shape == (n, B, P, R0.shape[2]) and out['E_pot'].shape == (n, B)
+    err = {k: np.abs(out[k] - clean[k]).max() for k in FIELDS}
+    for k in FIELDS:
+        print('%s P=%d %s %s: sensitivity %.2e, error %.2e' % (name, P, thermo, k, dev[k], err[k]))
+    for k in FIELDS:
+        assert err[k] <= 10.0 * dev[k], (name, P, thermo, k)
+    assert np.array_equal(out['R_end'], out['R'][-1]) and np.array_equal(out['V_end'], out['V'][-1])
+    eps = np.finfo(float).eps
+    # the centroid is the bead average: a sequential sum of P terms and a division, (P + 1) eps at the worst
+    assert np.abs(out['Rc'] - out['R'].mean(axis=2)).max() <= (P + 1) * eps * np.abs(out['R']).max()
+
+
+@pytest.mark.parametrize('P', [32, 64, 128])
+def test_many_beads_match_restatement(P):
+    """The shapes at which the first kernel changes: 1024 threads beyond 16 beads, more than 64 KiB of LDS from 64 beads, the
+    narrow tile beyond 64.  The rule of the test above, and the narrow tile's bits where both widths exist."""
+    name, B, n = 'n6_p1', 2, 5
+    clean, dev = _reference(name, P, B, n, 'pile')
+    model, R0, V0, masses, ring = _setup(name, P, B)
+    pred = GDMLPredict(model)
+    kw = dict(ring, record=ALL, **PILE)
+    out = pred.run_pimd(R0, V0, masses, mr.DT[name], n, **kw)
+    for k in FIELDS:
+        err = np.abs(out[k] - clean[k]).max()
+        print('%s P=%d pile %s: sensitivity %.2e, error %.2e' % (name, P, k, dev[k], err))
+        assert err <= 10.0 * dev[k], (P, k)
+    pred._ctx.set_option('predict.pimd_tile', 32)
+    assert _same(out, pred.run_pimd(R0, V0, masses, mr.DT[name], n, **kw))
+
+
+# ---- 2. bit for bit
+
+@pytest.mark.parametrize('thermo', ['nve', 'pile'])
+@pytest.mark.parametrize('name,P', [('n5_p4', 3), ('n100_m3', 4)])
+def test_deterministic_restart_record_every_chunks_and_tiles(name, P, thermo):
+    model, R0, V0, masses, ring = _setup(name, P, 2)
+    pred = GDMLPredict(model)
+    kw, dt, n = dict(ring, record=ALL, **THERMO[thermo]), mr.DT[name], 6
+    keys = ALL + pr.RING
+    full = pred.run_pimd(R0, V0, masses, dt, 2 * n, **kw)
+    assert _same(full, pred.run_pimd(R0, V0, masses, dt, 2 * n, **kw))  # identical calls, identical bits
+    a = pred.run_pimd(R0, V0, masses, dt, n, **kw)
+    b = pred.run_pimd(a['R_end'], a['V_end'], masses, dt, n, step0=a['step_end'], **kw)
+    assert b['step_end'] == 2 * n
+    for k in keys:
+        assert np.array_equal(np.concatenate([a[k], b[k]]), full[k]), k
+    assert np.array_equal(b['R_end'], full['R_end']) and np.array_equal(b['V_end'], full['V_end'])
+    for every in (3, 2 * n):
+        o = pred.run_pimd(R0, V0, masses, dt, 2 * n, record_every=every, **kw)
+        assert np.array_equal(o['R_end'], full['R_end']) and np.array_equal(o['V_end'], full['V_end'])
+        for k in keys:
+            assert np.array_equal(o[k], full[k][every - 1::every]), (every, k)
+    for frames in (1, 5):  # a chunk bound forced small: 12 or 3 synchronisations instead of one
+        pred._ctx.set_option('predict.md_chunk_frames', frames)
+        assert _same(full, pred.run_pimd(R0, V0, masses, dt, 2 * n, **kw))
+    pred._ctx.set_option('predict.md_chunk_frames', 0)
+    pred._ctx.set_option('predict.pimd_tile', 32)  # the narrow tile: the same bits
+    assert _same(full, pred.run_pimd(R0, V0, masses, dt, 2 * n, **kw))
+    pred._ctx.set_option('predict.pimd_tile', 0)
+    short = pred.run_pimd(R0, V0, masses, dt, 3, record_every=5, **kw)  # fewer steps than a frame takes
+    assert short['R'].shape[0] == 0 and short['K_cv'].shape == (0, 2) and short['step_end'] == 3
+    assert np.array_equal(short['R_end'], full['R'][2])
+    none = pred.run_pimd(R0, V0, masses, dt, 0, **kw)  # no step: the start comes back
+    assert np.array_equal(none['R_end'], R0) and np.array_equal(none['V_end'], V0) and none['R'].shape[0] == 0
+    default = pred.run_pimd(R0, V0, masses, dt, n, **dict(ring, **THERMO[thermo]))  # record defaults to ('Rc', 'E')
+    assert 'R' not in default and np.array_equal(default['Rc'], a['Rc']) and np.array_equal(default['E'], a['E'])
+
+
+# ---- 3. frames against the predictor
+
+def test_frames_are_the_predictors_bits():
+    """D > 256: predict() of host geometries runs the kernels gdml_predict_dev runs, so per-bead E and F of a frame are the
+    bits of predict() of the frame's B P geometries."""
+    model, R0, V0, masses, ring = _setup('n100_m3', 4, 2)
+    pred = GDMLPredict(model)
+    for th in THERMO.values():
+        out = pred.run_pimd(R0, V0, masses, mr.DT['n100_m3'], 6, record_every=2, record=ALL, **dict(ring, **th))
+        assert out['R'].shape == (3, 2, 4, 300)
+        for k in range(3):
+            E, F = pred.predict(out['R'][k].reshape(8, 300))
+            assert np.array_equal(out['E'][k].ravel(), E) and np.array_equal(out['F'][k].reshape(8, 300), F), k
+            assert np.abs(out['E_pot'][k] - out['E'][k].mean(axis=1)).max() <= 16 * np.finfo(float).eps * np.abs(E).max()
+
+
+# ---- 4. one bead
+
+def test_one_bead_is_run_md():
+    """beads = 1 with the PILE thermostat is Langevin BAOAB: the noise index b P + k collapses to the replica index, the only
+    mode is the centroid.  Against run_md on the general route at the tolerance of test 1; no springs, and both estimators are
+    the classical 3N kT / 2."""
+    name, B, n, g = 'n6_p1', 2, 30, 0.5
+    model, R0, V0, masses, ring = _setup(name, 1, B)
+    _, dev = _reference(name, 1, B, n, 'pile')
+    pred = GDMLPredict(model)
+    pred._ctx.set_option('predict.md_fused', 0)
+    ring_out = pred.run_pimd(R0, V0, masses, mr.DT[name], n, record=ALL, **dict(ring, **PILE))
+    md = pred.run_md(R0[:, 0], V0[:, 0], masses, mr.DT[name], n, record=('R', 'V', 'F', 'E'), thermostat='langevin', gamma=g,
+                     kT=KT, seed=PILE['seed'])
+    for k, a, b in (('R', ring_out['R'][:, :, 0], md['R']), ('V', ring_out['V'][:, :, 0], md['V']),
+                    ('E_pot', ring_out['E_pot'], md['E_pot']), ('E_kin', ring_out['E_kin'], md['E_kin'])):
+        err = np.abs(a - b).max()
+        print('one bead vs run_md, %s: %.2e (sensitivity %.2e)' % (k, err, dev[k]))
+        assert err <= 10.0 * dev[k], k
+    assert np.all(ring_out['E_spring'] == 0.0)
+    classical = 1.5 * len(masses) * KT
+    assert np.all(ring_out['K_prim'] == classical) and np.all(ring_out['K_cv'] == classical)
+
+
+# ---- 5. rings are independent
+
+@pytest.mark.parametrize('name,P', [('n6_p1', 3), ('n100_m3', 4)])
+def test_ring_alone_and_in_batch(name, P):
+    """Ring 0 alone draws the noise of ring 0 in the batch.  Bit for bit where predict() itself gives a geometry the same
+    bits alone and in a batch (decided as tests/test_md_gpu.py decides it), else at the tolerance of test 1."""
+    n = 10
+    model, R0, V0, masses, ring = _setup(name, P, 3)
+    pred = GDMLPredict(model)
+    kw = dict(ring, record=ALL, **PILE)
+    batch = pred.run_pimd(R0, V0, masses, mr.DT[name], n, **kw)
+    alone = pred.run_pimd(R0[:1], V0[:1], masses, mr.DT[name], n, **kw)
+    n3 = R0.shape[2]
+    E3, F3 = pred.predict(R0.reshape(3 * P, n3))
+    E1, F1 = pred.predict(R0[0])
+    if np.array_equal(F1, F3[:P]) and np.array_equal(E1, E3[:P]):
+        for k in ALL + pr.RING:
+            assert np.array_equal(alone[k][:, 0], batch[k][:, 0]), k
+    else:
+        _, dev = _reference(name, P, 3, n, 'pile')
+        for k in FIELDS:
+            err = np.abs(alone[k][:, 0] - batch[k][:, 0]).max()
+            print('%s ring 0 alone vs in batch, %s: %.2e (sensitivity %.2e)' % (name, k, err, dev[k]))
+            assert err <= 10.0 * dev[k], k
+
+
+@pytest.mark.parametrize('name,P', [('n6_p1', 3), ('n100_m3', 4)])
+def test_collapsed_ring_stays_collapsed(name, P):
+    """All beads at one point with one velocity, no thermostat: the internal modes are exactly zero and stay so, every bead
+    feels the same force.  The start is given as (B, 3N)."""
+    model, R7 = mr.case(name)
+    n3 = R7.shape[1]
+    masses = np.linspace(1.0, 2.0, n3 // 3)
+    V0 = mr.start_velocities(2, n3, mr.V_SCALE[name])
+    pred = GDMLPredict(model)
+    out = pred.run_pimd(R7[:2], V0, masses, mr.DT[name], 10, P, KT, 2 * P * KT * mr.DT[name], record=ALL)
+    assert out['R'].shape == (10, 2, P, n3)
+    for k in ('R', 'V', 'F', 'E'):
+        assert np.array_equal(out[k], np.repeat(out[k][:, :, :1], P, axis=2)), k
+    assert np.all(out['E_spring'] == 0.0)
+    assert not np.array_equal(out['R'][-1, :, 0], R7[:2])
+
+
+# ---- 6. physics
+
+@pytest.mark.parametrize('name', ['n6_p1', 'n100_m3'])
+def test_ring_energy_drift_is_second_order(name):
+    """The dt, dt / 2 drift ratio of H_P = P E_pot + E_kin + E_spring (tests/test_pimd_cpu.py) on the GPU, same hbar."""
+    P = 4
+    model, R0, V0, masses, ring = _setup(name, P, 1, unit_masses=True)
+    pred = GDMLPredict(model)
+    dt, n = mr.DT[name], 40
+    E0, F0 = pred.predict(R0[0])
+    m = np.repeat(masses, 3)[None, None, :]
+    q0 = pr.ring_quantities(R0, V0, E0[None], F0[None], m, P, KT, P * KT / ring['hbar'], 1.0)
+    H0 = P * q0[0] + q0[1] + q0[2]
+    d = []
+    for h, steps in ((dt, n), (dt / 2, 2 * n)):
+        out = pred.run_pimd(R0, V0, masses, h, steps, **ring)
+        d.append(np.abs(pr.hamiltonian(out, P) - H0[None]).max())
+    print('%s: drift %.3e at dt, %.3e at dt/2, ratio %.3f' % (name, d[0], d[1], d[0] / d[1]))
+    assert 3.0 <= d[0] / d[1] <= 5.0
+
+
+@pytest.mark.parametrize('name', ['n6_p1', 'n100_m3'])
+def test_total_momentum_is_conserved(name):
+    """No lattice, no thermostat, masses 1: tests/test_md_gpu.py's bound with N P in the place of N (the springs are internal
+    forces of the ring, the orthonormal transform adds rounding only)."""
+    P, B = 4, 2
+    model, R0, V0, masses, ring = _setup(name, P, B, unit_masses=True)
+    pred = GDMLPredict(model)
+    n, dt, N = 20, mr.DT[name], len(masses)
+    out = pred.run_pimd(R0, V0, masses, dt, n, record=ALL, **ring)
+    P0 = V0.reshape(B, P * N, 3).sum(axis=1)
+    Pt = out['V'].reshape(n, B, P * N, 3).sum(axis=2)
+    NP = N * P
+    bound = 4 * n * NP * np.finfo(float).eps * (dt * NP * np.abs(out['F']).max() + np.abs(out['V']).max())
+    print('%s: momentum change %.2e, bound %.2e' % (name, np.abs(Pt - P0[None]).max(), bound))
+    assert np.abs(Pt - P0[None]).max() <= bound
+
+
+# ---- 7. error paths
+
+def test_error_paths():
+    model, R0, V0, masses, ring = _setup('n6_p1', 3, 2)
+    pred = GDMLPredict(model)
+    ok = dict(ring, R0=R0, V0=V0, masses=masses, dt=0.02, n_steps=4)
+
+    def bad(exc=ValueError, **kw):
+        with pytest.raises(exc):
+            pred.run_pimd(**dict(ok, **kw))
+
+    bad(R0=R0[:, :2])  # two beads where three are announced
+    bad(R0=R0[:, :, :15])
+    bad(V0=V0[:1])
+    bad(V0=V0[:, :, :15])
+    bad(R0=R0.reshape(2, -1))
+    bad(record=('R', 'W'))
+    bad(record='Q')
+    bad(beads=0)
+    bad(beads=129)
+    bad(beads=2.5)
+    bad(thermostat='langevin')
+    bad(hbar=0.0)
+    bad(kT=0.0)
+    bad(pile_lambda=0.0, thermostat='pile')
+    bad(gamma_centroid=-1.0, thermostat='pile')
+    bad(masses=np.ones(5))
+    bad(dt=float('nan'))
+    with pytest.raises(FloatingPointError, match=r'ring \d+ stopped being finite at step \d+'):
+        pred.run_pimd(**dict(ok, f_unit=1e300, n_steps=8))  # the velocities overflow: a numerical event, reported per ring
+    out = pred.run_pimd(**ok)  # and the integrator itself still works
+    assert out['Rc'].shape == (4, 2, 18) and np.isfinite(out['K_cv']).all()
