@@ -182,6 +182,10 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *                         many as fit into 64 MiB); the results do not depend on it
  *   predict.pimd_tile (0)         coordinates per workgroup of gdml_pimd_run's first kernel: 0 = 64 up to 64 beads and 32 beyond,
  *                         32 = always 32.  The results do not depend on it
+ *   predict.relax_fused (1)       gdml_relax_run with 1-8 geometries of a molecule with D <= 256: one launch per evaluation (0: the
+ *                         general route of two pieces per evaluation)
+ *   predict.relax_chunk_steps (32)  evaluations gdml_relax_run queues between two synchronisations (the host learns at a chunk's
+ *                         end which replicas froze); the results do not depend on it
  *   chol.loo_chunk (64)            training points per pass of gdml_loo (their rows of L^-T are 3N n doubles each; fewer when free
  *                         memory is short).  The results do not depend on it
  *   chol.extend_chunk (64)         points per pass of gdml_factor_extend (their 3N rows are assembled, solved and factored together;
@@ -434,6 +438,77 @@ int gdml_pimd_run(gdml_ctx* ctx, const gdml_pimd_params* params, double* R, doub
                   double* R_rec, double* V_rec, double* F_rec, double* E_rec, double* Rc_rec, double* ring_rec,
                   int64_t* first_bad_step);
 int gdml_pimd_modes(int beads, double kT, double hbar, double* C /* (P,P) row j, column k */, double* omega /* (P) */);
+
+/* Geometry relaxation on the device: B independent geometries of the model's molecule descend to a minimum of the energy by
+ * FIRE (Bitzek, Koskinen, Gaehler, Moseler, Gumbsch, Phys. Rev. Lett. 97, 170201 (2006)) in the form ASE's FIRE optimiser
+ * uses: unit masses, the whole 3N-vector step clipped.  Positions, velocities, forces and the optimiser's state stay resident
+ * in device memory; the host sees the end state and a small history.  The reference has no counterpart (its users drive
+ * GDMLPredict.predict from ASE's optimisers, one host round trip per step).
+ * The step.  g = f_scale F' (F' the library's unscaled force, f_scale = std times the caller's unit factor); all sums and
+ *   norms run over a replica's 3N coordinates.  Per-replica state: v, dt, alpha, n_pos (steps since the last negative
+ *   power), n_taken (steps taken in the replica's lifetime).  Evaluation t = 0, 1, ... of a replica that is still active:
+ *   1. E', F' = predictor(r);  f_atom = max over atoms of |g_atom|;  E' and f_atom go into the history.  A non-finite r, v, F'
+ *      or E' sets the replica's first_bad_step (to t), as in gdml_md_run; such a replica never counts as converged.
+ *   2. f_atom < fmax: the replica is converged.  Its r, v, dt, alpha, n_pos, n_taken, E' and F' freeze: never written again.
+ *   3. otherwise, t = max_steps (the budget of this call is used up): the replica stops unconverged and freezes the same way.
+ *   4. otherwise update:
+ *        if n_taken > 0:  p = g . v
+ *          p > 0:   v <- (1 - alpha) v + (alpha |v| / |g|) g;   then, if n_pos > n_min:  dt <- min(dt f_inc, dt_max),
+ *                   alpha <- alpha f_alpha;   then n_pos += 1
+ *          p <= 0:  v <- 0,  alpha <- alpha_start,  dt <- dt f_dec,  n_pos <- 0
+ *        (n_taken = 0 skips this block -- ASE's "v is None" case; without it a fresh start would halve dt at once)
+ *        v <- v + dt g;   Delta = dt v;   if |Delta| > max_step:  Delta <- Delta (max_step / |Delta|);   r <- r + Delta;
+ *        n_taken += 1
+ *   A call makes at most max_steps + 1 evaluations per replica; E_end and F_end are always those of R_end.
+ *   Sums (g.v, |g|^2, |v|^2, |Delta|^2): per-thread partial sums in index order (coordinate k, k + 256, ...), then
+ *   gdml_md_run's 256-slot tree; the maximum over atoms is order-independent.  No floating-point atomics.
+ *   lat / lat_inv: the predictor's minimum image only; positions are never wrapped; the cell is fixed.
+ * Two routes, the same arithmetic of an update on both (one device function):
+ *   general (any shape): per evaluation the device prediction path exactly as gdml_predict_dev runs it for all B geometries
+ *     (frozen ones included; their results are discarded, so a frozen replica keeps the bits of its last evaluation), then a
+ *     kernel with one workgroup per replica: reductions, convergence test, update, history and frame write.  It writes
+ *     nothing another workgroup reads;
+ *   single launch (the shapes of predict.fused: D <= 256, B <= 8; option predict.relax_fused): ONE kernel per evaluation,
+ *     modelled on gdml_md_run's -- the predictor's row loop, row split, partial sums and ticket.  The replica's last
+ *     workgroup sums the partials in the predictor's order, back-projects F' and does 1-4 above; r(t+1) goes into the other
+ *     half of a ping-pong buffer (a freezing replica writes its r there too, so both halves hold it from then on).  The
+ *     workgroups of a frozen replica read its status word, written by an earlier launch, and return at once.  No persistent
+ *     kernel, no waiting between workgroups, no graph, no host polling.
+ *   Evaluations are plain launches queued back to back; the host synchronises once per chunk (option
+ *   predict.relax_chunk_steps evaluations, and at most predict.md_chunk_frames frames / 64 MiB when R is recorded), reads
+ *   the status words and first_bad_step flags and stops when no replica is active.  Frozen replicas are never rewritten, so
+ *   nothing in the result depends on the chunk length.
+ * Arguments.  R, V (B,3N), dt, alpha (B), n_pos, n_taken (B, int64): the state, the start on entry and the end on return (a
+ *   fresh start: V = 0, dt = the first time step, alpha = alpha_start, n_pos = n_taken = 0).  Passing the end state back
+ *   continues the run as if it had not been cut (max_steps is the budget of one call).
+ *   status (B,2) int64: [0] = 1 converged, 0 budget used up, -1 still active (only after a non-finite value stopped the
+ *   run); [1] = the evaluation of this call at which the replica froze = the steps it took in this call (-1 if active).
+ *   With n_made = 1 + the largest status[.][1] (the evaluations made; launches beyond it found every replica frozen):
+ *   E_hist, fmax_hist (max_steps + 1, B): rows 0 .. n_made - 1 are written, E' UNSCALED like gdml_predict and f_atom; a frozen
+ *   replica repeats its last value.  R_rec (max_steps / record_every + 1, B, 3N) or NULL (then record_every is not used):
+ *   frame k = the positions of evaluation k record_every, written for k record_every < n_made, a frozen replica repeating
+ *   its end positions.  record_every = 0 is allowed with R_rec = NULL only.  E_end (B), F_end (B,3N): E', F' UNSCALED at R.
+ *   first_bad_step (B): evaluation at which a value of the replica stopped being finite, -1 = none; checked at chunk ends.
+ * Bit-identical: the same call repeated; n steps then a continuation against 2 n steps; any chunk length; any record_every;
+ *   on the general route E_end, F_end are what gdml_predict_dev returns for R (same B).
+ * GDML_ERR_INVALID before any launch (ctx may be NULL for these checks): fmax <= 0 or not finite, max_steps < 0, a dt <= 0,
+ *   dt_max < a dt, max_step <= 0, f_inc < 1, f_dec outside (0, 1), alpha_start or f_alpha outside (0, 1], n_min < 0,
+ *   record_every < 0 (< 1 with R_rec), exactly one of lat / lat_inv, a NULL state or output array, N different from the
+ *   model's.  GDML_ERR_STATE without a model. */
+typedef struct gdml_relax_params {
+  int64_t B;
+  int N;
+  double f_scale;        /* g = f_scale * F' */
+  const double* lat;
+  const double* lat_inv; /* both or neither */
+  double fmax;           /* converged when the largest |g_atom| is below it */
+  double dt_max, max_step;
+  double f_inc, f_dec, alpha_start, f_alpha;
+  int64_t n_min;
+} gdml_relax_params;     /* 104 bytes */
+int gdml_relax_run(gdml_ctx* ctx, const gdml_relax_params* params, double* R, double* V, double* dt, double* alpha,
+                   int64_t* n_pos, int64_t* n_taken, int64_t max_steps, int64_t record_every, double* R_rec, double* E_hist,
+                   double* fmax_hist, double* E_end, double* F_end, int64_t* status, int64_t* first_bad_step);
 
 /* Strain derivative (virial) of B geometries: what pressure, NPT dynamics, cell relaxation and equation-of-state scans of a
  * periodic model need, and what its forces cannot give (with minimum-image pair vectors sum_i f_i (x) r_i is not the strain

@@ -33,6 +33,13 @@ class PIMDParams(C.Structure):
                 ('pile_lambda', C.c_double), ('kT', C.c_double), ('hbar', C.c_double), ('seed', C.c_uint64), ('step0', C.c_int64)]
 
 
+class RelaxParams(C.Structure):
+    """gdml_relax_params (include/gdml_hip.h)."""
+    _fields_ = [('B', C.c_int64), ('N', C.c_int), ('f_scale', C.c_double), ('lat', _vp), ('lat_inv', _vp), ('fmax', C.c_double),
+                ('dt_max', C.c_double), ('max_step', C.c_double), ('f_inc', C.c_double), ('f_dec', C.c_double),
+                ('alpha_start', C.c_double), ('f_alpha', C.c_double), ('n_min', C.c_int64)]
+
+
 # name -> (restype, argtypes).  Must list every symbol declared in include/gdml_hip.h.
 SIGNATURES = {
     'gdml_abi_version': (C.c_int, []),
@@ -67,6 +74,8 @@ SIGNATURES = {
     'gdml_md_noise': (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int, _vp, _vp]),
     'gdml_pimd_run': (C.c_int, [_vp, C.POINTER(PIMDParams), _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gdml_pimd_modes': (C.c_int, [C.c_int, C.c_double, C.c_double, _vp, _vp]),
+    'gdml_relax_run': (C.c_int, [_vp, C.POINTER(RelaxParams), _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp]),
     'gdml_predict_virial': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_virial_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
@@ -644,6 +653,47 @@ class Context(object):
         if lib.gdml_pimd_modes(P, float(kT), float(hbar), _ptr(Cm), _ptr(omega)) != GDML_OK:
             raise ValueError(lib.gdml_last_error(None).decode())
         return Cm, omega
+
+    def relax_run(self, R, fmax, max_steps, state, dt_max, max_step=0.2, n_min=5, f_inc=1.1, f_dec=0.5, alpha_start=0.1,
+                  f_alpha=0.99, f_scale=1.0, record_every=0, lat_and_inv=None):
+        """gdml_relax_run: B geometries (R: (B,3N)) descend by FIRE on the device for at most max_steps steps each.  state: dict
+        with 'V' (B,3N), 'dt', 'alpha' (B), 'n_pos', 'n_taken' (B, int) -- the optimiser's state at the start.  Returns a dict:
+        'R_end', 'E_end' (B; unscaled E'), 'F_end' (B,3N; unscaled), the end 'state', 'status' (B,2; see the header), 'n_made'
+        (evaluations made), 'E_hist', 'fmax_hist' (n_made,B), the frames 'R' (every record_every-th evaluation; only with
+        record_every > 0) and 'first_bad_step' (B; -1 = every value stayed finite)."""
+        n3 = 3 * self.model_n_atoms
+        R = np.array(R, dtype=np.float64).reshape(-1, n3)  # copies: the call overwrites the state with the end state
+        B = R.shape[0]
+        V = np.array(state['V'], dtype=np.float64).reshape(-1, n3)
+        if V.shape != R.shape:
+            raise ValueError('R and V differ in shape: {} and {}'.format(R.shape, V.shape))
+        dt, alpha = (np.array(state[k], dtype=np.float64).ravel() for k in ('dt', 'alpha'))
+        n_pos, n_taken = (np.array(state[k], dtype=np.int64).ravel() for k in ('n_pos', 'n_taken'))
+        for k, a in (('dt', dt), ('alpha', alpha), ('n_pos', n_pos), ('n_taken', n_taken)):
+            if a.shape != (B,):
+                raise ValueError("state['{}'] must have one entry per geometry ({}), got shape {}".format(k, B, a.shape))
+        lat = lat_inv = None
+        if lat_and_inv is not None:
+            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        max_steps, record_every = int(max_steps), int(record_every)
+        n_eval = max(max_steps, 0) + 1
+        R_rec = np.empty((max(max_steps, 0) // record_every + 1, B, n3)) if record_every > 0 else None
+        E_hist, f_hist = np.empty((n_eval, B)), np.empty((n_eval, B))
+        E_end, F_end = np.empty(B), np.empty((B, n3))
+        status = np.full((B, 2), -1, dtype=np.int64)
+        bad = np.full(B, -1, dtype=np.int64)
+        prm = RelaxParams(B, self.model_n_atoms, float(f_scale), _ptr(lat), _ptr(lat_inv), float(fmax), float(dt_max),
+                          float(max_step), float(f_inc), float(f_dec), float(alpha_start), float(f_alpha), int(n_min))
+        self._check(self._lib.gdml_relax_run(self._h, C.byref(prm), _ptr(R), _ptr(V), _ptr(dt), _ptr(alpha), _ptr(n_pos),
+                                             _ptr(n_taken), max_steps, record_every, _ptr(R_rec), _ptr(E_hist), _ptr(f_hist),
+                                             _ptr(E_end), _ptr(F_end), _ptr(status), _ptr(bad)))
+        n_made = int(status[:, 1].max()) + 1 if B and (status[:, 1] >= 0).all() else 0
+        out = dict(R_end=R, E_end=E_end, F_end=F_end, status=status, first_bad_step=bad, n_made=n_made,
+                   E_hist=E_hist[:n_made], fmax_hist=f_hist[:n_made],
+                   state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken))
+        if R_rec is not None:
+            out['R'] = R_rec[:(n_made + record_every - 1) // record_every]
+        return out
 
     def predict_virial(self, R, lat_and_inv=None):
         """Unscaled E' (B,), F (B,3N) and strain derivative W = dE'/d eps (B,3,3) of geometries R (B,3N) (gdml_predict_virial);

@@ -12,6 +12,8 @@
 // The host synchronises once per chunk of frames (bounded in bytes and in queued steps), copies the chunk out and reads the
 // per-replica "first non-finite step" flags.  fp64 throughout, no atomics on floating-point values: results do not depend on
 // chunking, on record_every or on how a run is cut into continued runs.
+// Geometry relaxation (gdml_relax_run, batched FIRE with per-replica convergence) is the last part of this file: the same two
+// routes and the same chunked driver, with a per-replica status word the host reads at chunk ends.
 #include <math.h>
 
 #include "common.h"
@@ -163,17 +165,22 @@ __global__ void __launch_bounds__(256) md_post_kernel(MdConst C, const double* _
 // ------------------------------------------------------------------------------------------
 #define MD_STEP_MAX_Q 8
 #define MD_STEP_MAX_COORDS 72  // 3 N for D = N (N - 1) / 2 <= 256: N <= 23
-struct MdStepArgs {
+// model tables, row split and work buffers of a single-launch step (md_step_kernel and relax_step_kernel)
+struct StepModel {
   const double* xp;
   const double* jap;
   const double* aE;
   int64_t MP;
   int D, N;
   double sig;
-  int rows_per_wave, init;
+  int rows_per_wave;
   double* part;       // (B, n_wg, D + 1) workgroup partials: F_x, then E
   unsigned* counter;  // [q] workgroups of replica q that have finished
   Lattice L;
+};
+struct MdStepArgs {
+  StepModel M;
+  int init;
   MdConst C;
   const double* mass;
   const double *inR, *inV, *inF;
@@ -203,18 +210,13 @@ __device__ __forceinline__ void md_pair_of(int k, int& i, int& j) {  // k = i (i
   j = k - i * (i - 1) / 2;
 }
 
+// The predictor's share of a single-launch step, for the geometry s_r (LDS) of replica q = blockIdx.y: this workgroup's table
+// rows into its partial, then the ticket.  True for the replica's last workgroup, which goes on to step_gather.
 template <int KPL>
-__global__ void __launch_bounds__(256) md_step_kernel(MdStepArgs A) {
-  __shared__ double s_fx[4][KPL * 64];  // per-wavefront F_x; reused by the replica's last workgroup: [0] = its summed F_x
-  __shared__ double s_E[4];
-  __shared__ double s_g[KPL * 64 * 3];
-  __shared__ double s_r[MD_STEP_MAX_COORDS], s_v[MD_STEP_MAX_COORDS];
-  __shared__ double s_red[256];
-  __shared__ double s_Eq;
-  __shared__ unsigned s_ticket;
-  __shared__ int s_nonfinite;
+__device__ __forceinline__ bool step_partials(const StepModel& A, const double* s_r, double (&s_fx)[4][KPL * 64], double (&s_E)[4],
+                                              unsigned& s_ticket) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int D = A.D, N = A.N, n3 = 3 * N;
+  const int D = A.D;
   const int q = (int)blockIdx.y;  // a workgroup serves ONE replica
   const double sig = A.sig, inv_sig = 1.0 / sig;
   const double sqrt5 = 2.23606797749978969641;
@@ -222,18 +224,7 @@ __global__ void __launch_bounds__(256) md_step_kernel(MdStepArgs A) {
   const double dscale = 5.0 / sig;
   const double inv_3sig = 1.0 / (3.0 * sig);
 
-  // ---- first half of the step, redone by every workgroup of the replica: r_{t+1} and the half-kicked velocity into LDS
-  if (tid < n3) {
-    const int64_t o = (int64_t)q * n3 + tid;
-    double r = A.inR[o], v = A.inV[o];
-    if (!A.init) md_first_half(A.C, A.mass[tid / 3], A.inF[o], A.step, q, tid, r, v);
-    s_r[tid] = r;
-    s_v[tid] = v;
-  }
-  if (tid == 0) s_nonfinite = 0;
-  __syncthreads();
-
-  // ---- descriptor of r_{t+1} (same arithmetic as desc_kernel)
+  // ---- descriptor of the geometry (same arithmetic as desc_kernel)
   double x[KPL], Fx[KPL], E = 0.0;
 #pragma unroll
   for (int t = 0; t < KPL; ++t) {
@@ -317,11 +308,17 @@ __global__ void __launch_bounds__(256) md_step_kernel(MdStepArgs A) {
   __syncthreads();
   if (tid == 0) s_ticket = atomicAdd(A.counter + q, 1u);
   __syncthreads();
-  if (s_ticket != gridDim.x - 1) return;
+  return s_ticket == gridDim.x - 1;
+}
 
-  // ---- the replica's last workgroup: every partial of this replica is visible
+// The replica's last workgroup (every partial of the replica is visible): the partials summed in the predictor's order into
+// fxs (D) and s_Eq, and the Jacobian entries of s_r into s_g (D, 3).  step_force then back-projects one coordinate.
+__device__ __forceinline__ void step_gather(const StepModel& A, const double* s_r, double* fxs, double* s_g, double& s_Eq) {
+  const int tid = threadIdx.x;
+  const int D = A.D;
+  const int q = (int)blockIdx.y;
+  const int n_wg = (int)gridDim.x;
   __threadfence();
-  double* fxs = &s_fx[0][0];
   const double* qpart = A.part + (int64_t)q * n_wg * (D + 1);
   for (int k = tid; k < D + 1; k += 256) {
     double s = 0.0;
@@ -351,16 +348,53 @@ __global__ void __launch_bounds__(256) md_step_kernel(MdStepArgs A) {
     s_g[k * 3 + 2] = d[2] * inv3;
   }
   __syncthreads();
+}
+
+// coordinate t of F = J_x^T F_x in the order of predict_epilogue_kernel
+__device__ __forceinline__ double step_force(int N, const double* s_g, const double* fxs, int t) {
+  const int a = t / 3, al = t - 3 * a;
+  double f = 0.0;
+  for (int m = 0; m < N; ++m) {
+    if (m == a) continue;
+    const int k = pair_idx(a, m);
+    const double v = s_g[k * 3 + al] * fxs[k];
+    f += (a < m) ? v : -v;
+  }
+  return f;
+}
+
+template <int KPL>
+__global__ void __launch_bounds__(256) md_step_kernel(MdStepArgs A) {
+  __shared__ double s_fx[4][KPL * 64];  // per-wavefront F_x; reused by the replica's last workgroup: [0] = its summed F_x
+  __shared__ double s_E[4];
+  __shared__ double s_g[KPL * 64 * 3];
+  __shared__ double s_r[MD_STEP_MAX_COORDS], s_v[MD_STEP_MAX_COORDS];
+  __shared__ double s_red[256];
+  __shared__ double s_Eq;
+  __shared__ unsigned s_ticket;
+  __shared__ int s_nonfinite;
+  const int tid = threadIdx.x;
+  const int N = A.M.N, n3 = 3 * N;
+  const int q = (int)blockIdx.y;  // a workgroup serves ONE replica
+
+  // ---- first half of the step, redone by every workgroup of the replica: r_{t+1} and the half-kicked velocity into LDS
+  if (tid < n3) {
+    const int64_t o = (int64_t)q * n3 + tid;
+    double r = A.inR[o], v = A.inV[o];
+    if (!A.init) md_first_half(A.C, A.mass[tid / 3], A.inF[o], A.step, q, tid, r, v);
+    s_r[tid] = r;
+    s_v[tid] = v;
+  }
+  if (tid == 0) s_nonfinite = 0;
+  __syncthreads();
+
+  if (!step_partials<KPL>(A.M, s_r, s_fx, s_E, s_ticket)) return;
+  double* fxs = &s_fx[0][0];
+  step_gather(A.M, s_r, fxs, s_g, s_Eq);
   double ek = 0.0;
-  if (tid < n3) {  // F = J_x^T F_x in the order of predict_epilogue_kernel, then the second half kick
-    const int t = tid, a = t / 3, al = t - 3 * a;
-    double f = 0.0;
-    for (int m = 0; m < N; ++m) {
-      if (m == a) continue;
-      const int k = pair_idx(a, m);
-      const double v = s_g[k * 3 + al] * fxs[k];
-      f += (a < m) ? v : -v;
-    }
+  if (tid < n3) {  // F = J_x^T F_x, then the second half kick
+    const int t = tid, a = t / 3;
+    const double f = step_force(N, s_g, fxs, t);
     const double m = A.mass[a];
     const double r = s_r[t];
     const double v = A.init ? s_v[t] : s_v[t] + 0.5 * A.C.dt * (A.C.f_scale * f / m);
@@ -391,7 +425,7 @@ __global__ void __launch_bounds__(256) md_step_kernel(MdStepArgs A) {
       A.fr.E[q] = e;
       A.fr.Ekin[q] = s_red[0];
     }
-    A.counter[q] = 0u;  // the next launch on the stream finds it reset
+    A.M.counter[q] = 0u;  // the next launch on the stream finds it reset
   }
 }
 
@@ -528,13 +562,13 @@ extern "C" int gdml_md_run(gdml_ctx* ctx, const gdml_md_params* p, double* R, do
   MdStepArgs S;
   memset(&S, 0, sizeof(S));
   if (fused) {
-    S.xp = md.xp; S.jap = md.jap; S.aE = md.has_aE ? md.aE : nullptr;
-    S.MP = MP; S.D = D; S.N = p->N; S.sig = md.sig; S.rows_per_wave = rows;
-    S.part = d_part; S.counter = d_counter; S.C = C; S.mass = d_mass; S.bad = d_bad;
+    S.M.xp = md.xp; S.M.jap = md.jap; S.M.aE = md.has_aE ? md.aE : nullptr;
+    S.M.MP = MP; S.M.D = D; S.M.N = p->N; S.M.sig = md.sig; S.M.rows_per_wave = rows;
+    S.M.part = d_part; S.M.counter = d_counter; S.C = C; S.mass = d_mass; S.bad = d_bad;
     if (p->lat && p->lat_inv) {
-      memcpy(S.L.lat, p->lat, sizeof(S.L.lat));
-      memcpy(S.L.inv, p->lat_inv, sizeof(S.L.inv));
-      S.L.use = 1;
+      memcpy(S.M.L.lat, p->lat, sizeof(S.M.L.lat));
+      memcpy(S.M.L.inv, p->lat_inv, sizeof(S.M.L.inv));
+      S.M.L.use = 1;
     }
   }
   int KPL = 1;
@@ -1058,5 +1092,438 @@ extern "C" int gdml_pimd_run(gdml_ctx* ctx, const gdml_pimd_params* p, double* R
   DROP_HIP(hipMemcpyAsync(V, d_V, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipStreamSynchronize(st));
   if (first_bad_step && n_steps > 0) memcpy(first_bad_step, h_bad.data(), (size_t)B * 8);
+  return drop(GDML_OK);
+}
+
+// ------------------------------------------------------------------------------------------
+// Geometry relaxation (gdml_relax_run): B independent geometries descend by FIRE (Bitzek et al., Phys. Rev. Lett. 97, 170201
+// (2006)) in the form ASE's FIRE uses -- unit masses, the whole 3N-vector step clipped.  The step (the contract;
+// include/gdml_hip.h and tests/_relax_ref.py state the same):
+//   g = f_scale F'; sums and norms over a replica's 3N coordinates; state v, dt, alpha, n_pos, n_taken per replica.
+//   Evaluation t = 0, 1, ... of an active replica:
+//   1. E', F' = predictor(r);  f_atom = max over atoms |g_atom|;  both into the history; non-finite r, v, F', E' -> bad[q] = t
+//   2. f_atom < fmax: converged -- r, v, dt, alpha, n_pos, n_taken, E', F' freeze, never written again
+//   3. else t = max_steps: stops unconverged, freezes the same way
+//   4. else, if n_taken > 0:  p = g . v;
+//        p > 0:   v <- (1 - alpha) v + (alpha |v| / |g|) g;  if n_pos > n_min: dt <- min(dt f_inc, dt_max), alpha <- alpha f_alpha;
+//                 n_pos += 1
+//        p <= 0:  v <- 0, alpha <- alpha_start, dt <- dt f_dec, n_pos <- 0
+//      v <- v + dt g;  Delta = dt v;  |Delta| > max_step: Delta <- Delta (max_step / |Delta|);  r <- r + Delta;  n_taken += 1
+// Sums: per-thread partial sums in index order, then the 256-slot tree of md_post_kernel.  Two routes, ONE update function
+// (relax_finish) on both:
+//   general:       gdml_predict_dev for all B geometries into scratch (frozen replicas' results are discarded), then
+//                  relax_update_kernel, one workgroup per replica
+//   single launch: relax_step_kernel (D <= 256, B <= 8), the predictor's share being md_step_kernel's (step_partials,
+//                  step_gather, step_force); r(t+1) into the other half of a ping-pong buffer
+// The host synchronises once per chunk and reads the status words; it stops when no replica is active.
+// ------------------------------------------------------------------------------------------
+struct RelaxConst {
+  int n3;
+  double f_scale, fmax, dt_max, max_step, f_inc, f_dec, alpha_start, f_alpha;
+  int64_t n_min;
+};
+struct RelaxState {  // per-replica state in device memory
+  double *V, *F, *E, *dt, *alpha;
+  int64_t *n_pos, *n_taken;
+  int64_t* status;  // (B,2): [0] -1 active, 0 budget used up, 1 converged; [1] the evaluation at which it froze
+  int64_t* bad;
+};
+struct RelaxSlot {  // where this evaluation goes in the chunk buffers
+  double *E, *fat;  // (B) rows of the history
+  double* R;        // (B,3N) frame; null when this is no recording evaluation
+};
+
+// Steps 1-4 for replica q once its F' is known, called by all 256 threads of one workgroup.  r: positions of this evaluation,
+// fp: F', e: E'; r_next: where r(t+1) goes (may be r itself: every coordinate is read and written by one thread); r_keep: where
+// a freezing replica's r is written as well (null: nowhere).  red: 4 x 256 doubles of LDS.
+__device__ __forceinline__ void relax_finish(const RelaxConst& C, const RelaxState& S, const RelaxSlot& sl, int64_t q, int64_t t,
+                                             int last, const double* r, const double* fp, double e, double* r_next,
+                                             double* r_keep, double (&red)[4][256]) {
+  const int tid = threadIdx.x, n3 = C.n3;
+  const int64_t o = q * n3;
+  double dt = S.dt[q], alpha = S.alpha[q];
+  int64_t n_pos = S.n_pos[q];
+  const int64_t n_taken = S.n_taken[q];
+
+  double gv = 0.0, gg = 0.0, vv = 0.0, fa = 0.0;
+  int nf = 0;
+  for (int k = tid; k < n3; k += 256) {
+    const double f = fp[k], v = S.V[o + k], g = C.f_scale * f;
+    gv += g * v;
+    gg += g * g;
+    vv += v * v;
+    nf |= !(isfinite(r[k]) && isfinite(v) && isfinite(f));
+    S.F[o + k] = f;
+    if (sl.R) sl.R[o + k] = r[k];
+  }
+  for (int a = tid; 3 * a < n3; a += 256) {
+    const double g0 = C.f_scale * fp[3 * a], g1 = C.f_scale * fp[3 * a + 1], g2 = C.f_scale * fp[3 * a + 2];
+    const double nrm = sqrt(g0 * g0 + g1 * g1 + g2 * g2);
+    fa = nrm > fa ? nrm : fa;
+  }
+  red[0][tid] = gv;
+  red[1][tid] = gg;
+  red[2][tid] = vv;
+  red[3][tid] = fa;
+  nf = __syncthreads_or(nf);
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) {
+      red[0][tid] += red[0][tid + s];
+      red[1][tid] += red[1][tid + s];
+      red[2][tid] += red[2][tid + s];
+      red[3][tid] = red[3][tid + s] > red[3][tid] ? red[3][tid + s] : red[3][tid];
+    }
+    __syncthreads();
+  }
+  const double p = red[0][0], g_nrm = sqrt(red[1][0]), v_nrm = sqrt(red[2][0]), f_atom = red[3][0];
+  const bool bad_now = nf || !isfinite(e);
+  const bool conv = !bad_now && f_atom < C.fmax;  // (the maximum skips a NaN)
+  if (tid == 0) {
+    S.E[q] = e;
+    sl.E[q] = e;
+    sl.fat[q] = f_atom;
+    if (bad_now && S.bad[q] < 0) S.bad[q] = t;
+  }
+  if (conv || last) {  // frozen from here on: no later launch writes anything of this replica
+    if (r_keep)
+      for (int k = tid; k < n3; k += 256) r_keep[k] = r[k];
+    if (tid == 0) {
+      S.status[2 * q] = conv ? 1 : 0;
+      S.status[2 * q + 1] = t;
+    }
+    return;
+  }
+
+  int mode = 0;  // 0: v as it is (the first step of a lifetime), 1: mixed with the force direction, 2: zeroed
+  double cv = 1.0, cg = 0.0;
+  if (n_taken > 0) {
+    if (p > 0.0) {
+      mode = 1;
+      cv = 1.0 - alpha;
+      cg = alpha * v_nrm / g_nrm;
+      if (n_pos > C.n_min) {
+        dt = fmin(dt * C.f_inc, C.dt_max);
+        alpha = alpha * C.f_alpha;
+      }
+      n_pos += 1;
+    } else {
+      mode = 2;
+      alpha = C.alpha_start;
+      dt = dt * C.f_dec;
+      n_pos = 0;
+    }
+  }
+  double dd = 0.0;
+  for (int k = tid; k < n3; k += 256) {
+    const double g = C.f_scale * fp[k];
+    double v = S.V[o + k];
+    if (mode == 1) v = cv * v + cg * g;
+    if (mode == 2) v = 0.0;
+    v = v + dt * g;
+    S.V[o + k] = v;
+    const double d = dt * v;
+    dd += d * d;
+  }
+  __syncthreads();  // every thread has read the first tree's results
+  red[0][tid] = dd;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[0][tid] += red[0][tid + s];
+    __syncthreads();
+  }
+  const double d_nrm = sqrt(red[0][0]);
+  const bool clip = d_nrm > C.max_step;
+  const double scale = C.max_step / d_nrm;
+  for (int k = tid; k < n3; k += 256) {
+    double d = dt * S.V[o + k];
+    if (clip) d = d * scale;
+    r_next[k] = r[k] + d;
+  }
+  if (tid == 0) {
+    S.dt[q] = dt;
+    S.alpha[q] = alpha;
+    S.n_pos[q] = n_pos;
+    S.n_taken[q] = n_taken + 1;
+  }
+}
+
+// general route, one workgroup per replica: F', E' of all B geometries lie in Ft, Et (gdml_predict_dev); a frozen replica's
+// are ignored
+__global__ void __launch_bounds__(256) relax_update_kernel(RelaxConst C, RelaxState S, RelaxSlot sl, double* R, const double* Ft,
+                                                           const double* Et, int64_t t, int last) {
+  __shared__ double red[4][256];
+  const int64_t q = blockIdx.x;
+  if (S.status[2 * q] >= 0) return;
+  double* r = R + q * C.n3;
+  relax_finish(C, S, sl, q, t, last, r, Ft + q * C.n3, Et[q], r, nullptr, red);
+}
+
+struct RelaxStepArgs {
+  StepModel M;
+  RelaxConst C;
+  RelaxState S;
+  RelaxSlot sl;
+  const double* inR;
+  double* outR;
+  int64_t t;
+  int last;
+};
+
+// single-launch evaluation: grid = (row shares, replicas) as md_step_kernel's.  The workgroups of a frozen replica return at
+// once (its status word was written by an earlier launch).  The replica's last workgroup back-projects F' and runs
+// relax_finish with its r in LDS; r(t+1) -- or the frozen r -- goes into the other half of the ping-pong buffer.
+template <int KPL>
+__global__ void __launch_bounds__(256) relax_step_kernel(RelaxStepArgs A) {
+  __shared__ double s_fx[4][KPL * 64];
+  __shared__ double s_E[4];
+  __shared__ double s_g[KPL * 64 * 3];
+  __shared__ double s_r[MD_STEP_MAX_COORDS], s_f[MD_STEP_MAX_COORDS];
+  __shared__ double red[4][256];
+  __shared__ double s_Eq;
+  __shared__ unsigned s_ticket;
+  const int tid = threadIdx.x;
+  const int N = A.M.N, n3 = 3 * N;
+  const int q = (int)blockIdx.y;
+  if (A.S.status[2 * q] >= 0) return;
+  if (tid < n3) s_r[tid] = A.inR[(int64_t)q * n3 + tid];
+  __syncthreads();
+
+  if (!step_partials<KPL>(A.M, s_r, s_fx, s_E, s_ticket)) return;
+  double* fxs = &s_fx[0][0];
+  step_gather(A.M, s_r, fxs, s_g, s_Eq);
+  if (tid < n3) s_f[tid] = step_force(N, s_g, fxs, tid);
+  __syncthreads();
+  double* out = A.outR + (int64_t)q * n3;
+  relax_finish(A.C, A.S, A.sl, q, A.t, A.last, s_r, s_f, s_Eq, out, out, red);
+  if (tid == 0) A.M.counter[q] = 0u;  // the next launch on the stream finds it reset
+}
+
+// argument checks; ctx may be NULL (the message then goes where gdml_ctx_create's goes)
+static int relax_check(gdml_ctx* ctx, const gdml_relax_params* p, const double* R, const double* V, const double* dt,
+                       const double* alpha, const int64_t* n_pos, const int64_t* n_taken, int64_t max_steps, int64_t record_every,
+                       const double* R_rec, const double* E_hist, const double* fmax_hist, const double* E_end,
+                       const double* F_end, const int64_t* status) {
+  if (!p) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: params is NULL");
+  if (max_steps < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: max_steps < 0");
+  if (record_every < 0 || (R_rec && record_every < 1))
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: record_every < 0, or < 1 with R_rec");
+  if (p->B < 0 || p->B > 0x7fffffffLL) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: B out of range");
+  if (p->N < 1 || p->N > GDML_MAX_ATOMS) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: N out of range");
+  if (!isfinite(p->f_scale)) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: f_scale is not finite");
+  if (!(p->fmax > 0.0) || !isfinite(p->fmax)) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: fmax must be positive and finite");
+  if (!(p->max_step > 0.0) || !isfinite(p->max_step))
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: max_step must be positive and finite");
+  if (!(p->f_inc >= 1.0) || !isfinite(p->f_inc)) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: f_inc < 1");
+  if (!(p->f_dec > 0.0 && p->f_dec < 1.0)) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: f_dec outside (0, 1)");
+  if (!(p->alpha_start > 0.0 && p->alpha_start <= 1.0))
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: alpha_start outside (0, 1]");
+  if (!(p->f_alpha > 0.0 && p->f_alpha <= 1.0)) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: f_alpha outside (0, 1]");
+  if (p->n_min < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: n_min < 0");
+  if ((p->lat == nullptr) != (p->lat_inv == nullptr))
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: lattice and inverse must both be given or both NULL");
+  if (!R || !V || !dt || !alpha || !n_pos || !n_taken)
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: a state array (R, V, dt, alpha, n_pos, n_taken) is NULL");
+  if (!E_hist || !fmax_hist || !E_end || !F_end || !status)
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: an output array (E_hist, fmax_hist, E_end, F_end, status) is NULL");
+  if (!(p->dt_max > 0.0) || !isfinite(p->dt_max))
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: dt_max must be positive and finite");
+  for (int64_t b = 0; b < p->B; ++b) {
+    if (!(dt[b] > 0.0) || !isfinite(dt[b]))
+      return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: dt of replica %lld must be positive and finite", (long long)b);
+    if (p->dt_max < dt[b])
+      return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: dt_max is below dt of replica %lld", (long long)b);
+  }
+  return GDML_OK;
+}
+
+extern "C" int gdml_relax_run(gdml_ctx* ctx, const gdml_relax_params* p, double* R, double* V, double* dt, double* alpha,
+                              int64_t* n_pos, int64_t* n_taken, int64_t max_steps, int64_t record_every, double* R_rec,
+                              double* E_hist, double* fmax_hist, double* E_end, double* F_end, int64_t* status,
+                              int64_t* first_bad_step) {
+  GDML_TRY(relax_check(ctx, p, R, V, dt, alpha, n_pos, n_taken, max_steps, record_every, R_rec, E_hist, fmax_hist, E_end, F_end,
+                       status));
+  if (!ctx) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: ctx is NULL");
+  Model& md = ctx->model;
+  if (!md.xp) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_relax_run: upload a model first");
+  if (md.N != p->N) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_relax_run: N = %d but the model has %d atoms", p->N, md.N);
+  const int64_t B = p->B;
+  const int n3 = 3 * p->N;
+  if (first_bad_step)
+    for (int64_t b = 0; b < B; ++b) first_bad_step[b] = -1;
+  if (B == 0) return GDML_OK;
+  HIP_CHECK(ctx, hipSetDevice(ctx->device));
+
+  const int64_t nc = B * n3;
+  const int64_t n_eval_max = max_steps + 1;
+  // evaluations per chunk, and frames of R per chunk where they are recorded
+  int64_t chunk_steps = (int64_t)ctx_opt(ctx, "predict.relax_chunk_steps", 32.0);
+  if (chunk_steps < 1) chunk_steps = 1;
+  if (chunk_steps > n_eval_max) chunk_steps = n_eval_max;
+  int64_t chunk_frames = 0;
+  if (R_rec) {
+    chunk_frames = MD_CHUNK_BYTES / (nc * 8);
+    const int64_t opt = (int64_t)ctx_opt(ctx, "predict.md_chunk_frames", 0.0);
+    if (opt > 0 && opt < chunk_frames) chunk_frames = opt;
+    if (chunk_frames < 1) chunk_frames = 1;
+    if (chunk_frames > chunk_steps) chunk_frames = chunk_steps;
+  }
+
+  const int D = md.D;
+  const bool fused = B <= MD_STEP_MAX_Q && D >= 1 && D <= 256 && n3 <= MD_STEP_MAX_COORDS && !ctx->profiling &&
+                     ctx_opt_i(ctx, "predict.relax_fused", 1) != 0;
+  const int64_t MP = md.M * md.P;
+  int rows = ctx_opt_i(ctx, "predict.fused_rows", 16);  // the row split of predict_fused: at most 4 x 256 wavefronts
+  if (rows < 2) rows = 2;
+  while ((MP + rows - 1) / rows > 1024) rows *= 2;
+  const int n_wg = (int)(((MP + rows - 1) / rows + 3) / 4);
+
+  // one allocation: two halves of R (the general route works in the first) | V | F | F', E' of the general route's prediction
+  // | E | dt | alpha | n_pos | n_taken | status | bad | a chunk of the history (E, f_atom) and of frames | partials, tickets
+  const int64_t n_state = 4 * nc + (fused ? 0 : nc + B) + 8 * B;
+  const int64_t n_chunk = 2 * chunk_steps * B + chunk_frames * nc;
+  const int64_t n_part = fused ? (int64_t)B * n_wg * (D + 1) + MD_STEP_MAX_Q : 0;
+  double* buf = nullptr;
+  GDML_TRY(ctx_alloc(ctx, (void**)&buf, (n_state + n_chunk + n_part) * 8));
+  auto drop = [&](int rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)ctx_free(ctx, buf);
+    return rc;
+  };
+  double* half[2] = {buf, buf + nc};
+  int cur = 0;  // the half that holds the current positions
+  double* d_V = buf + 2 * nc;
+  double* d_F = d_V + nc;
+  double* d_Ft = d_F + nc;
+  double* d_Et = d_Ft + (fused ? 0 : nc);
+  double* d_E = d_Et + (fused ? 0 : B);
+  double* d_dt = d_E + B;
+  double* d_alpha = d_dt + B;
+  int64_t* d_npos = (int64_t*)(d_alpha + B);
+  int64_t* d_ntaken = d_npos + B;
+  int64_t* d_status = d_ntaken + B;
+  int64_t* d_bad = d_status + 2 * B;
+  double* c_E = (double*)(d_bad + B);
+  double* c_fat = c_E + chunk_steps * B;
+  double* c_R = c_fat + chunk_steps * B;
+  double* d_part = c_R + chunk_frames * nc;
+  unsigned* d_counter = (unsigned*)(d_part + (int64_t)B * n_wg * (D + 1));
+
+  hipStream_t st = ctx->stream;
+  DROP_HIP(hipMemcpyAsync(half[0], R, (size_t)nc * 8, hipMemcpyHostToDevice, st));
+  DROP_HIP(hipMemcpyAsync(d_V, V, (size_t)nc * 8, hipMemcpyHostToDevice, st));
+  DROP_HIP(hipMemcpyAsync(d_dt, dt, (size_t)B * 8, hipMemcpyHostToDevice, st));
+  DROP_HIP(hipMemcpyAsync(d_alpha, alpha, (size_t)B * 8, hipMemcpyHostToDevice, st));
+  DROP_HIP(hipMemcpyAsync(d_npos, n_pos, (size_t)B * 8, hipMemcpyHostToDevice, st));
+  DROP_HIP(hipMemcpyAsync(d_ntaken, n_taken, (size_t)B * 8, hipMemcpyHostToDevice, st));
+  md_fill_i64_kernel<<<ceil_div(3 * B, 256), 256, 0, st>>>(d_status, 3 * B, -1);  // status and bad
+  if (fused) DROP_HIP(hipMemsetAsync(d_counter, 0, MD_STEP_MAX_Q * 8, st));
+  // the caller's arrays are pageable: the copies above have to be through before they may change
+  DROP_HIP(hipStreamSynchronize(st));
+
+  RelaxConst C;
+  C.n3 = n3;
+  C.f_scale = p->f_scale;
+  C.fmax = p->fmax;
+  C.dt_max = p->dt_max;
+  C.max_step = p->max_step;
+  C.f_inc = p->f_inc;
+  C.f_dec = p->f_dec;
+  C.alpha_start = p->alpha_start;
+  C.f_alpha = p->f_alpha;
+  C.n_min = p->n_min;
+  RelaxState S = {d_V, d_F, d_E, d_dt, d_alpha, d_npos, d_ntaken, d_status, d_bad};
+
+  RelaxStepArgs A;
+  memset(&A, 0, sizeof(A));
+  if (fused) {
+    A.M.xp = md.xp; A.M.jap = md.jap; A.M.aE = md.has_aE ? md.aE : nullptr;
+    A.M.MP = MP; A.M.D = D; A.M.N = p->N; A.M.sig = md.sig; A.M.rows_per_wave = rows;
+    A.M.part = d_part; A.M.counter = d_counter; A.C = C; A.S = S;
+    if (p->lat && p->lat_inv) {
+      memcpy(A.M.L.lat, p->lat, sizeof(A.M.L.lat));
+      memcpy(A.M.L.inv, p->lat_inv, sizeof(A.M.L.inv));
+      A.M.L.use = 1;
+    }
+  }
+  int KPL = 1;
+  while (KPL * 64 < D) KPL <<= 1;
+
+  // status (B,2), bad (B) and the chunk's history lie side by side: ONE copy per chunk brings them to the host
+  const int64_t n_out = 3 * B + 2 * chunk_steps * B;
+  std::vector<int64_t> h_out((size_t)n_out, -1);
+  const int64_t* h_flags = h_out.data();
+  const double* h_E = (const double*)(h_out.data() + 3 * B);
+  const double* h_fat = h_E + chunk_steps * B;
+  int64_t t = 0, frames_done = 0;
+  bool active = true, any_bad = false;
+  while (t <= max_steps && active && !any_bad) {
+    const int64_t t0 = t;
+    int64_t in_chunk = 0;
+    for (; t <= max_steps && t - t0 < chunk_steps; ++t) {
+      const bool rec = R_rec && t % record_every == 0;
+      if (rec && in_chunk == chunk_frames) break;
+      RelaxSlot sl = {c_E + (t - t0) * B, c_fat + (t - t0) * B, rec ? c_R + in_chunk * nc : nullptr};
+      if (rec) ++in_chunk;
+      const int last = t == max_steps;
+      if (fused) {
+        A.sl = sl; A.t = t; A.last = last;
+        A.inR = half[cur]; A.outR = half[cur ^ 1];
+        const dim3 grid((unsigned)n_wg, (unsigned)B);
+        switch (KPL) {
+          case 1: hipLaunchKernelGGL(relax_step_kernel<1>, grid, dim3(256), 0, st, A); break;
+          case 2: hipLaunchKernelGGL(relax_step_kernel<2>, grid, dim3(256), 0, st, A); break;
+          default: hipLaunchKernelGGL(relax_step_kernel<4>, grid, dim3(256), 0, st, A); break;
+        }
+        cur ^= 1;
+      } else {
+        // the timer of the previous evaluation's prediction is dropped unread: reading it would wait for it on the host
+        ctx->phase_pending.clear();
+        DROP_TRY(gdml_predict_dev(ctx, half[0], B, p->lat, p->lat_inv, d_Et, d_Ft));
+        relax_update_kernel<<<(unsigned)B, 256, 0, st>>>(C, S, sl, half[0], d_Ft, d_Et, t, last);
+      }
+    }
+    DROP_HIP(hipGetLastError());
+    if (in_chunk > 0) {
+      DROP_HIP(hipMemcpyAsync(R_rec + frames_done * nc, c_R, (size_t)(in_chunk * nc) * 8, hipMemcpyDeviceToHost, st));
+      frames_done += in_chunk;
+    }
+    DROP_HIP(hipMemcpyAsync(h_out.data(), d_status, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
+    DROP_HIP(hipStreamSynchronize(st));
+    memcpy(E_hist + t0 * B, h_E, (size_t)((t - t0) * B) * 8);
+    memcpy(fmax_hist + t0 * B, h_fat, (size_t)((t - t0) * B) * 8);
+    active = false;
+    for (int64_t b = 0; b < B; ++b) {
+      active |= h_flags[(size_t)(2 * b)] < 0;
+      any_bad |= h_flags[(size_t)(2 * B + b)] >= 0;
+    }
+  }
+  DROP_HIP(hipMemcpyAsync(R, half[cur], (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(hipMemcpyAsync(V, d_V, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(hipMemcpyAsync(F_end, d_F, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(hipMemcpyAsync(E_end, d_E, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(hipMemcpyAsync(dt, d_dt, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(hipMemcpyAsync(alpha, d_alpha, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(hipMemcpyAsync(n_pos, d_npos, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(hipMemcpyAsync(n_taken, d_ntaken, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(hipStreamSynchronize(st));
+  memcpy(status, h_flags, (size_t)(2 * B) * 8);
+  if (first_bad_step) memcpy(first_bad_step, h_flags + 2 * B, (size_t)B * 8);
+
+  // evaluations made; a frozen replica repeats its last history values and its end positions up to there (the launches
+  // behind its freeze wrote nothing for it)
+  int64_t n_made = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t e = h_flags[(size_t)(2 * b + 1)];
+    n_made = std::max(n_made, e < 0 ? t : e + 1);
+  }
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t e = h_flags[(size_t)(2 * b + 1)];
+    if (e < 0) continue;
+    for (int64_t u = e + 1; u < n_made; ++u) {
+      E_hist[u * B + b] = E_hist[e * B + b];
+      fmax_hist[u * B + b] = fmax_hist[e * B + b];
+      if (R_rec && u % record_every == 0) memcpy(R_rec + (u / record_every) * nc + b * n3, R + b * n3, (size_t)n3 * 8);
+    }
+  }
   return drop(GDML_OK);
 }

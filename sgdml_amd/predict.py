@@ -443,6 +443,69 @@ class GDMLPredict(object):
         out['step_end'] = step0 + int(n_steps)
         return out
 
+    # ---- geometry relaxation on the device (gdml_relax_run, csrc/md.hip)
+
+    def relax(self, R0, fmax, max_steps=1000, dt_start=0.1, dt_max=None, max_step=0.2, n_min=5, f_inc=1.1, f_dec=0.5,
+              alpha_start=0.1, f_alpha=0.99, state=None, lattice=None, f_unit=1.0, record_every=0):
+        """Minimise the energy of B independent geometries on the device by FIRE (Bitzek et al., PRL 97, 170201 (2006)) in the
+        form ASE's FIRE uses: unit masses, gradient g = f_unit * F with F the forces of predict(), the whole step clipped to
+        max_step.  R0: (B,3N) or (3N,).  A geometry is converged when its largest atomic |g| is below fmax; every geometry
+        takes at most max_steps steps in this call and stops on its own (the others run on).  dt_max=None: 10 dt_start.
+        state: the 'state' of an earlier call ({'V', 'dt', 'alpha', 'n_pos', 'n_taken'}), passed back together with its R_end,
+        continues that run bit for bit; None is a fresh start.  lattice: as in predict() (the cell is fixed, positions are not
+        wrapped).  record_every > 0 also returns 'R' (every record_every-th evaluated geometry, the start included).
+        Returns a dict: 'R_end' (B,3N), 'E_end' (B) and 'F_end' (B,3N) scaled like predict(), 'fmax_end' (B), 'n_steps' (B; steps
+        taken in this call), 'converged' (B, bool), 'E_hist' and 'fmax_hist' (evaluations made, B; a geometry that has stopped
+        repeats its last value) and 'state'.  Runs on the predictor's first device.  ValueError for non-finite or out-of-range
+        parameters and misshapen input before anything is launched; FloatingPointError naming geometry and evaluation when a
+        value is not finite (a NaN in R0 included: evaluation 0)."""
+        n3 = 3 * self.n_atoms
+        R0 = np.asarray(R0, dtype=np.float64)
+        if R0.ndim == 1:
+            R0 = R0[None, :]
+        if R0.ndim == 3:
+            R0 = R0.reshape(R0.shape[0], -1)
+        if R0.ndim != 2 or R0.shape[1] != n3:
+            raise ValueError('R0 must be (B, {}) for this model, got shape {}'.format(n3, R0.shape))
+        B = R0.shape[0]
+        if dt_max is None:
+            dt_max = 10.0 * dt_start
+        for name, val in (('fmax', fmax), ('dt_start', dt_start), ('dt_max', dt_max), ('max_step', max_step), ('f_inc', f_inc),
+                          ('f_dec', f_dec), ('alpha_start', alpha_start), ('f_alpha', f_alpha), ('f_unit', f_unit)):
+            if not np.isfinite(val):
+                raise ValueError('{} must be finite'.format(name))
+        if int(max_steps) != max_steps or int(record_every) != record_every or int(n_min) != n_min:
+            raise ValueError('max_steps, record_every and n_min must be integers')
+        if state is None:
+            state = dict(V=np.zeros((B, n3)), dt=np.full(B, float(dt_start)), alpha=np.full(B, float(alpha_start)),
+                         n_pos=np.zeros(B, dtype=np.int64), n_taken=np.zeros(B, dtype=np.int64))
+        else:
+            missing = [k for k in ('V', 'dt', 'alpha', 'n_pos', 'n_taken') if k not in state]
+            if missing:
+                raise ValueError('state lacks {}'.format(missing))
+            if np.shape(state['V']) != R0.shape:
+                raise ValueError("state['V'] must have the shape of R0 {}, got {}".format(R0.shape, np.shape(state['V'])))
+            if not all(np.isfinite(np.asarray(state[k], dtype=np.float64)).all() for k in ('V', 'dt', 'alpha')):
+                raise ValueError('state must be finite')
+        # a NaN start is not a usage error: the run reports the geometry and the evaluation (FloatingPointError)
+        out = self._ctx.relax_run(R0, fmax, max_steps, state, dt_max, max_step=max_step, n_min=n_min, f_inc=f_inc, f_dec=f_dec,
+                                  alpha_start=alpha_start, f_alpha=f_alpha, f_scale=self.std * float(f_unit),
+                                  record_every=record_every, lat_and_inv=self._lat_and_inv(lattice))
+        bad = out.pop('first_bad_step')
+        if (bad >= 0).any():
+            b = int(np.argmax(bad >= 0))
+            raise FloatingPointError('geometry {} stopped being finite at evaluation {}'.format(b, int(bad[b])))
+        status = out.pop('status')
+        out.pop('n_made')
+        out['F_end'] *= self.std
+        for k in ('E_end', 'E_hist'):
+            out[k] *= self.std
+            out[k] += self.c
+        out['n_steps'] = status[:, 1].copy()
+        out['converged'] = status[:, 0] == 1
+        out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
+        return out
+
     # ---- path-integral molecular dynamics on the device (gdml_pimd_run, csrc/md.hip)
 
     def run_pimd(self, R0, V0, masses, dt, n_steps, beads, kT, hbar, record_every=1, thermostat=None, gamma_centroid=0.0,
