@@ -196,6 +196,31 @@ def i64(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _lat_pair(lat_and_inv):
+    """(lattice, inverse) as contiguous fp64 arrays for _ptr(), or (None, None)."""
+    if lat_and_inv is None:
+        return None, None
+    return f64(lat_and_inv[0]), f64(lat_and_inv[1])
+
+
+def _state_copies(R, V, shape):
+    """Copies of R and V in `shape` (the trajectory entries overwrite them with the end state)."""
+    R = np.array(R, dtype=np.float64).reshape(shape)
+    V = np.array(V, dtype=np.float64).reshape(shape)
+    if V.shape != R.shape:
+        raise ValueError('R and V differ in shape: {} and {}'.format(R.shape, V.shape))
+    return R, V
+
+
+def _record_arrays(record, shapes):
+    """One uninitialised array per field of `shapes` that `record` names, None for the others."""
+    return {k: (np.empty(shp) if k in record else None) for k, shp in shapes.items()}
+
+
+def _recorded(rec):
+    return {k: v for k, v in rec.items() if v is not None}
+
+
 def _digest(a):
     """Content fingerprint of a contiguous array (xxhash when present, else md5)."""
     try:
@@ -380,9 +405,7 @@ class Context(object):
         D = n_atoms * (n_atoms - 1) // 2
         xd = np.empty((M, D))
         gd = np.empty((M, D, 3))
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         self._check(self._lib.gdml_desc_from_R(self._h, _ptr(R), M, n_atoms, _ptr(lat), _ptr(lat_inv),
                                                _ptr(xd), _ptr(gd)))
         return xd, gd
@@ -559,9 +582,7 @@ class Context(object):
             B = R.shape[0]
         E = np.empty(B) if return_E else None
         F = np.empty((B, 3 * n_atoms))
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         if R is None or B <= self.max_query_batch:
             self._check(self._lib.gdml_predict(self._h, _ptr(R), B, _ptr(lat), _ptr(lat_inv), _ptr(E), _ptr(F)))
             return E, F
@@ -574,33 +595,32 @@ class Context(object):
                                                _ptr(F[b0:b1])))
         return E, F
 
+    def _masses(self, mass):
+        mass = f64(mass).ravel()
+        if mass.size != self.model_n_atoms:
+            raise ValueError('{} masses for {} atoms'.format(mass.size, self.model_n_atoms))
+        return mass
+
     def md_run(self, R, V, mass, dt, n_steps, record_every=1, f_scale=1.0, thermostat=0, gamma=0.0, kT=0.0, seed=0, step0=0,
                lat_and_inv=None, record=('R',)):
         """gdml_md_run: B replicas (R, V: (B,3N)) advance n_steps on the device.  Returns a dict with the end state 'R_end',
         'V_end', the frames 'E' (n_rec,B; unscaled E'), 'Ekin' (n_rec,B) and those of 'R', 'V', 'F' (n_rec,B,3N) named in
         `record`, and 'first_bad_step' (B; -1 = every value stayed finite)."""
         n3 = 3 * self.model_n_atoms
-        R = np.array(R, dtype=np.float64).reshape(-1, n3)  # copies: the call overwrites them with the end state
-        V = np.array(V, dtype=np.float64).reshape(-1, n3)
-        if V.shape != R.shape:
-            raise ValueError('R and V differ in shape: {} and {}'.format(R.shape, V.shape))
+        R, V = _state_copies(R, V, (-1, n3))
         B = R.shape[0]
-        mass = f64(mass).ravel()
-        if mass.size != self.model_n_atoms:
-            raise ValueError('{} masses for {} atoms'.format(mass.size, self.model_n_atoms))
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        mass = self._masses(mass)
+        lat, lat_inv = _lat_pair(lat_and_inv)
         n_steps, record_every = int(n_steps), int(record_every)
         n_rec = n_steps // record_every if (n_steps > 0 and record_every > 0) else 0
-        rec = {k: (np.empty((n_rec, B, n3)) if k in record else None) for k in ('R', 'V', 'F')}
+        rec = _record_arrays(record, {k: (n_rec, B, n3) for k in ('R', 'V', 'F')})
         E, Ek = np.empty((n_rec, B)), np.empty((n_rec, B))
         bad = np.full(B, -1, dtype=np.int64)
         prm = MDParams(B, self.model_n_atoms, float(dt), _ptr(mass), float(f_scale), _ptr(lat), _ptr(lat_inv), int(thermostat),
                        float(gamma), float(kT), int(seed), int(step0))
         self._check(self._lib.gdml_md_run(self._h, C.byref(prm), _ptr(R), _ptr(V), n_steps, record_every, _ptr(rec['R']),
                                           _ptr(rec['V']), _ptr(rec['F']), _ptr(E), _ptr(Ek), _ptr(bad)))
-        out = {k: v for k, v in rec.items() if v is not None}
+        out = _recorded(rec)
         out.update(R_end=R, V_end=V, E=E, Ekin=Ek, first_bad_step=bad)
         return out
 
@@ -618,21 +638,14 @@ class Context(object):
         n3, P = 3 * self.model_n_atoms, int(beads)
         if P < 1:
             raise ValueError('beads must be at least 1, got {}'.format(beads))
-        R = np.array(R, dtype=np.float64).reshape(-1, P, n3)  # copies: the call overwrites them with the end state
-        V = np.array(V, dtype=np.float64).reshape(-1, P, n3)
-        if V.shape != R.shape:
-            raise ValueError('R and V differ in shape: {} and {}'.format(R.shape, V.shape))
+        R, V = _state_copies(R, V, (-1, P, n3))
         B = R.shape[0]
-        mass = f64(mass).ravel()
-        if mass.size != self.model_n_atoms:
-            raise ValueError('{} masses for {} atoms'.format(mass.size, self.model_n_atoms))
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        mass = self._masses(mass)
+        lat, lat_inv = _lat_pair(lat_and_inv)
         n_steps, record_every = int(n_steps), int(record_every)
         n_rec = n_steps // record_every if (n_steps > 0 and record_every > 0) else 0
-        shapes = {'R': (n_rec, B, P, n3), 'V': (n_rec, B, P, n3), 'F': (n_rec, B, P, n3), 'E': (n_rec, B, P), 'Rc': (n_rec, B, n3)}
-        rec = {k: (np.empty(shp) if k in record else None) for k, shp in shapes.items()}
+        rec = _record_arrays(record, {'R': (n_rec, B, P, n3), 'V': (n_rec, B, P, n3), 'F': (n_rec, B, P, n3), 'E': (n_rec, B, P),
+                                      'Rc': (n_rec, B, n3)})
         ring = np.empty((n_rec, B, 5))
         bad = np.full(B, -1, dtype=np.int64)
         prm = PIMDParams(B, self.model_n_atoms, P, float(dt), _ptr(mass), float(f_scale), _ptr(lat), _ptr(lat_inv),
@@ -640,7 +653,7 @@ class Context(object):
         self._check(self._lib.gdml_pimd_run(self._h, C.byref(prm), _ptr(R), _ptr(V), n_steps, record_every, _ptr(rec['R']),
                                             _ptr(rec['V']), _ptr(rec['F']), _ptr(rec['E']), _ptr(rec['Rc']), _ptr(ring),
                                             _ptr(bad)))
-        out = {k: v for k, v in rec.items() if v is not None}
+        out = _recorded(rec)
         out.update(R_end=R, V_end=V, ring=ring, first_bad_step=bad)
         return out
 
@@ -662,19 +675,14 @@ class Context(object):
         (evaluations made), 'E_hist', 'fmax_hist' (n_made,B), the frames 'R' (every record_every-th evaluation; only with
         record_every > 0) and 'first_bad_step' (B; -1 = every value stayed finite)."""
         n3 = 3 * self.model_n_atoms
-        R = np.array(R, dtype=np.float64).reshape(-1, n3)  # copies: the call overwrites the state with the end state
+        R, V = _state_copies(R, state['V'], (-1, n3))
         B = R.shape[0]
-        V = np.array(state['V'], dtype=np.float64).reshape(-1, n3)
-        if V.shape != R.shape:
-            raise ValueError('R and V differ in shape: {} and {}'.format(R.shape, V.shape))
         dt, alpha = (np.array(state[k], dtype=np.float64).ravel() for k in ('dt', 'alpha'))
         n_pos, n_taken = (np.array(state[k], dtype=np.int64).ravel() for k in ('n_pos', 'n_taken'))
         for k, a in (('dt', dt), ('alpha', alpha), ('n_pos', n_pos), ('n_taken', n_taken)):
             if a.shape != (B,):
                 raise ValueError("state['{}'] must have one entry per geometry ({}), got shape {}".format(k, B, a.shape))
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         max_steps, record_every = int(max_steps), int(record_every)
         n_eval = max(max_steps, 0) + 1
         R_rec = np.empty((max(max_steps, 0) // record_every + 1, B, n3)) if record_every > 0 else None
@@ -704,9 +712,7 @@ class Context(object):
         R = f64(R).reshape(-1, n3)
         B = R.shape[0]
         E, F, W = np.empty(B), np.empty((B, n3)), np.empty((B, 3, 3))
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         for b0 in range(0, max(B, 1), self.max_query_batch):
             b1 = min(B, b0 + self.max_query_batch)
             self._check(self._lib.gdml_predict_virial(self._h, _ptr(R[b0:b1]), b1 - b0, _ptr(lat), _ptr(lat_inv),
@@ -715,9 +721,7 @@ class Context(object):
 
     def predict_virial_dev(self, R_dev, B, E_dev, F_dev, W_dev, lat_and_inv=None):
         """gdml_predict_virial_dev on device pointers (ints or c_void_p; E_dev / F_dev may be None)."""
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         self._check(self._lib.gdml_predict_virial_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), E_dev, F_dev,
                                                       W_dev))
 
@@ -733,9 +737,7 @@ class Context(object):
         R = f64(R).reshape(-1, n3)
         B = R.shape[0]
         E, F, H = np.empty(B), np.empty((B, n3)), np.empty((B, n3, n3))
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         step = self.hessian_batch()
         for b0 in range(0, max(B, 1), step):
             b1 = min(B, b0 + step)
@@ -745,9 +747,7 @@ class Context(object):
 
     def predict_hessian_dev(self, R_dev, B, E_dev, F_dev, H_dev, lat_and_inv=None):
         """gdml_predict_hessian_dev on device pointers (ints or c_void_p; E_dev / F_dev may be None)."""
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         self._check(self._lib.gdml_predict_hessian_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), E_dev, F_dev,
                                                        H_dev))
 
@@ -770,9 +770,7 @@ class Context(object):
         n3 = 3 * self.n_atoms
         R = f64(R).reshape(-1, n3)
         B = R.shape[0]
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         Kx, kqq = np.empty((B * n3, self.n_train * n3)), np.empty((B, n3, n3))
         self._check(self._lib.gdml_uncert_cross(self._h, _ptr(R), B, _ptr(lat), _ptr(lat_inv), _ptr(Kx), _ptr(kqq)))
         return Kx, kqq
@@ -784,18 +782,14 @@ class Context(object):
         n3 = 3 * self.n_atoms
         R = f64(R).reshape(-1, n3)
         B = R.shape[0]
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         out = np.empty((B, n3, n3) if full else (B, n3))
         self._check(self._lib.gdml_predict_cov(self._h, _ptr(R), B, _ptr(lat), _ptr(lat_inv), int(bool(full)), _ptr(out)))
         return out
 
     def predict_cov_dev(self, R_dev, B, cov_dev, lat_and_inv=None, full=False):
         """gdml_predict_cov_dev on device pointers (ints or c_void_p)."""
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         self._check(self._lib.gdml_predict_cov_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), int(bool(full)),
                                                    cov_dev))
 
@@ -807,18 +801,14 @@ class Context(object):
         n3 = 3 * self.n_atoms
         R = f64(R).reshape(-1, n3)
         B = R.shape[0]
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         out = np.empty((B, n3, n3) if full else (B, n3))
         self._check(self._lib.gdml_predict_cov_few(self._h, _ptr(R), B, _ptr(lat), _ptr(lat_inv), int(bool(full)), _ptr(out)))
         return out
 
     def predict_cov_few_dev(self, R_dev, B, cov_dev, lat_and_inv=None, full=False):
         """gdml_predict_cov_few_dev on device pointers (ints or c_void_p)."""
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         self._check(self._lib.gdml_predict_cov_few_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), int(bool(full)),
                                                        cov_dev))
 
@@ -900,9 +890,7 @@ class Context(object):
         n3 = 3 * self.n_atoms
         R = f64(R).reshape(-1, n3)
         B = R.shape[0]
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         n_select = int(n_select)
         idx, gain, gain0 = np.zeros(max(n_select, 0), dtype=np.int64), np.zeros(max(n_select, 0)), np.empty(B)
         k, info = C.c_int64(0), C.c_int(0)
@@ -917,9 +905,7 @@ class Context(object):
         R = f64(R).reshape(-1, 3 * n_atoms)
         F_ref = f64(F_ref).reshape(R.shape[0], 3 * n_atoms)
         E_ref = None if E_ref is None else f64(E_ref).ravel()
-        lat = lat_inv = None
-        if lat_and_inv is not None:
-            lat, lat_inv = f64(lat_and_inv[0]), f64(lat_and_inv[1])
+        lat, lat_inv = _lat_pair(lat_and_inv)
         out = np.empty(8)
         self._check(self._lib.gdml_predict_errors(self._h, _ptr(R), R.shape[0], _ptr(lat), _ptr(lat_inv), float(std),
                                                   float(c), _ptr(E_ref), _ptr(F_ref), _ptr(out)))

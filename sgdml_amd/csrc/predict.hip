@@ -21,6 +21,7 @@
 #include <stddef.h>
 
 #include "common.h"
+#include "fused_core.h"
 #include <chrono>
 #include <thread>
 
@@ -1205,46 +1206,17 @@ extern "C" int gdml_set_alphas(gdml_ctx* ctx, const double* alphas_F, const doub
 // B <= 8 queries, D <= 256 (N <= 23), 3 N B <= 384 coordinates (3 KB of kernel arguments: six queries at N = 21).
 // ------------------------------------------------------------------------------------------
 #define FUSED_MAX_COORDS 384
-#define FUSED_MAX_Q 8
 struct FusedArgs {
-  const double* xp;
-  const double* jap;
-  const double* aE;
-  int64_t MP;
-  int D, N, B, want_E;
-  double sig;
-  int rows_per_wave;
-  double* part;                // (B, n_wg, D + 1) workgroup partials: F_x, then E
-  unsigned* counter;           // [q] workgroups of query q that have finished; [FUSED_MAX_Q] queries done
+  FusedModel M;
+  int B, want_E;
   double* out;                 // host-mapped: E (B), F (B, 3N)
   unsigned long long* flag;    // host-mapped
   unsigned long long seq;
-  Lattice L;
   double R[FUSED_MAX_COORDS];  // (B, N, 3)
 };
 typedef const __attribute__((address_space(4))) double* kernarg_dp;
 
-// r_i - r_j of query q (minimum image with a lattice: desc.py:44-77), from the kernel-argument copy of R
-__device__ __forceinline__ void fused_pair_diff(kernarg_dp R, const Lattice& L, int N, int q, int i, int j, double (&d)[3]) {
-  const int bi = (q * N + i) * 3, bj = (q * N + j) * 3;
-  double d0 = R[bi] - R[bj], d1 = R[bi + 1] - R[bj + 1], d2 = R[bi + 2] - R[bj + 2];
-  if (L.use) {
-    const double c0 = rint(L.inv[0] * d0 + L.inv[1] * d1 + L.inv[2] * d2);
-    const double c1 = rint(L.inv[3] * d0 + L.inv[4] * d1 + L.inv[5] * d2);
-    const double c2 = rint(L.inv[6] * d0 + L.inv[7] * d1 + L.inv[8] * d2);
-    d0 -= L.lat[0] * c0 + L.lat[1] * c1 + L.lat[2] * c2;
-    d1 -= L.lat[3] * c0 + L.lat[4] * c1 + L.lat[5] * c2;
-    d2 -= L.lat[6] * c0 + L.lat[7] * c1 + L.lat[8] * c2;
-  }
-  d[0] = d0; d[1] = d1; d[2] = d2;
-}
-__device__ __forceinline__ void fused_pair_of(int k, int& i, int& j) {  // k = i (i - 1) / 2 + j, i > j
-  i = (int)((1.0 + sqrt(1.0 + 8.0 * (double)k)) * 0.5);
-  while (i * (i - 1) / 2 > k) --i;
-  while ((i + 1) * i / 2 <= k) ++i;
-  j = k - i * (i - 1) / 2;
-}
-
+// The predictor's share is fused_core.h's, the geometry read from the kernel-argument copy of R.
 // VIRIAL (gdml_predict_virial): the query's last workgroup also sums W = sum_k F_x[k] d_k (x) d_k / |d_k|^3 from the pair
 // vectors it recomputes for the Jacobian, and writes it as (B, 9) behind F in the mapped block.
 template <int KPL, bool VIRIAL = false>
@@ -1254,134 +1226,20 @@ __global__ void __launch_bounds__(256) predict_fused_kernel(FusedArgs A) {
   __shared__ double s_g[KPL * 64 * 3];
   __shared__ unsigned s_ticket;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int D = A.D, N = A.N, B = A.B;
+  const int N = A.M.N, B = A.B;
   const int q = (int)blockIdx.y;  // a workgroup serves ONE query: grid = (row shares, queries)
-  kernarg_dp Rk = (kernarg_dp)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() +
-                               offsetof(FusedArgs, R));
-  const double sig = A.sig, inv_sig = 1.0 / sig;
-  const double sqrt5 = 2.23606797749978969641;
-  const double fact = 5.0 / (3.0 * sig * sig * sig);
-  const double dscale = 5.0 / sig;
-  const double inv_3sig = 1.0 / (3.0 * sig);
-
-  // ---- query descriptor (same arithmetic as desc_kernel)
-  double x[KPL], Fx[KPL], E = 0.0;
-#pragma unroll
-  for (int t = 0; t < KPL; ++t) {
-    const int k = lane + 64 * t;
-    double v = 0.0;
-    if (k < D) {
-      int i, j;
-      fused_pair_of(k, i, j);
-      double d[3];
-      fused_pair_diff(Rk, A.L, N, q, i, j, d);
-      v = 1.0 / sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    }
-    x[t] = v;
-    Fx[t] = 0.0;
-  }
-
-  // ---- this wavefront's table rows (the row loop of predict_kernel)
-  const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
-  const int64_t r0 = gw * A.rows_per_wave;
-  const int64_t r1 = (r0 + A.rows_per_wave < A.MP) ? r0 + A.rows_per_wave : A.MP;
-  const bool has_aE = A.aE != nullptr;
-  auto load_row = [&](int64_t r, double (&X)[KPL], double (&JA)[KPL], double& ae) {
-#pragma unroll
-    for (int t = 0; t < KPL; ++t) {
-      const int k = lane + 64 * t;
-      const int kc = k < D ? k : D - 1;
-      const double xv = __hip_atomic_load(A.xp + r * D + kc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-      const double jv = __hip_atomic_load(A.jap + r * D + kc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-      X[t] = (k < D) ? xv : 0.0;
-      JA[t] = (k < D) ? jv : 0.0;
-    }
-    ae = has_aE ? __hip_atomic_load(A.aE + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) : 0.0;
-  };
-  auto row = [&](const double (&X)[KPL], const double (&JA)[KPL], double ae) {
-    double d[KPL];
-    double s2 = 0.0, sa = 0.0;
-#pragma unroll
-    for (int t = 0; t < KPL; ++t) {
-      d[t] = x[t] - X[t];
-      s2 += d[t] * d[t];
-      sa += d[t] * JA[t];
-    }
-    s2 = wave_sum(s2);
-    sa = wave_sum(sa);
-    const double nrm = sqrt5 * sqrt(s2);
-    const double ex = exp(-nrm * inv_sig);
-    const double b = fact * ex;
-    const double b2 = b * (nrm + sig);
-    double w1 = dscale * sa * b;
-    E += sa * b2;
-    if (has_aE) {
-      w1 += ae * b2;
-      E += ae * (1.0 + (nrm * inv_sig) * (1.0 + nrm * inv_3sig)) * ex;
-    }
-#pragma unroll
-    for (int t = 0; t < KPL; ++t) Fx[t] += w1 * d[t] - b2 * JA[t];
-  };
-  if (r0 < r1) {
-    double X0[KPL], JA0[KPL], X1[KPL], JA1[KPL], ae0, ae1;
-    int64_t r = r0;
-    load_row(r, X0, JA0, ae0);
-    for (; r + 1 < r1; r += 2) {
-      load_row(r + 1, X1, JA1, ae1);
-      row(X0, JA0, ae0);
-      load_row(r + 2 < r1 ? r + 2 : r1 - 1, X0, JA0, ae0);
-      row(X1, JA1, ae1);
-    }
-    if (r < r1) row(X0, JA0, ae0);
-  }
-
-  // ---- the workgroup's four wavefronts -> one partial (padding lanes hold zeros)
-#pragma unroll
-  for (int t = 0; t < KPL; ++t) s_fx[wave][lane + 64 * t] = Fx[t];
-  if (lane == 0) s_E[wave] = E;
-  __syncthreads();
-  const int n_wg = (int)gridDim.x;
-  double* my_part = A.part + ((int64_t)q * n_wg + blockIdx.x) * (D + 1);
-  for (int k = tid; k < D; k += 256) my_part[k] = (s_fx[0][k] + s_fx[1][k]) + (s_fx[2][k] + s_fx[3][k]);
-  if (tid == 0) my_part[D] = (s_E[0] + s_E[1]) + (s_E[2] + s_E[3]);
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_ticket = atomicAdd(A.counter + q, 1u);
-  __syncthreads();
-  if (s_ticket != gridDim.x - 1) return;
+  kernarg_dp Rq = (kernarg_dp)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() +
+                               offsetof(FusedArgs, R)) + q * N * 3;
+  if (!fused_partials<KPL>(A.M, Rq, s_fx, s_E, s_ticket)) return;
 
   // ---- the query's last workgroup: every partial of this query is visible
-  __threadfence();
   double* fxs = &s_fx[0][0];
-  const double* qpart = A.part + (int64_t)q * n_wg * (D + 1);
-  for (int k = tid; k < D + 1; k += 256) {
-    double s = 0.0;
-    for (int w0 = 0; w0 < n_wg; w0 += 8) {
-      double v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int w = w0 + u < n_wg ? w0 + u : n_wg - 1;
-        v[u] = __hip_atomic_load(qpart + (int64_t)w * (D + 1) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (w0 + u < n_wg) s += v[u];
-    }
-    if (k < D) fxs[k] = s;
-    else if (A.want_E) A.out[q] = s;
-  }
-  double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // VIRIAL: xx, yy, zz, yz, xz, xy of this thread's pairs
-  for (int k = tid; k < D; k += 256) {  // Jacobian entries (r_i - r_j) / d^3  (desc.py:193-205)
-    int i, j;
-    fused_pair_of(k, i, j);
-    double d[3];
-    fused_pair_diff(Rk, A.L, N, q, i, j, d);
-    const double dist = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    const double inv3 = 1.0 / (dist * dist * dist);
-    s_g[k * 3 + 0] = d[0] * inv3;
-    s_g[k * 3 + 1] = d[1] * inv3;
-    s_g[k * 3 + 2] = d[2] * inv3;
-    if constexpr (VIRIAL) {
+  fused_sum_partials(A.M, fxs, [&](double e) {
+    if (A.want_E) A.out[q] = e;
+  });
+  if constexpr (VIRIAL) {
+    double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // xx, yy, zz, yz, xz, xy of this thread's pairs
+    fused_jacobian(A.M, Rq, s_g, [&](int k, const double (&d)[3], double inv3) {
       const double c = fxs[k] * inv3;  // fxs[k] was written by this thread
       const double c0 = c * d[0], c1 = c * d[1], c2 = c * d[2];
       w[0] += c0 * d[0];
@@ -1390,14 +1248,15 @@ __global__ void __launch_bounds__(256) predict_fused_kernel(FusedArgs A) {
       w[3] += c1 * d[2];
       w[4] += c0 * d[2];
       w[5] += c0 * d[1];
-    }
-  }
-  if constexpr (VIRIAL) {  // fixed tree: per-thread sums -> xor shuffles -> the four wavefronts in order (s_fx[1] is free here)
+    });
+    // fixed tree: per-thread sums -> xor shuffles -> the four wavefronts in order (s_fx[1] is free here)
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
       const double v = wave_sum(w[c]);
       if (lane == 0) s_fx[1][wave * 6 + c] = v;
     }
+  } else {
+    fused_jacobian(A.M, Rq, s_g);
   }
   __syncthreads();
   if constexpr (VIRIAL) {
@@ -1409,25 +1268,15 @@ __global__ void __launch_bounds__(256) predict_fused_kernel(FusedArgs A) {
       W[cc * 3 + r] = v;
     }
   }
-  for (int t = tid; t < 3 * N; t += 256) {  // F = J_x^T F_x  (desc.py:405-408), same order as predict_epilogue_kernel
-    const int a = t / 3, al = t - 3 * a;
-    double s = 0.0;
-    for (int m = 0; m < N; ++m) {
-      if (m == a) continue;
-      const int k = pair_idx(a, m);
-      const double v = s_g[k * 3 + al] * fxs[k];
-      s += (a < m) ? v : -v;
-    }
-    A.out[B + (int64_t)q * 3 * N + t] = s;
-  }
+  for (int t = tid; t < 3 * N; t += 256) A.out[B + (int64_t)q * 3 * N + t] = fused_force(N, s_g, fxs, t);
   __threadfence_system();  // this query's E, F are in host memory before it is counted as done
   __syncthreads();
   if (tid == 0) {
-    A.counter[q] = 0u;
-    const unsigned done = atomicAdd(A.counter + FUSED_MAX_Q, 1u);
+    A.M.counter[q] = 0u;
+    const unsigned done = atomicAdd(A.M.counter + FUSED_MAX_Q, 1u);
     if (done == (unsigned)B - 1) {  // the last query to finish publishes the sequence number
       __threadfence_system();
-      A.counter[FUSED_MAX_Q] = 0u;
+      A.M.counter[FUSED_MAX_Q] = 0u;
       __hip_atomic_store(A.flag, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
@@ -1438,8 +1287,8 @@ static int predict_fused(gdml_ctx* ctx, const double* R, int64_t B, const double
                          double* F_out, double* W_out, int* done) {
   *done = 0;
   Model& md = ctx->model;
-  const int N = md.N, D = md.D;
-  if (B < 1 || B > FUSED_MAX_Q || D > 256 || D < 1 || B * 3 * N > FUSED_MAX_COORDS || ctx->profiling ||
+  const int N = md.N;
+  if (!fused_serves(md, B) || B * 3 * N > FUSED_MAX_COORDS || ctx->profiling ||
       !ctx_opt_i(ctx, "predict.fused", 1))
     return GDML_OK;
   if (!ctx->h_map) {
@@ -1460,45 +1309,22 @@ static int predict_fused(gdml_ctx* ctx, const double* R, int64_t B, const double
     GDML_TRY(ctx_alloc(ctx, (void**)&ctx->d_fused_counter, 64));
     HIP_CHECK(ctx, hipMemsetAsync(ctx->d_fused_counter, 0, 64, ctx->stream));
   }
-  const int64_t MP = md.M * md.P;
-  int rows = ctx_opt_i(ctx, "predict.fused_rows", 16);
-  if (rows < 2) rows = 2;
-  // at most 4 x 256 wavefronts (a few per CU: the launch is latency bound, not throughput bound)
-  while ((MP + rows - 1) / rows > 1024) rows *= 2;
-  const int64_t n_waves = (MP + rows - 1) / rows;
-  const int n_wg = (int)((n_waves + 3) / 4);
+  const FusedPlan plan = fused_plan(ctx, md);
   double* part;
-  GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, (int64_t)n_wg * B * (D + 1) * 8, &part));
+  GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, fused_part_len(md, plan, B) * 8, &part));
   FusedArgs A;
-  A.xp = md.xp; A.jap = md.jap; A.aE = md.has_aE ? md.aE : nullptr;
-  A.MP = MP; A.D = D; A.N = N; A.B = (int)B; A.want_E = E_out != nullptr;
-  A.sig = md.sig; A.rows_per_wave = rows; A.part = part; A.counter = ctx->d_fused_counter;
+  fused_fill(A.M, md, plan, lat, lat_inv, part, ctx->d_fused_counter);
+  A.B = (int)B;
+  A.want_E = E_out != nullptr;
   A.out = ctx->h_map_dev + 8;
   A.flag = (unsigned long long*)ctx->h_map_dev;
   A.seq = ++ctx->fused_seq;
-  memset(&A.L, 0, sizeof(A.L));
-  if (lat && lat_inv) {
-    memcpy(A.L.lat, lat, sizeof(A.L.lat));
-    memcpy(A.L.inv, lat_inv, sizeof(A.L.inv));
-    A.L.use = 1;
-  }
   memcpy(A.R, R, (size_t)B * 3 * N * 8);
-  int KPL = 1;
-  while (KPL * 64 < D) KPL <<= 1;
-  const dim3 grid((unsigned)n_wg, (unsigned)B);
-  if (W_out) {
-    switch (KPL) {
-      case 1: hipLaunchKernelGGL((predict_fused_kernel<1, true>), grid, dim3(256), 0, ctx->stream, A); break;
-      case 2: hipLaunchKernelGGL((predict_fused_kernel<2, true>), grid, dim3(256), 0, ctx->stream, A); break;
-      default: hipLaunchKernelGGL((predict_fused_kernel<4, true>), grid, dim3(256), 0, ctx->stream, A); break;
-    }
-  } else {
-    switch (KPL) {
-      case 1: hipLaunchKernelGGL(predict_fused_kernel<1>, grid, dim3(256), 0, ctx->stream, A); break;
-      case 2: hipLaunchKernelGGL(predict_fused_kernel<2>, grid, dim3(256), 0, ctx->stream, A); break;
-      default: hipLaunchKernelGGL(predict_fused_kernel<4>, grid, dim3(256), 0, ctx->stream, A); break;
-    }
-  }
+  if (W_out)
+    fused_launch(plan, B, ctx->stream, predict_fused_kernel<1, true>, predict_fused_kernel<2, true>,
+                 predict_fused_kernel<4, true>, A);
+  else
+    fused_launch(plan, B, ctx->stream, predict_fused_kernel<1>, predict_fused_kernel<2>, predict_fused_kernel<4>, A);
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
   // completion: the kernel's last store is the sequence number (system scope, after E and F)

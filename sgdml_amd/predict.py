@@ -108,6 +108,40 @@ def check_lattice(lattice):
     return lat, np.array(adj, dtype=np.float64).reshape(3, 3) / det
 
 
+# ---- input checks and result conversion shared by run_md(), run_pimd() and relax()
+
+def _as_batch(A, n3=None):
+    """(B,3N), (3N,) or (B,N,3) -> (B,3N) float64; with n3, anything else is a ValueError naming R0."""
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim == 1:
+        A = A[None, :]
+    if A.ndim == 3:
+        A = A.reshape(A.shape[0], -1)
+    if n3 is not None and (A.ndim != 2 or A.shape[1] != n3):
+        raise ValueError('R0 must be (B, {}) for this model, got shape {}'.format(n3, A.shape))
+    return A
+
+
+def _check_finite(*named):
+    for name, val in named:
+        if not np.isfinite(val):
+            raise ValueError('{} must be finite'.format(name))
+
+
+def _record_fields(record, known):
+    record = (record,) if isinstance(record, str) else tuple(record)
+    for k in record:
+        if k not in known:
+            raise ValueError('record names an unknown field {!r} (known: {})'.format(k, ', '.join(map(repr, known))))
+    return record
+
+
+def _raise_first_bad(bad, noun, unit):
+    if (bad >= 0).any():
+        b = int(np.argmax(bad >= 0))
+        raise FloatingPointError('{} {} stopped being finite at {} {}'.format(noun, b, unit, int(bad[b])))
+
+
 class GDMLPredict(object):
     def __init__(
         self,
@@ -394,18 +428,7 @@ class GDMLPredict(object):
         ValueError for non-finite or misshapen input before anything is launched; FloatingPointError naming replica and step
         when a trajectory stops being finite."""
         n3 = 3 * self.n_atoms
-        R0 = np.asarray(R0, dtype=np.float64)
-        V0 = np.asarray(V0, dtype=np.float64)
-        if R0.ndim == 1:
-            R0 = R0[None, :]
-        if V0.ndim == 1:
-            V0 = V0[None, :]
-        if R0.ndim == 3:
-            R0 = R0.reshape(R0.shape[0], -1)
-        if V0.ndim == 3:
-            V0 = V0.reshape(V0.shape[0], -1)
-        if R0.ndim != 2 or R0.shape[1] != n3:
-            raise ValueError('R0 must be (B, {}) for this model, got shape {}'.format(n3, R0.shape))
+        R0, V0 = _as_batch(R0, n3), _as_batch(V0)
         if V0.shape != R0.shape:
             raise ValueError('V0 must have the shape of R0 {}, got {}'.format(R0.shape, V0.shape))
         masses = np.asarray(masses, dtype=np.float64)
@@ -413,15 +436,10 @@ class GDMLPredict(object):
             raise ValueError('masses must be ({},), got shape {}'.format(self.n_atoms, masses.shape))
         if not (np.isfinite(R0).all() and np.isfinite(V0).all() and np.isfinite(masses).all()):
             raise ValueError('R0, V0 and masses must be finite')
-        for name, val in (('dt', dt), ('gamma', gamma), ('kT', kT), ('f_unit', f_unit)):
-            if not np.isfinite(val):
-                raise ValueError('{} must be finite'.format(name))
+        _check_finite(('dt', dt), ('gamma', gamma), ('kT', kT), ('f_unit', f_unit))
         if thermostat not in (None, 'langevin'):
             raise ValueError("thermostat must be None or 'langevin', got {!r}".format(thermostat))
-        record = (record,) if isinstance(record, str) else tuple(record)
-        for k in record:
-            if k not in ('R', 'V', 'F', 'E'):
-                raise ValueError("record names an unknown field {!r} (known: 'R', 'V', 'F', 'E')".format(k))
+        record = _record_fields(record, ('R', 'V', 'F', 'E'))
         seed, step0 = int(seed), int(step0)
         if not 0 <= seed < 2**64:
             raise ValueError('seed must fit into 64 unsigned bits')
@@ -429,10 +447,7 @@ class GDMLPredict(object):
         out = self._ctx.md_run(R0, V0, masses, dt, n_steps, record_every, f_scale=self.std * float(f_unit),
                                thermostat=0 if thermostat is None else 1, gamma=gamma, kT=kT, seed=seed, step0=step0,
                                lat_and_inv=lat_and_inv, record=record)
-        bad = out.pop('first_bad_step')
-        if (bad >= 0).any():
-            b = int(np.argmax(bad >= 0))
-            raise FloatingPointError('replica {} stopped being finite at step {}'.format(b, int(bad[b])))
+        _raise_first_bad(out.pop('first_bad_step'), 'replica', 'step')
         if 'F' in out:
             out['F'] *= self.std
         E = out.pop('E')
@@ -443,7 +458,7 @@ class GDMLPredict(object):
         out['step_end'] = step0 + int(n_steps)
         return out
 
-    # ---- geometry relaxation on the device (gdml_relax_run, csrc/md.hip)
+    # ---- geometry relaxation on the device (gdml_relax_run, csrc/relax.hip)
 
     def relax(self, R0, fmax, max_steps=1000, dt_start=0.1, dt_max=None, max_step=0.2, n_min=5, f_inc=1.1, f_dec=0.5,
               alpha_start=0.1, f_alpha=0.99, state=None, lattice=None, f_unit=1.0, record_every=0):
@@ -460,20 +475,12 @@ class GDMLPredict(object):
         parameters and misshapen input before anything is launched; FloatingPointError naming geometry and evaluation when a
         value is not finite (a NaN in R0 included: evaluation 0)."""
         n3 = 3 * self.n_atoms
-        R0 = np.asarray(R0, dtype=np.float64)
-        if R0.ndim == 1:
-            R0 = R0[None, :]
-        if R0.ndim == 3:
-            R0 = R0.reshape(R0.shape[0], -1)
-        if R0.ndim != 2 or R0.shape[1] != n3:
-            raise ValueError('R0 must be (B, {}) for this model, got shape {}'.format(n3, R0.shape))
+        R0 = _as_batch(R0, n3)
         B = R0.shape[0]
         if dt_max is None:
             dt_max = 10.0 * dt_start
-        for name, val in (('fmax', fmax), ('dt_start', dt_start), ('dt_max', dt_max), ('max_step', max_step), ('f_inc', f_inc),
-                          ('f_dec', f_dec), ('alpha_start', alpha_start), ('f_alpha', f_alpha), ('f_unit', f_unit)):
-            if not np.isfinite(val):
-                raise ValueError('{} must be finite'.format(name))
+        _check_finite(('fmax', fmax), ('dt_start', dt_start), ('dt_max', dt_max), ('max_step', max_step), ('f_inc', f_inc),
+                      ('f_dec', f_dec), ('alpha_start', alpha_start), ('f_alpha', f_alpha), ('f_unit', f_unit))
         if int(max_steps) != max_steps or int(record_every) != record_every or int(n_min) != n_min:
             raise ValueError('max_steps, record_every and n_min must be integers')
         if state is None:
@@ -491,10 +498,7 @@ class GDMLPredict(object):
         out = self._ctx.relax_run(R0, fmax, max_steps, state, dt_max, max_step=max_step, n_min=n_min, f_inc=f_inc, f_dec=f_dec,
                                   alpha_start=alpha_start, f_alpha=f_alpha, f_scale=self.std * float(f_unit),
                                   record_every=record_every, lat_and_inv=self._lat_and_inv(lattice))
-        bad = out.pop('first_bad_step')
-        if (bad >= 0).any():
-            b = int(np.argmax(bad >= 0))
-            raise FloatingPointError('geometry {} stopped being finite at evaluation {}'.format(b, int(bad[b])))
+        _raise_first_bad(out.pop('first_bad_step'), 'geometry', 'evaluation')
         status = out.pop('status')
         out.pop('n_made')
         out['F_end'] *= self.std
@@ -506,7 +510,7 @@ class GDMLPredict(object):
         out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
         return out
 
-    # ---- path-integral molecular dynamics on the device (gdml_pimd_run, csrc/md.hip)
+    # ---- path-integral molecular dynamics on the device (gdml_pimd_run, csrc/pimd.hip)
 
     def run_pimd(self, R0, V0, masses, dt, n_steps, beads, kT, hbar, record_every=1, thermostat=None, gamma_centroid=0.0,
                  pile_lambda=1.0, seed=0, step0=0, lattice=None, f_unit=1.0, record=('Rc', 'E')):
@@ -546,16 +550,11 @@ class GDMLPredict(object):
             raise ValueError('masses must be ({},), got shape {}'.format(self.n_atoms, masses.shape))
         if not (np.isfinite(R0).all() and np.isfinite(V0).all() and np.isfinite(masses).all()):
             raise ValueError('R0, V0 and masses must be finite')
-        for name, val in (('dt', dt), ('gamma_centroid', gamma_centroid), ('pile_lambda', pile_lambda), ('kT', kT), ('hbar', hbar),
-                          ('f_unit', f_unit)):
-            if not np.isfinite(val):
-                raise ValueError('{} must be finite'.format(name))
+        _check_finite(('dt', dt), ('gamma_centroid', gamma_centroid), ('pile_lambda', pile_lambda), ('kT', kT), ('hbar', hbar),
+                      ('f_unit', f_unit))
         if thermostat not in (None, 'pile'):
             raise ValueError("thermostat must be None or 'pile', got {!r}".format(thermostat))
-        record = (record,) if isinstance(record, str) else tuple(record)
-        for k in record:
-            if k not in ('R', 'V', 'F', 'E', 'Rc'):
-                raise ValueError("record names an unknown field {!r} (known: 'R', 'V', 'F', 'E', 'Rc')".format(k))
+        record = _record_fields(record, ('R', 'V', 'F', 'E', 'Rc'))
         seed, step0 = int(seed), int(step0)
         if not 0 <= seed < 2**64:
             raise ValueError('seed must fit into 64 unsigned bits')
@@ -563,10 +562,7 @@ class GDMLPredict(object):
         out = self._ctx.pimd_run(R0, V0, masses, dt, n_steps, P, kT, hbar, record_every, f_scale=self.std * float(f_unit),
                                  thermostat=0 if thermostat is None else 1, gamma_centroid=gamma_centroid,
                                  pile_lambda=pile_lambda, seed=seed, step0=step0, lat_and_inv=lat_and_inv, record=record)
-        bad = out.pop('first_bad_step')
-        if (bad >= 0).any():
-            b = int(np.argmax(bad >= 0))
-            raise FloatingPointError('ring {} stopped being finite at step {}'.format(b, int(bad[b])))
+        _raise_first_bad(out.pop('first_bad_step'), 'ring', 'step')
         if 'F' in out:
             out['F'] *= self.std
         if 'E' in out:

@@ -7,6 +7,7 @@ import numpy as np
 
 import _hessian_ref as hr
 import _stress_ref as sr
+from oracle import gdml_oracle as orc
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
@@ -86,6 +87,32 @@ def case(name):
     R7 = np.concatenate([Rt[:6], g['R_train'][:1].reshape(1, -1)])
     R7.setflags(write=False)
     return model, R7
+
+
+@functools.lru_cache(maxsize=None)
+def synth_n12():
+    """(model, seven start geometries) of the synthetic N = 12, M = 150 model of tests/test_hip_r5.py
+    (test_single_launch_prediction_aspirin_size): D = 66, two descriptor entries per lane in the single-launch kernels.
+    Random J alpha, sig = 20, identity permutation, std = 1, c = 0; read-only."""
+    N, M = 12, 150
+    ds = orc.synth_dataset(N, M + 7, seed=4, jitter=0.3)
+    Rf = ds['R'].reshape(M + 7, -1)
+    xo, _ = orc.desc_from_R(Rf[:M])
+    JA = np.random.default_rng(1).standard_normal(xo.shape)
+    perms = np.arange(N, dtype=np.int64)[None]
+    tp = orc.tril_perms_from_atom_perms(perms)
+    model = {'type': 'm', 'z': np.ones(N, dtype=np.int64), 'R_desc': np.ascontiguousarray(xo.T), 'R_d_desc_alpha': JA,
+             'sig': 20.0, 'std': 1.0, 'c': 0.0, 'perms': perms, 'tril_perms_lin': orc.tril_perms_lin_from_tril_perms(tp)}
+    R7 = np.ascontiguousarray(Rf[M:])
+    R7.setflags(write=False)
+    return model, R7
+
+
+# Runs on synth_n12() (masses 1): time step and start-velocity scale of the MD runs, first time step and step cap of the
+# relaxation.  Over six steps (evaluations) of the restatements (run() here, _relax_ref.run) the shortest pair distance of a
+# replica changes by 0.48 % at most (NVE and Langevin) and by 0.21 % (FIRE from rest): below 1 %.
+SYNTH_DT, SYNTH_V_SCALE = 0.0005, 0.2
+SYNTH_RELAX = dict(dt_start=0.02, max_step=0.01)
 
 
 def force_fn(model, rel_noise=0.0, seed=0):

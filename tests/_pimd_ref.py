@@ -1,4 +1,4 @@
-"""NumPy restatement of the on-device path-integral integrator (gdml_pimd_run, csrc/md.hip; include/gdml_hip.h has the
+"""NumPy restatement of the on-device path-integral integrator (gdml_pimd_run, csrc/pimd.hip; include/gdml_hip.h has the
 equations): B rings of P beads, BAOAB with the exact free ring-polymer flow in normal-mode space and the PILE-L thermostat,
 around a force callback.  The noise stream, fixtures and restated forces are those of _md_ref."""
 import numpy as np

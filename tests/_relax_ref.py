@@ -1,8 +1,8 @@
-"""NumPy restatement of the on-device geometry relaxation (gdml_relax_run, csrc/md.hip) around a force callback, the margins
+"""NumPy restatement of the on-device geometry relaxation (gdml_relax_run, csrc/relax.hip) around a force callback, the margins
 of its decisions, and a bound toy model (the committed fixtures are fits to synthetic data without a minimum: under FIRE their
 molecules dissociate or collapse, so they serve for step-by-step parity only).
 
-The step (the contract; include/gdml_hip.h and csrc/md.hip state the same).  g = f_unit * F, F the forces of predict(); sums
+The step (the contract; include/gdml_hip.h and csrc/relax.hip state the same).  g = f_unit * F, F the forces of predict(); sums
 and norms over a replica's 3N coordinates; state v, dt, alpha, n_pos, n_taken per replica.  Evaluation t = 0, 1, ... of an
 active replica:
   1. E, F = predictor(r);  f_atom = max over atoms |g_atom|;  both into the history

@@ -139,6 +139,20 @@ def test_frames_match_the_predictor_small_shapes(name, route):
             _frames_vs_predict(pred, out, exact=(route == 'step' and B * R0.shape[1] <= 384))
 
 
+def test_frames_are_the_predictors_bits_two_entries_per_lane():
+    """D = 66 (N = 12, synthetic model): the instance of the single-launch step with two descriptor entries per lane, which no
+    fixture reaches.  B = 1 and 7 (252 coordinates: predict() takes its single launch too), six steps, every frame: E_pot and
+    F are the bits of predict(R_frame)."""
+    model, R7 = mr.synth_n12()
+    V0 = mr.start_velocities(7, R7.shape[1], mr.SYNTH_V_SCALE)
+    pred = GDMLPredict(model)
+    for B in (1, 7):
+        for th in THERMO.values():
+            out = pred.run_md(R7[:B], V0[:B], np.ones(12), mr.SYNTH_DT, 6, record=ALL, **th)
+            assert out['R'].shape == (6, B, 36)
+            _frames_vs_predict(pred, out, exact=True)
+
+
 # ---- 3. determinism and restart
 
 @pytest.mark.parametrize('thermo', ['nve', 'langevin'])

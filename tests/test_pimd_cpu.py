@@ -1,4 +1,4 @@
-"""CPU-side checks of the on-device path-integral MD (gdml_pimd_run, gdml_pimd_modes, csrc/md.hip): the library surface
+"""CPU-side checks of the on-device path-integral MD (gdml_pimd_run, gdml_pimd_modes, csrc/pimd.hip): the library surface
 (exports, struct layout, argument errors that need no device), the normal-mode matrix of the library against its defining
 properties and the restatement's, and the restated integrator (tests/_pimd_ref.py) as a yardstick: exact free flow, restart,
 the quantum harmonic oscillator's kinetic energy, second-order drift."""

@@ -1,4 +1,4 @@
-"""Path-integral MD on the GPU (gdml_pimd_run, csrc/md.hip; GDMLPredict.run_pimd): against the NumPy restatement
+"""Path-integral MD on the GPU (gdml_pimd_run, csrc/pimd.hip; GDMLPredict.run_pimd): against the NumPy restatement
 (tests/_pimd_ref.py), recorded frames against predict(), determinism, restart, record_every, chunking and tile width bit for
 bit, the one-bead ring against run_md, independent rings, conservation laws and error paths.
 

@@ -1,4 +1,4 @@
-"""CPU-side checks of the on-device geometry relaxation (gdml_relax_run, csrc/md.hip; GDMLPredict.relax): the NumPy
+"""CPU-side checks of the on-device geometry relaxation (gdml_relax_run, csrc/relax.hip; GDMLPredict.relax): the NumPy
 restatement (tests/_relax_ref.py) meets the conditions the GPU tests rely on, and the library surface (export, struct layout,
 argument errors that need no device)."""
 import ctypes as C

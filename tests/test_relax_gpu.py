@@ -1,5 +1,5 @@
-"""Geometry relaxation on the GPU (gdml_relax_run, csrc/md.hip; GDMLPredict.relax): step by step against the NumPy restatement
-(tests/_relax_ref.py), to convergence on a bound toy model, end state against predict(), determinism, continuation, chunking
+"""Geometry relaxation on the GPU (gdml_relax_run, csrc/relax.hip; GDMLPredict.relax): step by step against the NumPy
+restatement (tests/_relax_ref.py), to convergence on a bound toy model, end state against predict(), determinism, continuation, chunking
 and record_every bit for bit, replicas that finish at different steps, edges and error paths."""
 import functools
 import os
@@ -143,6 +143,18 @@ def test_end_state_is_the_predictors_bits_mfma_route():
     out = pred.relax(R0, **dict(prm, fmax=float(np.median(f0[:7])), max_steps=3))
     assert (out['n_steps'][f0 < np.median(f0[:7])] == 0).all() and (out['n_steps'] == 0).any() and (out['n_steps'] > 0).any()
     _end_vs_predict(pred, out, exact=True)
+
+
+def test_end_state_is_the_predictors_bits_two_entries_per_lane():
+    """D = 66 (N = 12, synthetic model): the instance of the single-launch evaluation with two descriptor entries per lane,
+    which no fixture reaches.  B = 1 and 7 (252 coordinates: predict() takes its single launch too), six evaluations from
+    rest: E_end and F_end are the bits of predict(R_end)."""
+    model, R7 = mr.synth_n12()
+    pred = GDMLPredict(model)
+    for B in (1, 7):
+        out = pred.relax(R7[:B], fmax=1e-12, max_steps=5, **mr.SYNTH_RELAX)
+        assert out['E_hist'].shape == (6, B) and (out['n_steps'] == 5).all()
+        _end_vs_predict(pred, out, exact=True)
 
 
 @pytest.mark.parametrize('route', ['step', 'general'])
