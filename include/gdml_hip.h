@@ -510,6 +510,71 @@ int gdml_relax_run(gdml_ctx* ctx, const gdml_relax_params* params, double* R, do
                    int64_t* n_pos, int64_t* n_taken, int64_t max_steps, int64_t record_every, double* R_rec, double* E_hist,
                    double* fmax_hist, double* E_end, double* F_end, int64_t* status, int64_t* first_bad_step);
 
+/* Nudged elastic band on the device: B independent bands of P images each, images 0 and P - 1 fixed end points (two minima),
+ * relax to the minimum-energy path between them; with `climb` the highest image climbs to the saddle, whose energy above the
+ * end points is the barrier.  A band is ONE FIRE system (one v, dt, alpha, n_pos, n_taken per band), which is how ASE drives
+ * FIRE(NEB(...)).  Positions, velocities, forces and the optimiser's state stay resident in device memory.  The reference has
+ * no counterpart (its users wrap GDMLPredict.predict in ASE's NEB, one host round trip per evaluation).
+ * The step.  g = f_scale F' as in gdml_relax_run; E' is the predictor's unscaled energy.  Evaluation t = 0, 1, ... of a band
+ *   that is still active:
+ *   1. E', F' = predictor of all P images.  The end points are recomputed each evaluation and their results are not used for
+ *      motion (so E_end, F_end are what gdml_predict_dev returns for the B P geometries of R).
+ *   2. NEB force.  For every interior image i, with tau+ = r_{i+1} - r_i and tau- = r_i - r_{i-1} (plain differences;
+ *      positions are never wrapped), the improved tangent (Henkelman, Jonsson, J. Chem. Phys. 113, 9978 (2000)):
+ *        E_{i+1} > E_i > E_{i-1}:  tau = tau+
+ *        E_{i+1} < E_i < E_{i-1}:  tau = tau-
+ *        otherwise, with dE_max and dE_min the larger and the smaller of |E_{i+1} - E_i| and |E_{i-1} - E_i|:
+ *          tau = tau+ dE_max + tau- dE_min  if E_{i+1} > E_{i-1},  else  tau = tau+ dE_min + tau- dE_max
+ *        tau^ = tau / |tau|
+ *      F_i = g_i - (g_i . tau^) tau^ + k (|tau+| - |tau-|) tau^          (k = k_spring, in units of g per length)
+ *      With climb: the interior image of highest E' (ties go to the lowest index; chosen anew at every evaluation) gets
+ *      F_i = g_i - 2 (g_i . tau^) tau^ and no spring (Henkelman, Uberuaga, Jonsson, J. Chem. Phys. 113, 9901 (2000)).
+ *      Energies enter through comparisons and the ratio of the two dE only: their scale and offset do not matter.
+ *   3. Convergence.  f_atom = max over interior images and atoms of |F_{i,atom}|; E'(highest interior image) and f_atom go
+ *      into the history.  f_atom < fmax: the band is converged; otherwise t = max_steps: it stops unconverged.  A frozen band
+ *      is never written again, exactly as a frozen replica of gdml_relax_run.  A non-finite r, v, F or E' of the band sets
+ *      first_bad_step (to t); such a band never counts as converged.
+ *   4. Update.  Otherwise gdml_relax_run's update 4, verbatim, on the band vector of (P - 2) 3N coordinates with F in place
+ *      of g (the n_taken = 0 case, the clip of the whole vector to max_step and the counters included).
+ *   Sums: the four per-image sums (g . tau, |tau+|^2, |tau-|^2, |tau|^2) over 3N and the band sums (F . v, |F|^2, |v|^2,
+ *   |Delta|^2) over (P - 2) 3N as per-thread partial sums in index order (k, k + 256, ...), then gdml_md_run's 256-slot tree.
+ *   No floating-point atomics.
+ * Three pieces per evaluation, stream order the only dependency: the device prediction path for the B P geometries exactly
+ *   as gdml_predict_dev runs it; neb_force_kernel, one workgroup per interior image (it finds the climbing image itself from
+ *   the band's energies and writes nothing another workgroup of the launch reads); neb_step_kernel, one workgroup per band:
+ *   gdml_relax_run's update function on the band vector, history, frame and status, and on freeze the end-of-run outputs.
+ *   Workgroups of a frozen band read its status word and return at once.  Chunks, readback and the recorder are
+ *   gdml_relax_run's (predict.relax_chunk_steps, predict.md_chunk_frames / 64 MiB); nothing depends on the chunk length.
+ * Arguments.  R, V (B,P,3N), dt, alpha (B), n_pos, n_taken (B, int64): the state, start on entry and end on return; rows 0 and
+ *   P - 1 of every band of R and V are never written (pass V = 0 there).  Passing the end state back continues the run as if
+ *   it had not been cut; a relaxation without climb followed by one with climb is such a continuation.
+ *   status, first_bad_step, record_every: as in gdml_relax_run, per band.  Emax_hist, fmax_hist (max_steps + 1, B): E'
+ *   UNSCALED of the highest interior image, and f_atom, of the evaluations made.  R_rec (max_steps / record_every + 1, B, P,
+ *   3N) or NULL.  Written when a band freezes (zero for a band that a non-finite value stopped): E_end (B,P), F_end (B,P,3N):
+ *   E', F' UNSCALED at R;  i_climb (B): the interior image of highest E';  s (B,P): cumulative Euclidean arc length
+ *   sum_{j<=i} |r_j - r_{j-1}|;  f_tangent (B,P): g . tau^ of the interior images, 0 at the ends.
+ * Bit-identical: the same call repeated; n steps then a continuation against 2 n steps; any chunk length; any record_every.
+ * GDML_ERR_INVALID before any launch (ctx may be NULL for these checks): everything gdml_relax_run rejects, P outside
+ *   3 ... 128, k_spring <= 0 or not finite, B P >= 2^31, a NULL state or output array.  GDML_ERR_STATE without a model. */
+typedef struct gdml_neb_params {
+  int64_t B;             /* bands */
+  int N;
+  int P;                 /* images per band, end points included */
+  double f_scale;        /* g = f_scale * F' */
+  const double* lat;
+  const double* lat_inv; /* both or neither */
+  double fmax;           /* converged when the largest |F_atom| of the interior images is below it */
+  double dt_max, max_step;
+  double f_inc, f_dec, alpha_start, f_alpha;
+  int64_t n_min;
+  double k_spring;
+  int climb;             /* 0: plain band, else the highest image climbs */
+} gdml_neb_params;       /* 120 bytes */
+int gdml_neb_run(gdml_ctx* ctx, const gdml_neb_params* params, double* R, double* V, double* dt, double* alpha, int64_t* n_pos,
+                 int64_t* n_taken, int64_t max_steps, int64_t record_every, double* R_rec, double* Emax_hist, double* fmax_hist,
+                 double* E_end, double* F_end, int64_t* i_climb, double* s, double* f_tangent, int64_t* status,
+                 int64_t* first_bad_step);
+
 /* Strain derivative (virial) of B geometries: what pressure, NPT dynamics, cell relaxation and equation-of-state scans of a
  * periodic model need, and what its forces cannot give (with minimum-image pair vectors sum_i f_i (x) r_i is not the strain
  * derivative).  The reference has no counterpart.  Straining atoms and cell together, r -> (I + eps) r, lattice -> (I + eps)

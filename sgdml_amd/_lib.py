@@ -40,6 +40,14 @@ class RelaxParams(C.Structure):
                 ('alpha_start', C.c_double), ('f_alpha', C.c_double), ('n_min', C.c_int64)]
 
 
+class NebParams(C.Structure):
+    """gdml_neb_params (include/gdml_hip.h)."""
+    _fields_ = [('B', C.c_int64), ('N', C.c_int), ('P', C.c_int), ('f_scale', C.c_double), ('lat', _vp), ('lat_inv', _vp),
+                ('fmax', C.c_double), ('dt_max', C.c_double), ('max_step', C.c_double), ('f_inc', C.c_double),
+                ('f_dec', C.c_double), ('alpha_start', C.c_double), ('f_alpha', C.c_double), ('n_min', C.c_int64),
+                ('k_spring', C.c_double), ('climb', C.c_int)]
+
+
 # name -> (restype, argtypes).  Must list every symbol declared in include/gdml_hip.h.
 SIGNATURES = {
     'gdml_abi_version': (C.c_int, []),
@@ -76,6 +84,8 @@ SIGNATURES = {
     'gdml_pimd_modes': (C.c_int, [C.c_int, C.c_double, C.c_double, _vp, _vp]),
     'gdml_relax_run': (C.c_int, [_vp, C.POINTER(RelaxParams), _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp]),
+    'gdml_neb_run': (C.c_int, [_vp, C.POINTER(NebParams), _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_virial': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_virial_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
@@ -698,6 +708,53 @@ class Context(object):
         n_made = int(status[:, 1].max()) + 1 if B and (status[:, 1] >= 0).all() else 0
         out = dict(R_end=R, E_end=E_end, F_end=F_end, status=status, first_bad_step=bad, n_made=n_made,
                    E_hist=E_hist[:n_made], fmax_hist=f_hist[:n_made],
+                   state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken))
+        if R_rec is not None:
+            out['R'] = R_rec[:(n_made + record_every - 1) // record_every]
+        return out
+
+    def neb_run(self, R, fmax, k_spring, max_steps, state, dt_max, climb=False, max_step=0.2, n_min=5, f_inc=1.1, f_dec=0.5,
+                alpha_start=0.1, f_alpha=0.99, f_scale=1.0, record_every=0, lat_and_inv=None):
+        """gdml_neb_run: B bands of P images (R: (B,P,3N), images 0 and P - 1 fixed) relax by FIRE on the NEB force, a band being
+        one FIRE system, for at most max_steps steps each.  state: dict with 'V' (B,P,3N; the end points' rows are not used and
+        come back zero), 'dt', 'alpha' (B), 'n_pos', 'n_taken' (B, int).  Returns a dict: 'R_end', 'E_end' (B,P; unscaled E'),
+        'F_end' (B,P,3N; unscaled), 'i_climb' (B), 's', 'f_tangent' (B,P), the end 'state', 'status' (B,2; see the header),
+        'n_made', 'Emax_hist' (unscaled), 'fmax_hist' (n_made,B), the frames 'R' (only with record_every > 0) and
+        'first_bad_step' (B)."""
+        n3 = 3 * self.model_n_atoms
+        R = np.asarray(R, dtype=np.float64)
+        if R.ndim != 3 or R.shape[2] != n3:
+            raise ValueError('R must be (B, P, {}), got shape {}'.format(n3, R.shape))
+        B, P = R.shape[:2]
+        R, V = _state_copies(R, state['V'], (B, P, n3))
+        if P >= 1:
+            V[:, 0] = 0.0
+            V[:, -1] = 0.0
+        dt, alpha = (np.array(state[k], dtype=np.float64).ravel() for k in ('dt', 'alpha'))
+        n_pos, n_taken = (np.array(state[k], dtype=np.int64).ravel() for k in ('n_pos', 'n_taken'))
+        for k, a in (('dt', dt), ('alpha', alpha), ('n_pos', n_pos), ('n_taken', n_taken)):
+            if a.shape != (B,):
+                raise ValueError("state['{}'] must have one entry per band ({}), got shape {}".format(k, B, a.shape))
+        lat, lat_inv = _lat_pair(lat_and_inv)
+        max_steps, record_every = int(max_steps), int(record_every)
+        n_eval = max(max_steps, 0) + 1
+        R_rec = np.empty((max(max_steps, 0) // record_every + 1, B, P, n3)) if record_every > 0 else None
+        E_hist, f_hist = np.empty((n_eval, B)), np.empty((n_eval, B))
+        E_end, F_end = np.zeros((B, P)), np.zeros((B, P, n3))
+        s, f_tan = np.zeros((B, P)), np.zeros((B, P))
+        i_climb = np.zeros(B, dtype=np.int64)
+        status = np.full((B, 2), -1, dtype=np.int64)
+        bad = np.full(B, -1, dtype=np.int64)
+        prm = NebParams(B, self.model_n_atoms, P, float(f_scale), _ptr(lat), _ptr(lat_inv), float(fmax), float(dt_max),
+                        float(max_step), float(f_inc), float(f_dec), float(alpha_start), float(f_alpha), int(n_min),
+                        float(k_spring), int(bool(climb)))
+        self._check(self._lib.gdml_neb_run(self._h, C.byref(prm), _ptr(R), _ptr(V), _ptr(dt), _ptr(alpha), _ptr(n_pos),
+                                           _ptr(n_taken), max_steps, record_every, _ptr(R_rec), _ptr(E_hist), _ptr(f_hist),
+                                           _ptr(E_end), _ptr(F_end), _ptr(i_climb), _ptr(s), _ptr(f_tan), _ptr(status),
+                                           _ptr(bad)))
+        n_made = int(status[:, 1].max()) + 1 if B and (status[:, 1] >= 0).all() else 0
+        out = dict(R_end=R, E_end=E_end, F_end=F_end, i_climb=i_climb, s=s, f_tangent=f_tan, status=status, first_bad_step=bad,
+                   n_made=n_made, Emax_hist=E_hist[:n_made], fmax_hist=f_hist[:n_made],
                    state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken))
         if R_rec is not None:
             out['R'] = R_rec[:(n_made + record_every - 1) // record_every]

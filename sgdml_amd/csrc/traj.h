@@ -1,6 +1,8 @@
-// What the on-device trajectory entries (gdml_md_run in md.hip, gdml_pimd_run in pimd.hip, gdml_relax_run in relax.hip) share:
+// What the on-device trajectory entries (gdml_md_run in md.hip, gdml_pimd_run in pimd.hip, gdml_relax_run in relax.hip,
+// gdml_neb_run in neb.hip) share:
 // the counter-based noise, the fixed reduction tree, the argument checks and prelude, the recorder of a chunk of frames and
-// the chunk loop of the two MD entries.
+// the chunk loop of the two MD entries, and the chunk loop of the entries whose replicas freeze on their own (gdml_relax_run,
+// gdml_neb_run in neb.hip).
 #pragma once
 #include <math.h>
 
@@ -218,4 +220,68 @@ static int traj_run_chunks(gdml_ctx* ctx, Recorder& rec, int64_t n_steps, int64_
     if (any_bad) break;
   }
   return GDML_OK;
+}
+
+// The chunk loop of gdml_relax_run and gdml_neb_run, whose replicas (geometries, bands) freeze on their own: enqueue(t, row,
+// frame, last) queues evaluation t = 0 .. max_steps on ctx->stream; row = its row in the chunk's two history buffers, frame =
+// the chunk slot of its recorded positions or -1, last = (t == max_steps).  d_flags: status (B,2) | bad (B) | history a
+// (chunk_steps,B) | history b (chunk_steps,B), side by side in device memory, so ONE copy per chunk brings them into h_out
+// (3 B + 2 chunk_steps B words); the rows go on into hist_a, hist_b (max_steps + 1, B).  Ends when no status word says active
+// (-1), a bad flag is set or the budget is used up; *t_queued = evaluations queued.
+template <class Enqueue>
+static int traj_run_until_frozen(gdml_ctx* ctx, Recorder& rec, bool record, int64_t B, int64_t max_steps, int64_t record_every,
+                                 int64_t chunk_steps, const int64_t* d_flags, double* hist_a, double* hist_b,
+                                 std::vector<int64_t>& h_out, int64_t* t_queued, Enqueue&& enqueue) {
+  hipStream_t st = ctx->stream;
+  const int64_t n_out = 3 * B + 2 * chunk_steps * B;
+  h_out.assign((size_t)n_out, -1);
+  const int64_t* h_flags = h_out.data();
+  const double* h_a = (const double*)(h_out.data() + 3 * B);
+  const double* h_b = h_a + chunk_steps * B;
+  int64_t t = 0;
+  bool active = true, any_bad = false;
+  while (t <= max_steps && active && !any_bad) {
+    const int64_t t0 = t;
+    int64_t in_chunk = 0;
+    for (; t <= max_steps && t - t0 < chunk_steps; ++t) {
+      const bool on = record && t % record_every == 0;
+      if (on && in_chunk == rec.frames) break;
+      GDML_TRY(enqueue(t, t - t0, on ? in_chunk : (int64_t)-1, (int)(t == max_steps)));
+      if (on) ++in_chunk;
+    }
+    HIP_CHECK(ctx, hipGetLastError());
+    if (in_chunk > 0) HIP_CHECK(ctx, rec.flush(st, in_chunk));
+    HIP_CHECK(ctx, hipMemcpyAsync(h_out.data(), d_flags, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(ctx, hipStreamSynchronize(st));
+    memcpy(hist_a + t0 * B, h_a, (size_t)((t - t0) * B) * 8);
+    memcpy(hist_b + t0 * B, h_b, (size_t)((t - t0) * B) * 8);
+    active = false;
+    for (int64_t b = 0; b < B; ++b) {
+      active |= h_flags[(size_t)(2 * b)] < 0;
+      any_bad |= h_flags[(size_t)(2 * B + b)] >= 0;
+    }
+  }
+  *t_queued = t;
+  return GDML_OK;
+}
+
+// After such a run: a frozen replica repeats its last history values and its end positions (R, len doubles per replica) up to
+// the last evaluation any replica made (the launches behind its freeze wrote nothing for it).  h_flags: status (B,2) as read
+// back; t: evaluations queued.
+static inline void traj_repeat_frozen(const int64_t* h_flags, int64_t B, int64_t t, int64_t record_every, double* hist_a,
+                                      double* hist_b, double* R_rec, const double* R, int64_t len) {
+  int64_t n_made = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t e = h_flags[(size_t)(2 * b + 1)];
+    n_made = std::max(n_made, e < 0 ? t : e + 1);
+  }
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t e = h_flags[(size_t)(2 * b + 1)];
+    if (e < 0) continue;
+    for (int64_t u = e + 1; u < n_made; ++u) {
+      hist_a[u * B + b] = hist_a[e * B + b];
+      hist_b[u * B + b] = hist_b[e * B + b];
+      if (R_rec && u % record_every == 0) memcpy(R_rec + (u / record_every) * B * len + b * len, R + b * len, (size_t)len * 8);
+    }
+  }
 }

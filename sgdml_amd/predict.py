@@ -510,6 +510,87 @@ class GDMLPredict(object):
         out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
         return out
 
+    # ---- nudged elastic band on the device (gdml_neb_run, csrc/neb.hip)
+
+    @staticmethod
+    def interpolate_path(R_a, R_b, n_images):
+        """Linear interpolation between end points R_a and R_b ((B,3N), (3N,) or (B,N,3)): (B, n_images, 3N) with image 0 = R_a
+        and image n_images - 1 = R_b, bit for bit.  Host only.  No minimum image: for a periodic model, unwrap R_b first."""
+        if isinstance(n_images, bool) or int(n_images) != n_images or int(n_images) < 2:
+            raise ValueError('n_images must be an integer of at least 2, got {!r}'.format(n_images))
+        A, Bm = _as_batch(R_a), _as_batch(R_b)
+        if A.ndim != 2 or A.shape != Bm.shape:
+            raise ValueError('R_a and R_b must have the same shape (B, 3N), got {} and {}'.format(A.shape, Bm.shape))
+        t = (np.arange(int(n_images)) / (int(n_images) - 1.0))[None, :, None]
+        path = A[:, None, :] + t * (Bm - A)[:, None, :]
+        path[:, 0], path[:, -1] = A, Bm
+        return path
+
+    def neb(self, R_path, fmax, k_spring=0.1, climb=False, max_steps=1000, dt_start=0.1, dt_max=None, max_step=0.2, n_min=5,
+            f_inc=1.1, f_dec=0.5, alpha_start=0.1, f_alpha=0.99, state=None, lattice=None, f_unit=1.0, record_every=0):
+        """Relax B independent bands of P images each to the minimum-energy path between their fixed end points (images 0 and
+        P - 1) on the device: nudged elastic band with the improved tangent (Henkelman, Jonsson, JCP 113, 9978 (2000)), springs
+        of constant k_spring (in units of f_unit * F per length) and, with climb=True, a climbing image (Henkelman, Uberuaga,
+        Jonsson, JCP 113, 9901 (2000): the image of highest energy, chosen anew at every evaluation), driven by FIRE with the
+        whole band as one system -- ASE's FIRE(NEB(...)); the FIRE parameters are relax()'s.  R_path: (B,P,3N) or (P,3N), 3 <= P
+        <= 128 (interpolate_path() makes one).  A band is converged when the largest atomic |NEB force| of its interior images is
+        below fmax; every band takes at most max_steps steps in this call and stops on its own.  state: the 'state' of an
+        earlier call, passed back with its R_end, continues that run bit for bit (relaxing first without and then with climb is
+        such a continuation); None is a fresh start.  lattice: as in predict(); positions are never wrapped.
+        Returns a dict: 'R_end' (B,P,3N), 'E_end' (B,P) and 'F_end' (B,P,3N): the true energies and forces of R_end scaled like
+        predict(), 'fmax_end', 'n_steps', 'converged' (B), 'i_climb' (B; the interior image of highest energy), 'barrier' (B,2;
+        E(i_climb) - E of image 0 and of image P - 1), 's' (B,P; cumulative Euclidean arc length), 'f_tangent' (B,P; f_unit * F
+        along the unit tangent at the interior images, 0 at the ends), 'fmax_hist' and 'Emax_hist' (evaluations made, B; the
+        energy of the highest interior image), 'R' frames with record_every > 0, and 'state' ('V' (B,P,3N) with zero rows at the
+        ends, 'dt', 'alpha', 'n_pos', 'n_taken' (B)).  ValueError for non-finite or out-of-range parameters and misshapen input
+        before anything is launched; FloatingPointError naming band and evaluation when a value is not finite."""
+        n3 = 3 * self.n_atoms
+        R_path = np.asarray(R_path, dtype=np.float64)
+        if R_path.ndim == 2:
+            R_path = R_path[None]
+        if R_path.ndim != 3 or R_path.shape[2] != n3:
+            raise ValueError('R_path must be (B, P, {}) for this model, got shape {}'.format(n3, R_path.shape))
+        B, P = R_path.shape[:2]
+        if not 3 <= P <= 128:
+            raise ValueError('a band needs 3 to 128 images, got {}'.format(P))
+        if dt_max is None:
+            dt_max = 10.0 * dt_start
+        _check_finite(('fmax', fmax), ('k_spring', k_spring), ('dt_start', dt_start), ('dt_max', dt_max), ('max_step', max_step),
+                      ('f_inc', f_inc), ('f_dec', f_dec), ('alpha_start', alpha_start), ('f_alpha', f_alpha), ('f_unit', f_unit))
+        if not k_spring > 0.0:
+            raise ValueError('k_spring must be positive')
+        if int(max_steps) != max_steps or int(record_every) != record_every or int(n_min) != n_min:
+            raise ValueError('max_steps, record_every and n_min must be integers')
+        if state is None:
+            state = dict(V=np.zeros((B, P, n3)), dt=np.full(B, float(dt_start)), alpha=np.full(B, float(alpha_start)),
+                         n_pos=np.zeros(B, dtype=np.int64), n_taken=np.zeros(B, dtype=np.int64))
+        else:
+            missing = [k for k in ('V', 'dt', 'alpha', 'n_pos', 'n_taken') if k not in state]
+            if missing:
+                raise ValueError('state lacks {}'.format(missing))
+            if np.shape(state['V']) != R_path.shape:
+                raise ValueError("state['V'] must have the shape of R_path {}, got {}".format(R_path.shape, np.shape(state['V'])))
+            if not all(np.isfinite(np.asarray(state[k], dtype=np.float64)).all() for k in ('V', 'dt', 'alpha')):
+                raise ValueError('state must be finite')
+        # a NaN image is not a usage error: the run reports the band and the evaluation (FloatingPointError)
+        out = self._ctx.neb_run(R_path, fmax, k_spring, max_steps, state, dt_max, climb=climb, max_step=max_step, n_min=n_min,
+                                f_inc=f_inc, f_dec=f_dec, alpha_start=alpha_start, f_alpha=f_alpha,
+                                f_scale=self.std * float(f_unit), record_every=record_every,
+                                lat_and_inv=self._lat_and_inv(lattice))
+        _raise_first_bad(out.pop('first_bad_step'), 'band', 'evaluation')
+        status = out.pop('status')
+        out.pop('n_made')
+        out['F_end'] *= self.std
+        for k in ('E_end', 'Emax_hist'):
+            out[k] *= self.std
+            out[k] += self.c
+        out['n_steps'] = status[:, 1].copy()
+        out['converged'] = status[:, 0] == 1
+        out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
+        E_top = out['E_end'][np.arange(B), out['i_climb']] if B else np.empty(0)
+        out['barrier'] = np.stack([E_top - out['E_end'][:, 0], E_top - out['E_end'][:, -1]], axis=1)
+        return out
+
     # ---- path-integral molecular dynamics on the device (gdml_pimd_run, csrc/pimd.hip)
 
     def run_pimd(self, R0, V0, masses, dt, n_steps, beads, kT, hbar, record_every=1, thermostat=None, gamma_centroid=0.0,
