@@ -186,6 +186,8 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *                         general route of two pieces per evaluation)
  *   predict.relax_chunk_steps (32)  evaluations gdml_relax_run queues between two synchronisations (the host learns at a chunk's
  *                         end which replicas froze); the results do not depend on it
+ *   predict.vib_chunk (0)         geometries per chunk of gdml_vib_run (0 = as many as keep its Hessians and work matrices under
+ *                         256 MiB); steps b to d of that entry do not depend on it
  *   chol.loo_chunk (64)            training points per pass of gdml_loo (their rows of L^-T are 3N n doubles each; fewer when free
  *                         memory is short).  The results do not depend on it
  *   chol.extend_chunk (64)         points per pass of gdml_factor_extend (their 3N rows are assembled, solved and factored together;
@@ -227,7 +229,7 @@ int gdml_desc_from_R(gdml_ctx* ctx, const double* R, int64_t M, int N, const dou
  *   if it exceeds `capacity` only the first `capacity` were stored (call again with more room; M (M-1)/2 always suffices). */
 /* |eigenvectors| (M,N,N) of M symmetric N x N matrices, columns by decreasing eigenvalue (replaces the per-geometry
  * numpy.linalg.eig of perm.py:183-187): one workgroup per matrix, cyclic two-sided Jacobi in LDS.  gdml_perm_match runs the same
- * kernel when `absv` is NULL. */
+ * kernel when `absv` is NULL.  (gdml_sym_eig below returns eigenvalues and signed eigenvectors from the same sweeps.) */
 int gdml_sym_eig_absv(gdml_ctx* ctx, const double* adj, int64_t M, int N, double* absv_out);
 int gdml_perm_match(gdml_ctx* ctx, const double* absv, const double* adj, const int32_t* species, int64_t M, int N,
                     double* cost_out, int32_t* found_ij, int32_t* found_perm, int64_t capacity, int64_t* n_found);
@@ -608,6 +610,63 @@ int gdml_predict_hessian(gdml_ctx* ctx, const double* R, int64_t B, const double
                          double* E_out, double* F_out, double* H_out);
 int gdml_predict_hessian_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat,
                              const double* lat_inv, double* E_dev, double* F_dev, double* H_dev);
+
+/* Eigenvalues and eigenvectors of M symmetric n x n matrices on the device: one workgroup per matrix (grid-stride over M),
+ * cyclic two-sided Jacobi with the round-robin ordering -- the sweep loop of gdml_sym_eig_absv (csrc/sym_eig.h holds the one
+ * copy both kernels call).  Only the mean of the two triangles of A enters.
+ *   w (M,n): eigenvalues ascending; equal ones in the order of their Jacobi columns.
+ *   V (M,n,n) or NULL: V[m][k][:] is the unit eigenvector of w[m][k], a ROW; its component of largest magnitude is positive
+ *   (the lowest index on ties), so outputs are comparable across calls.  NULL: the same w, bit for bit.
+ *   sweeps (M) or NULL: sweeps made per matrix (0 for a diagonal matrix).
+ * Storage: working matrix and rotations in LDS when both fit (n <= 100), only the matrix (n <= 141), both in device memory
+ *   above that.  A sweep stops the iteration when the off-diagonal mass is below 1e-30 of the whole; at most 30 sweeps.  A
+ *   matrix still above the threshold after them (in practice: one that is not finite) makes the call return GDML_ERR_INVALID
+ *   naming the first such matrix, after the outputs of all matrices were written.
+ * The _dev variant takes device pointers throughout (V_dev may be A_dev: every matrix is read whole before its rows are
+ *   written) and synchronises once, to read the sweeps.  The same input gives bit-identical results: on either entry, alone or
+ *   inside a batch, with or without V.
+ * GDML_ERR_INVALID before any launch (ctx may be NULL for these checks): M < 0, n < 1 or n > 591 (3 x 197), NULL A or w,
+ *   M n n >= 2^62.  M = 0 does nothing. */
+int gdml_sym_eig(gdml_ctx* ctx, const double* A, int64_t M, int n, double* w, double* V, int64_t* sweeps);
+int gdml_sym_eig_dev(gdml_ctx* ctx, const double* A_dev, int64_t M, int n, double* w_dev, double* V_dev, int64_t* sweeps_dev);
+
+/* Harmonic vibrational analysis of B geometries on the device: squared frequencies and normal modes of the mass-weighted
+ * Hessian with the rigid-body motion projected out -- what follows gdml_relax_run (is it a minimum?) and gdml_neb_run with a
+ * climbing image (is it a first-order saddle?).  The reference has no counterpart.  Per chunk of geometries:
+ *   a. H' = gdml_predict_hessian_dev of the chunk; E (B) and F (B,3N) are its E' and F, UNSCALED like gdml_predict (either may
+ *      be NULL).
+ *   b. D_ij = h_scale sym(H')_ij / sqrt(m_i m_j) (h_scale = std times the caller's unit factor, as f_scale of gdml_md_run).
+ *      Rigid basis in mass-weighted coordinates, in this order: translations sqrt(m_i) e_c (project >= 1), infinitesimal
+ *      rotations about the centre of mass sqrt(m_i) (e_c x (r_i - r_cm)) (project = 2), c = x, y, z; modified Gram-Schmidt in
+ *      that order; a vector whose remainder has a squared norm below 1e-10 of its own is dropped (linear molecule: n_rigid = 5,
+ *      one atom: 3).  With Q the orthonormal rows kept and P = I - Q^T Q:
+ *        D_s = P D P + Lambda Q^T Q,  Lambda = 2 |P D P|_F (1 if that is 0)
+ *      The rigid modes are exact eigenvectors at Lambda and every vibration has |lambda| <= |P D P|_2 < Lambda: a soft or
+ *      imaginary vibration is never confused with a rigid mode, however far the geometry is from a stationary point.
+ *   c. gdml_sym_eig_dev's kernel on D_s, in place.
+ *   d. w2 (B,3N): entries [0, 3N - n_rigid) are the vibrational omega^2 ascending (imaginary modes negative, first); the last
+ *      n_rigid entries are exactly 0.  n_neg (B): vibrational entries below -tau, tau = 3N eps |D_s|_F.  modes (B,3N,3N) or
+ *      NULL: modes[b][k][:] is the mass-weighted orthonormal vector of w2[b][k]; the last n_rigid rows span the rigid space.
+ *      NULL: nothing of size (3N)^2 leaves the device.  sweeps (B) or NULL: Jacobi sweeps per geometry.
+ * One workgroup per geometry in b and c, every sum in a fixed order, no atomics.  Chunks hold as many geometries as keep the
+ *   Hessians and the eigensolver's work matrices under 256 MiB (option predict.vib_chunk, 0 = automatic; tests).
+ * Bit-identical: the same call repeated; modes NULL or not; and steps b to d never depend on the batch or the chunk -- so any
+ *   chunk length, and a geometry alone against the same geometry inside a batch, as far as gdml_predict_hessian_dev returns the
+ *   same bits for that geometry (its plan depends on the number of geometries per call for large tables).
+ * GDML_ERR_INVALID before any launch (ctx may be NULL for these checks): B < 0, N < 1, project outside 0 .. 2, exactly one of
+ *   lat / lat_inv, project = 2 with a lattice (rotations are no symmetry of a periodic cell), h_scale not finite or <= 0, a mass
+ *   not finite or <= 0, a coordinate that is not finite, NULL params, R, masses, w2, n_rigid or n_neg; N different from the
+ *   model's.  GDML_ERR_UNSUPPORTED for N > 197 (the Hessian's limit).  GDML_ERR_STATE without a model. */
+typedef struct gdml_vib_params {
+  int64_t B;
+  int N;
+  double h_scale;        /* D = h_scale * M^-1/2 H' M^-1/2 */
+  const double* lat;
+  const double* lat_inv; /* both or neither */
+  int project;           /* 0 none, 1 translations, 2 translations + rotations */
+} gdml_vib_params;       /* 48 bytes */
+int gdml_vib_run(gdml_ctx* ctx, const gdml_vib_params* params, const double* R, const double* masses, double* w2,
+                 double* modes /* or NULL */, int64_t* n_rigid, int64_t* n_neg, double* E, double* F, int64_t* sweeps);
 
 /* Posterior force covariance of the Gaussian process behind the model (active learning, leaving the training distribution):
  *   cov F(x*) = k(x*,x*) - K*^T (K + lam I)^-1 K*.  The reference has no counterpart (its solve runs on the host and drops the

@@ -48,6 +48,11 @@ class NebParams(C.Structure):
                 ('k_spring', C.c_double), ('climb', C.c_int)]
 
 
+class VibParams(C.Structure):
+    """gdml_vib_params (include/gdml_hip.h)."""
+    _fields_ = [('B', C.c_int64), ('N', C.c_int), ('h_scale', C.c_double), ('lat', _vp), ('lat_inv', _vp), ('project', C.c_int)]
+
+
 # name -> (restype, argtypes).  Must list every symbol declared in include/gdml_hip.h.
 SIGNATURES = {
     'gdml_abi_version': (C.c_int, []),
@@ -90,6 +95,9 @@ SIGNATURES = {
     'gdml_predict_virial_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_sym_eig': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
+    'gdml_sym_eig_dev': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
+    'gdml_vib_run': (C.c_int, [_vp, C.POINTER(VibParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gdml_uncert_prepare': (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_int)]),
     'gdml_uncert_release': (C.c_int, [_vp]),
     'gdml_uncert_cross': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
@@ -807,6 +815,41 @@ class Context(object):
         lat, lat_inv = _lat_pair(lat_and_inv)
         self._check(self._lib.gdml_predict_hessian_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), E_dev, F_dev,
                                                        H_dev))
+
+    def sym_eig(self, A, vectors=True):
+        """gdml_sym_eig: eigenvalues w (M,n) ascending, eigenvectors V (M,n,n) as rows (largest component positive; None without
+        `vectors`) and the Jacobi sweeps (M,) of symmetric matrices A (M,n,n)."""
+        A = f64(A)
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise ValueError('A must be (M,n,n), got shape {}'.format(A.shape))
+        M, n = A.shape[0], A.shape[1]
+        w, V = np.empty((M, n)), (np.empty((M, n, n)) if vectors else None)
+        sweeps = np.zeros(M, dtype=np.int64)
+        self._check(self._lib.gdml_sym_eig(self._h, _ptr(A), M, n, _ptr(w), _ptr(V), _ptr(sweeps)))
+        return w, V, sweeps
+
+    def sym_eig_dev(self, A_dev, M, n, w_dev, V_dev, sweeps_dev=None):
+        """gdml_sym_eig_dev on device pointers (ints or c_void_p; V_dev / sweeps_dev may be None, V_dev may be A_dev)."""
+        self._check(self._lib.gdml_sym_eig_dev(self._h, A_dev, int(M), int(n), w_dev, V_dev, sweeps_dev))
+
+    def vib_run(self, R, mass, h_scale=1.0, project=2, modes=False, lat_and_inv=None):
+        """gdml_vib_run: squared frequencies of B geometries R (B,3N).  Returns a dict: 'w2' (B,3N), 'n_rigid', 'n_neg',
+        'sweeps' (B), 'E' (B) and 'F' (B,3N) unscaled, and 'modes' (B,3N,3N) when asked for."""
+        n3 = 3 * self.model_n_atoms
+        R = f64(R).reshape(-1, n3)
+        B = R.shape[0]
+        mass = self._masses(mass)
+        lat, lat_inv = _lat_pair(lat_and_inv)
+        w2, E, F = np.empty((B, n3)), np.empty(B), np.empty((B, n3))
+        md = np.empty((B, n3, n3)) if modes else None
+        n_rigid, n_neg, sweeps = (np.zeros(B, dtype=np.int64) for _ in range(3))
+        prm = VibParams(B, self.model_n_atoms, float(h_scale), _ptr(lat), _ptr(lat_inv), int(project))
+        self._check(self._lib.gdml_vib_run(self._h, C.byref(prm), _ptr(R), _ptr(mass), _ptr(w2), _ptr(md), _ptr(n_rigid),
+                                           _ptr(n_neg), _ptr(E), _ptr(F), _ptr(sweeps)))
+        out = dict(w2=w2, n_rigid=n_rigid, n_neg=n_neg, sweeps=sweeps, E=E, F=F)
+        if modes:
+            out['modes'] = md
+        return out
 
     def uncert_prepare(self, sig, lam):
         """Factor A = -K + lam I of the resident training set and keep it for predict_cov (gdml_uncert_prepare).  Raises

@@ -86,6 +86,8 @@ struct Model {
 //                     (gdml_predict_cov_few hands a batch beyond its limit to gdml_predict_cov BEFORE it carves anything; its
 //                     inverted diagonal blocks are the fixed part of SLOT_GRAM_WS and live for one call); tall_trsm in between
 //                     requests SLOT_PANEL_TRSM only.  gdml_factor_extend / gdml_factor_remove release both: they were sized for n
+//   SLOT_VIB_WS       gdml_sym_eig, gdml_sym_eig_dev and gdml_vib_run carve it anew and call none of the others; the Hessian call
+//                     inside gdml_vib_run holds the scratch buffer and SLOT_PREDICT_WS only
 enum CtxSlot {
   SLOT_PREDICT_WS = 0,      // row-split partials of F_x and E (predict_device, predict_fused); workspace of hess_device
   SLOT_MATVEC_OUT = 1,      // forces and energies of this rank's query points (matvec_device)
@@ -102,6 +104,7 @@ enum CtxSlot {
   SLOT_MATVEC_VREF = 12,    // coefficients back in the reference order (matvec_device, sharded with energy constraints)
   SLOT_GRAM_WS = 13,        // queries / coefficients, partial Gram tiles, staged output (gram_workspace)
   SLOT_GRAM_ROWS = 14,      // the (3N x chunk, padded to 128 rows) x K_ld row buffer (gram_workspace)
+  SLOT_VIB_WS = 15,         // matrices, spectra and the eigensolver's work matrices of a chunk (gdml_sym_eig*, gdml_vib_run)
   SLOT_COUNT
 };
 

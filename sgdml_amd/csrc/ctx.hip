@@ -34,7 +34,7 @@ static const char* kKnownOptions[] = {
     "chol.fused_min_rows", "chol.outer", "chol.outer_min_rows", "gemm.balance", "trsm.debug",
     "trsv.persist", "predict.wave_only", "predict.mfma", "predict.fill", "predict.mfma_wide", "predict.fused", "predict.fused_rows", "predict.fused_spin",
     "lu.nb", "comm.force_collectives", "nys.force_qr", "nys.force_fail", "dist.nb", "dist.lookahead", "dist.force_panels", "pcg.depth", "pcg.precon_form", "pcg.f32_rows_per", "pcg.f32_rw", "pcg.f32_min_pivot", "pcg.f32_last_min_pivot", "pcg.f32_gram_rows", "pcg.f32_inplace",
-    "predict.hess_generic", "predict.hess_chunk_rows", "predict.cov_chunk", "predict.cov_global", "predict.cov_few_rows", "predict.cov_few_split_timers", "predict.md_chunk_frames", "predict.md_fused", "predict.pimd_tile", "predict.relax_fused", "predict.relax_chunk_steps", "chol.loo_chunk", "chol.extend_chunk", "chol.remove_chunk", "chol.select_chunk", "chol.select_mem_budget",
+    "predict.hess_generic", "predict.hess_chunk_rows", "predict.cov_chunk", "predict.cov_global", "predict.cov_few_rows", "predict.cov_few_split_timers", "predict.md_chunk_frames", "predict.md_fused", "predict.pimd_tile", "predict.relax_fused", "predict.relax_chunk_steps", "predict.vib_chunk", "chol.loo_chunk", "chol.extend_chunk", "chol.remove_chunk", "chol.select_chunk", "chol.select_mem_budget",
     "chol.evidence_chunk", "chol.evidence_mem_budget", "chol.evidence_global"};
 
 double ctx_opt(const gdml_ctx* ctx, const char* key, double dflt) {

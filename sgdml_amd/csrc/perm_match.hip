@@ -16,6 +16,7 @@
 // The eigenvectors come from sym_eig_kernel below (batched Jacobi) unless the caller brings them; the spanning tree and the group
 // closure are host work (utils/perm.py).
 #include "common.h"
+#include "sym_eig.h"
 
 #include <cmath>
 #include <vector>
@@ -226,9 +227,8 @@ __global__ void __launch_bounds__(64) perm_match_kernel(PermMatchArgs A) {
 // host form here: one batched LAPACK eigh -- 4.5 s for 1000 geometries of 100 atoms, more than the matching itself).  One
 // workgroup per matrix, cyclic two-sided Jacobi with the round-robin ordering: a step rotates N/2 disjoint index pairs at once
 // (angles from the current matrix, then all row updates, then all column updates -- disjoint rotations commute), N - 1 steps
-// visit every pair once.  The working matrix and the accumulated rotations live in LDS when both fit (N <= 100), the rotations
-// in the output buffer otherwise (N <= 140; above that both in device memory).  Converged when the off-diagonal mass is below
-// 1e-30 of the diagonal's -- eigenvectors to a few ulp for separated eigenvalues.  Output: |V| with columns by decreasing
+// visit every pair once.  The sweep loop, its storage routes and its stopping rule are sym_eig.h's (gdml_sym_eig in vib.hip
+// runs the same loop).  Output: |V| with columns by decreasing
 // eigenvalue, the form the matching consumes (only |V| enters, perm.py:66-70, so the sign convention is immaterial).
 // ------------------------------------------------------------------------------------------
 struct SymEigArgs {
@@ -244,16 +244,9 @@ struct SymEigArgs {
 __global__ void __launch_bounds__(256) sym_eig_kernel(SymEigArgs S) {
   extern __shared__ __attribute__((aligned(8))) unsigned char eig_raw[];
   const int N = S.N, NP = S.NP, tid = threadIdx.x;
-  const int ne = (N + 1) & ~1, npairs = ne / 2, m = ne - 1;
-  double* lds = reinterpret_cast<double*>(eig_raw);
-  double* cs = lds;              // [npairs][2]
-  int* pq = reinterpret_cast<int*>(cs + 2 * npairs);  // [npairs][2]
-  double* red = reinterpret_cast<double*>(pq + 2 * npairs + (npairs & 1) * 2);  // [8]
-  double* next = red + 8;
-  double* gw = S.work + (int64_t)blockIdx.x * 2 * N * NP;
-  double* A = S.a_in_lds ? next : gw;
-  if (S.a_in_lds) next += N * NP;
-  double* V = S.v_in_lds ? next : gw + N * NP;
+  const SymEigWork w = sym_eig_carve(eig_raw, N, NP, S.a_in_lds, S.v_in_lds, S.work + (int64_t)blockIdx.x * 2 * N * NP);
+  double* A = w.A;
+  double* V = w.V;
 
   for (int64_t mat = blockIdx.x; mat < S.M; mat += gridDim.x) {
     const double* G = S.adj + mat * N * N;
@@ -264,79 +257,7 @@ __global__ void __launch_bounds__(256) sym_eig_kernel(SymEigArgs S) {
     }
     __threadfence_block();
     __syncthreads();
-    for (int sweep = 0; sweep < 30; ++sweep) {
-      // off-diagonal mass against the diagonal's
-      double off = 0.0, dia = 0.0;
-      for (int e = tid; e < N * N; e += 256) {
-        const int r = e / N, c = e - r * N;
-        const double a = A[r * NP + c];
-        if (r == c) dia += a * a; else off += a * a;
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { off += __shfl_xor(off, o, 64); dia += __shfl_xor(dia, o, 64); }
-      if ((tid & 63) == 0) { red[2 * (tid >> 6)] = off; red[2 * (tid >> 6) + 1] = dia; }
-      __syncthreads();
-      off = red[0] + red[2] + red[4] + red[6];
-      dia = red[1] + red[3] + red[5] + red[7];
-      __syncthreads();
-      if (off <= 1e-30 * (dia + off)) break;
-      for (int step = 0; step < m; ++step) {
-        if (tid < npairs) {
-          int p, q;
-          if (tid == 0) { p = step % m; q = m; }
-          else { p = (step + tid) % m; q = (step + m - tid) % m; }
-          if (p > q) { const int t = p; p = q; q = t; }
-          double c = 1.0, s = 0.0;
-          if (q < N) {
-            const double apq = A[p * NP + q];
-            if (apq != 0.0) {
-              const double tau = (A[q * NP + q] - A[p * NP + p]) / (2.0 * apq);
-              const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-              c = 1.0 / sqrt(1.0 + t * t);
-              s = t * c;
-            }
-          } else {
-            q = -1;  // the padding index of an odd N: no rotation
-          }
-          cs[2 * tid] = c; cs[2 * tid + 1] = s;
-          pq[2 * tid] = p; pq[2 * tid + 1] = q;
-        }
-        __syncthreads();
-        // rows p, q of A:  A <- J^T A
-        for (int e = tid; e < npairs * N; e += 256) {
-          const int k = e / N, j = e - k * N;
-          const int p = pq[2 * k], q = pq[2 * k + 1];
-          if (q < 0) continue;
-          const double c = cs[2 * k], s = cs[2 * k + 1];
-          const double ap = A[p * NP + j], aq = A[q * NP + j];
-          A[p * NP + j] = c * ap - s * aq;
-          A[q * NP + j] = s * ap + c * aq;
-        }
-        __threadfence_block();
-        __syncthreads();
-        // columns p, q of A and of V:  A <- A J,  V <- V J
-        for (int e = tid; e < npairs * N; e += 256) {
-          const int k = e / N, i = e - k * N;
-          const int p = pq[2 * k], q = pq[2 * k + 1];
-          if (q < 0) continue;
-          const double c = cs[2 * k], s = cs[2 * k + 1];
-          const double ap = A[i * NP + p], aq = A[i * NP + q];
-          A[i * NP + p] = c * ap - s * aq;
-          A[i * NP + q] = s * ap + c * aq;
-          const double vp = V[i * NP + p], vq = V[i * NP + q];
-          V[i * NP + p] = c * vp - s * vq;
-          V[i * NP + q] = s * vp + c * vq;
-        }
-        __threadfence_block();
-        __syncthreads();
-        // (the rotated pair's off-diagonal entry is zero up to rounding: make it exactly symmetric-zero)
-        if (tid < npairs && pq[2 * tid + 1] >= 0) {
-          A[pq[2 * tid] * NP + pq[2 * tid + 1]] = 0.0;
-          A[pq[2 * tid + 1] * NP + pq[2 * tid]] = 0.0;
-        }
-        __syncthreads();
-      }
-    }
+    sym_eig_sweeps(w, N, NP, tid);  // (sym_eig.h)
     // columns by decreasing eigenvalue (ties: lower index first), absolute values out
     double* O = S.absv + mat * N * N;
     double* OT = S.absvT + mat * N * N;
@@ -364,15 +285,10 @@ __global__ void __launch_bounds__(256) sym_eig_kernel(SymEigArgs S) {
 static int launch_sym_eig(gdml_ctx* ctx, const double* d_adj, double* d_v, double* d_vT, int64_t M, int N) {
   SymEigArgs e;
   e.adj = d_adj; e.absv = d_v; e.absvT = d_vT; e.M = M; e.N = N;
-  e.NP = (N % 2 == 0) ? N + 1 : N;
-  const int ne = (N + 1) & ~1, npairs = ne / 2;
-  const size_t fixed = (size_t)(2 * npairs) * 8 + (size_t)(2 * npairs + (npairs & 1) * 2) * 4 + 8 * 8;
-  const size_t mat_b = (size_t)N * e.NP * 8, lds_max = 160 * 1024;
-  e.a_in_lds = fixed + mat_b <= lds_max;
-  e.v_in_lds = e.a_in_lds && fixed + 2 * mat_b <= lds_max;
-  const size_t eig_lds = fixed + (e.a_in_lds ? mat_b : 0) + (e.v_in_lds ? mat_b : 0);
-  int64_t eg = (int64_t)ctx->num_cus * (eig_lds > 80 * 1024 ? 1 : eig_lds > 40 * 1024 ? 2 : 4);
-  if (eg > M) eg = M;
+  const SymEigPlan pl = sym_eig_plan(ctx->num_cus, M, N);
+  e.NP = pl.NP; e.a_in_lds = pl.a_in_lds; e.v_in_lds = pl.v_in_lds;
+  const size_t eig_lds = pl.lds;
+  const int64_t eg = pl.grid;
   double* d_w = nullptr;
   GDML_TRY(ctx_alloc(ctx, (void**)&d_w, eg * 2 * (int64_t)N * e.NP * 8));
   e.work = d_w;

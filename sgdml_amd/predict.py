@@ -510,6 +510,94 @@ class GDMLPredict(object):
         out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
         return out
 
+    # ---- harmonic vibrational analysis on the device (gdml_vib_run, csrc/vib.hip)
+
+    _VIB_PROJECT = {'none': 0, 'trans': 1, 'rigid': 2}
+
+    def vibrations(self, R, masses, project=None, modes=False, lattice=None, f_unit=1.0):
+        """Squared harmonic frequencies (and normal modes) of B geometries on the device: eigenvalues of the mass-weighted
+        Hessian f_unit * H_ij / sqrt(m_i m_j), H the Hessian of predict_hessian(), with the rigid-body motion projected out.
+        R: (B,3N) or (3N,); masses (N,); f_unit as in run_md (accelerations = f_unit * F / m), so w2 comes in the caller's time
+        unit^-2.  project: 'rigid' (translations and rotations; the default without a lattice), 'trans' (translations; the
+        default with one -- 'rigid' with a lattice is a ValueError), 'none'.  lattice: as in predict().
+        Returns a dict: 'w2' (B,3N) -- the vibrational entries ascending (imaginary modes negative, first), then n_rigid exact
+        zeros; 'freq' = sign(w2) sqrt|w2|; 'n_rigid' (B; 6, 5 for a linear molecule, 3 for an atom or 'trans'); 'n_imag' (B;
+        vibrational w2 below -3N eps |D|_F); 'E' (B) and 'F' (B,3N) scaled like predict(); 'sweeps' (B; Jacobi sweeps); with
+        modes=True 'modes' (B,3N,3N): row k the mass-weighted orthonormal vector of w2[k] (the last n_rigid rows span the
+        rigid motions).  Batches are split over the predictor's devices like predict_hessian's.  ValueError for non-finite or
+        misshapen input before anything is launched."""
+        n3 = 3 * self.n_atoms
+        if R is None:
+            raise ValueError('vibrations needs geometries R (there is no training-set mode)')
+        R = _as_batch(R, n3)
+        masses = np.asarray(masses, dtype=np.float64)
+        if masses.shape != (self.n_atoms,):
+            raise ValueError('masses must be ({},), got shape {}'.format(self.n_atoms, masses.shape))
+        if not (np.isfinite(R).all() and np.isfinite(masses).all()):
+            raise ValueError('R and masses must be finite')
+        if not (masses > 0.0).all():
+            raise ValueError('masses must be positive')
+        _check_finite(('f_unit', f_unit))
+        if not float(f_unit) > 0.0:
+            raise ValueError('f_unit must be positive')
+        lat_and_inv = self._lat_and_inv(lattice)
+        if project is None:
+            project = 'rigid' if lat_and_inv is None else 'trans'
+        if project not in self._VIB_PROJECT:
+            raise ValueError("project must be None, 'none', 'trans' or 'rigid', got {!r}".format(project))
+        if project == 'rigid' and lat_and_inv is not None:
+            raise ValueError("project='rigid' with a lattice: rotations are no symmetry of a periodic cell (use 'trans')")
+        h_scale, pj = self.std * float(f_unit), self._VIB_PROJECT[project]
+        parts = self._sharded(R.shape[0], lambda ctx, lo, hi: ctx.vib_run(R[lo:hi], masses, h_scale=h_scale, project=pj,
+                                                                          modes=modes, lat_and_inv=lat_and_inv),
+                              min_shard=self._min_shard_hessian)
+        out = parts[0] if len(parts) == 1 else {k: np.concatenate([p_[k] for p_ in parts]) for k in parts[0]}
+        out['E'] *= self.std
+        out['E'] += self.c
+        out['F'] *= self.std
+        out['n_imag'] = out.pop('n_neg')
+        out['freq'] = np.sign(out['w2']) * np.sqrt(np.abs(out['w2']))
+        return out
+
+    @staticmethod
+    def harmonic_thermo(w2_vib, kT, hbar):
+        """Quantum harmonic oscillators of squared frequencies w2_vib (the vibrational entries of vibrations()['w2'], any
+        shape; summed over the last axis) at temperature kT: 'zpe' = sum hbar w / 2, 'F_vib' = zpe + kT sum ln(1 - exp(-hbar w
+        / kT)), 'U_vib' = zpe + sum hbar w / (exp(hbar w / kT) - 1) and 'S_vib' = (U_vib - F_vib) / kT in units of k_B.  kT = 0
+        gives the zero-point values.  ValueError for a negative or non-finite entry, kT < 0 or hbar <= 0.  Host only."""
+        w2 = np.asarray(w2_vib, dtype=np.float64)
+        if not np.isfinite(w2).all() or (w2 < 0.0).any():
+            raise ValueError('harmonic_thermo needs finite squared frequencies >= 0 (leave imaginary and rigid modes out)')
+        if not (np.isfinite(kT) and kT >= 0.0 and np.isfinite(hbar) and hbar > 0.0):
+            raise ValueError('harmonic_thermo needs kT >= 0 and hbar > 0')
+        e = float(hbar) * np.sqrt(w2)  # level spacings
+        zpe = 0.5 * e.sum(axis=-1)
+        if kT == 0.0:
+            z = np.zeros_like(zpe)
+            return dict(zpe=zpe, F_vib=zpe.copy(), U_vib=zpe.copy(), S_vib=z)
+        x = e / float(kT)
+        with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+            F = zpe + kT * np.log(-np.expm1(-x)).sum(axis=-1)
+            U = zpe + np.where(x > 0.0, e / np.expm1(x), kT).sum(axis=-1)
+        return dict(zpe=zpe, F_vib=F, U_vib=U, S_vib=(U - F) / kT)
+
+    @staticmethod
+    def htst_prefactor(w2_min, w2_saddle):
+        """Prefactor of harmonic transition-state theory, (1 / 2 pi) prod w_min / prod' w_saddle, from the vibrational squared
+        frequencies of the minimum (n entries, all positive) and of the saddle (n entries, exactly one negative: left out of
+        the product), computed in logarithms.  With neb()'s 'barrier': rate = prefactor * exp(-barrier / kT).  Host only."""
+        a, b = np.asarray(w2_min, dtype=np.float64).ravel(), np.asarray(w2_saddle, dtype=np.float64).ravel()
+        if a.size != b.size:
+            raise ValueError('htst_prefactor needs as many modes at the minimum as at the saddle, got {} and {}'.format(a.size, b.size))
+        if not (np.isfinite(a).all() and np.isfinite(b).all()):
+            raise ValueError('htst_prefactor needs finite squared frequencies')
+        if not (a > 0.0).all():
+            raise ValueError('htst_prefactor: every mode of the minimum must have w2 > 0')
+        if int((b < 0.0).sum()) != 1 or (b == 0.0).any():
+            raise ValueError('htst_prefactor: the saddle must have exactly one negative w2 and no zero one, got {} negative'.format(
+                int((b < 0.0).sum())))
+        return float(np.exp(0.5 * (np.log(a).sum() - np.log(b[b > 0.0]).sum())) / (2.0 * np.pi))
+
     # ---- nudged elastic band on the device (gdml_neb_run, csrc/neb.hip)
 
     @staticmethod
