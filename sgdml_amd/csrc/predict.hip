@@ -10,9 +10,10 @@
 //   with alphas_E: F_x += aE_j b (n+sig) d ; E' += aE_j (1 + n/sig (1 + n/(3 sig))) exp(-n/sig)
 // and finally F = J_x^T F_x (desc.py:388-408).
 //
-// Three kernels, chosen by batch size (predict_device): predict_mfma_kernel<NT> for B >= 256 and D <= 256
-// (both contractions on v_mfma_f64_16x16x4_f64, see its header below), predict_bulk_kernel<NCH> (its VALU
-// predecessor, GDML_PREDICT_NO_MFMA=1) and predict_kernel<KPL,QB> for small batches / large D:
+// Five routes, chosen on the host by predict_plan.h (its header states the conditions; predict_device_w launches the plan):
+// predict_mfma_kernel<NT> for B >= 256 and D <= 256 (both contractions on v_mfma_f64_16x16x4_f64, see its header below),
+// predict_bulk_kernel<NCH> (its VALU predecessor, predict.mfma = 0), predict_big_kernel<KT> for D > 1024, the GEMM pipeline
+// of predict_wide.hip, and predict_kernel<KPL,QB> for small batches:
 // Layout of predict_kernel: the descriptor index k runs across the 64 lanes of a wavefront (KPL entries per
 // lane), so every table row is one coalesced read; each wavefront owns QB queries (held in
 // registers) and a contiguous split of the table rows, reduces |d|^2 and a with cross-lane
@@ -22,6 +23,7 @@
 
 #include "common.h"
 #include "fused_core.h"
+#include "predict_plan.h"
 #include <chrono>
 #include <thread>
 
@@ -272,8 +274,7 @@ __global__ void __launch_bounds__(512) predict_big_kernel(PredArgs A) {
 //            F_x[q][k] += w1 (x - X_r[k]) - b2 JA_r[k] over the 32 rows.
 // Per (query,row,k): 6 VALU instructions and < 2 LDS reads.
 // ------------------------------------------------------------------------------------------
-#define PQ 32
-#define PR 32
+// PQ = 32 queries per workgroup, PR = 32 table rows per tile: predict_plan.h
 #define PKC 32
 #define PPITCH 34
 
@@ -487,9 +488,7 @@ __device__ __forceinline__ void mfma_results_ready(d4p& c0, d4p& c1) {
 __device__ __forceinline__ void mfma_results_ready_v(d4p& c0, d4p& c1) {
   asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" : "+v"(c0), "+v"(c1));
 }
-#define MQ 64  // queries per workgroup
-#define MR 16  // table rows per tile
-
+// MQ = 64 queries per workgroup, MR = 16 table rows per tile: predict_plan.h
 template <int NT>  // NT = number of 16-column tiles covering D
 __global__ void __launch_bounds__(256, 1) predict_mfma_kernel(PredArgs A, const double* __restrict__ nX,
                                                              const double* __restrict__ cX) {
@@ -917,28 +916,96 @@ __global__ void __launch_bounds__(256) predict_epilogue_virial_kernel(const doub
   }
 }
 
-template <int KPL, int QB>
-static void launch_pred(gdml_ctx* ctx, const PredArgs& A) {
-  int64_t n_qt = (A.B + QB - 1) / QB;
-  int64_t waves = n_qt * A.JS;
-  hipLaunchKernelGGL((predict_kernel<KPL, QB>), dim3((unsigned)ceil_div(waves, 4)), dim3(256), 0,
-                     ctx->stream, A);
-}
-
+// One launch function per route of predict_plan.h: the route's kernel at the plan's template selector, grid and LDS size.
 template <int KPL>
-static void dispatch_qb(gdml_ctx* ctx, const PredArgs& A, int QB) {
-  constexpr int MAXQB = KPL <= 4 ? 8 : (KPL == 8 ? 4 : (KPL == 16 ? 2 : 1));
-  if (QB > MAXQB) QB = MAXQB;
-  if constexpr (MAXQB >= 8) if (QB == 8) return launch_pred<KPL, 8>(ctx, A);
-  if constexpr (MAXQB >= 4) if (QB >= 4) return launch_pred<KPL, 4>(ctx, A);
-  if constexpr (MAXQB >= 2) if (QB >= 2) return launch_pred<KPL, 2>(ctx, A);
-  return launch_pred<KPL, 1>(ctx, A);
+static int launch_wave_qb(gdml_ctx* ctx, const PredArgs& A, const PredPlan& p) {
+  constexpr int MAXQB = KPL <= 4 ? 8 : (KPL == 8 ? 4 : (KPL == 16 ? 2 : 1));  // the plan stays within it
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+#define WC(v)                                                                        \
+  if constexpr (MAXQB >= v)                                                          \
+    if (p.QB == v) {                                                                 \
+      hipLaunchKernelGGL((predict_kernel<KPL, v>), grid, block, 0, ctx->stream, A);  \
+      return GDML_OK;                                                                \
+    }
+  WC(8) WC(4) WC(2) WC(1)
+#undef WC
+  return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "predict: bad query block");
 }
 
-static int max_qb_for(int KPL) { return KPL <= 4 ? 8 : (KPL == 8 ? 4 : (KPL == 16 ? 2 : 1)); }
+static int launch_wave(gdml_ctx* ctx, const PredArgs& A, const PredPlan& p) {
+  switch (p.sel) {
+    case 1: return launch_wave_qb<1>(ctx, A, p);
+    case 2: return launch_wave_qb<2>(ctx, A, p);
+    case 4: return launch_wave_qb<4>(ctx, A, p);
+    case 8: return launch_wave_qb<8>(ctx, A, p);
+    case 16: return launch_wave_qb<16>(ctx, A, p);
+    default: return launch_wave_qb<32>(ctx, A, p);
+  }
+}
+
+static int launch_big(gdml_ctx* ctx, const PredArgs& A, const PredPlan& p) {
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  if (p.sel == 8) hipLaunchKernelGGL(predict_big_kernel<8>, grid, block, 0, ctx->stream, A);
+  else hipLaunchKernelGGL(predict_big_kernel<16>, grid, block, 0, ctx->stream, A);
+  return GDML_OK;
+}
+
+static int launch_bulk(gdml_ctx* ctx, const PredArgs& A, const PredPlan& p) {
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  switch (p.sel) {
+#define BC(v) case v: hipLaunchKernelGGL(predict_bulk_kernel<v>, grid, block, 0, ctx->stream, A); break;
+    BC(1) BC(2) BC(3) BC(4) BC(5) BC(6) BC(7) default: hipLaunchKernelGGL(predict_bulk_kernel<8>, grid, block, 0, ctx->stream, A); break;
+#undef BC
+  }
+  return GDML_OK;
+}
+
+// row statistics of the table first (SLOT_PREDICT_STATS), then the kernel
+static int launch_mfma(gdml_ctx* ctx, const PredArgs& A, const PredPlan& p) {
+  const Model& md = ctx->model;
+  double* stats;
+  GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_STATS, p.stats_bytes, &stats));
+  hipLaunchKernelGGL(row_stats_kernel, dim3(ceil_div(A.MP, 4)), dim3(256), 0, ctx->stream, md.xp, md.jap, A.MP, A.D, stats,
+                     stats + A.MP);
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  switch (p.sel) {
+#define MC(v)                                                                                              \
+  case v:                                                                                                  \
+    hipFuncSetAttribute((const void*)predict_mfma_kernel<v>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                        (int)p.lds_bytes);                                                                 \
+    hipLaunchKernelGGL(predict_mfma_kernel<v>, grid, block, p.lds_bytes, ctx->stream, A, stats, stats + A.MP); \
+    break;
+    MC(2) MC(4) MC(6) MC(8) MC(10) MC(12) MC(14) MC(16)
+#undef MC
+    default: return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "predict: bad tile count");
+  }
+  ctx->launch_counter++;
+  return GDML_OK;
+}
+
+// large molecules: the contractions as tiled fp64-MFMA GEMMs (predict_wide.hip, which plans, counts and checks its launches)
+static int launch_wide(gdml_ctx* ctx, const PredArgs& A, const PredPlan&) {
+  return predict_wide_device(ctx, A.xq, A.B, A.part_F, A.part_E);
+}
+
+// Sums the plan's JS partials in split order and applies J^T; F_x through an LDS row, or in place where the row is longer
+// than that (D > 8192); with d_W the kernel that also writes W (B,3,3).
+static void launch_epilogue(gdml_ctx* ctx, const PredPlan& p, const PredArgs& A, const double* d_gq, int N, double* d_E,
+                            double* d_F, double* d_W) {
+  const dim3 grid((unsigned)A.B), block(256);
+#define EPI(lds_row)                                                                                                     \
+  if (p.epi_virial)                                                                                                      \
+    hipLaunchKernelGGL(predict_epilogue_virial_kernel<lds_row>, grid, block, p.epi_lds_bytes, ctx->stream, A.part_F,     \
+                       A.part_E, A.xq, d_gq, A.B, N, A.D, p.epi_JS, d_E, d_F, d_W);                                      \
+  else                                                                                                                   \
+    hipLaunchKernelGGL(predict_epilogue_kernel<lds_row>, grid, block, p.epi_lds_bytes, ctx->stream, A.part_F, A.part_E,  \
+                       d_gq, A.B, N, A.D, p.epi_JS, d_E, d_F);
+  if (p.epi_lds_row) { EPI(true) } else { EPI(false) }
+#undef EPI
+}
 
 // d_W == nullptr: the launches of gdml_predict.  Otherwise the epilogue is predict_epilogue_virial_kernel, which also writes
-// W (B,3,3); d_F may then be NULL.
+// W (B,3,3); d_F may then be NULL.  Plan (predict_plan.h) -> workspace -> the route's launch -> epilogue.
 static int predict_device_w(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B, double* d_E, double* d_F,
                             double* d_W) {
   Model& md = ctx->model;
@@ -946,143 +1013,31 @@ static int predict_device_w(gdml_ctx* ctx, const double* d_xq, const double* d_g
   if (B == 0) return GDML_OK;
   const int D = md.D, N = md.N;
   const int64_t MP = md.M * md.P;
-  int KPL = 1;
-  while (KPL * 64 < D) KPL <<= 1;
-  const bool big = D > 1024;  // beyond the register-resident wave kernel
-  // below ~1e9 (row, query, descriptor) triples the seven launches of the pipeline cost more than the wave kernel
-  // (tools/predict_wide_probe.py); option predict.mfma_wide = 2 forces it (tests)
-  const int wide_opt = ctx_opt_i(ctx, "predict.mfma_wide", 1);
-  // D > 8192 (N > 128): beyond the register rows of predict_big_kernel<16> -- the GEMM pipeline has no size limit and
-  // takes every batch there (a single query too: correct, if not what the pipeline is tuned for)
-  const bool beyond = D > 8192;
-  const bool wide = beyond || ((B >= 256) && (D > 256) && !ctx_opt_i(ctx, "predict.wave_only", 0) &&
-                               (wide_opt == 2 || (wide_opt == 1 && (double)MP * (double)B * (double)D >= 1.0e9)));
-  if (wide) {  // large molecules: the contractions as tiled fp64-MFMA GEMMs (predict_wide.hip)
-    double* part;
-    GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, (B * (int64_t)D + B) * 8, &part));
-    const int slot = ktime_begin(ctx);
-    GDML_TRY(predict_wide_device(ctx, d_xq, B, part, part + B * (int64_t)D));
-    ktime_end(ctx, slot, "predict", 10.0 * (double)D * (double)B * (double)MP);
-    if (d_W && beyond)
-      hipLaunchKernelGGL(predict_epilogue_virial_kernel<false>, dim3((unsigned)B), dim3(256), 0, ctx->stream, part,
-                         part + B * (int64_t)D, d_xq, d_gq, B, N, D, 1, d_E, d_F, d_W);
-    else if (d_W)
-      hipLaunchKernelGGL(predict_epilogue_virial_kernel<true>, dim3((unsigned)B), dim3(256), (size_t)D * 8, ctx->stream,
-                         part, part + B * (int64_t)D, d_xq, d_gq, B, N, D, 1, d_E, d_F, d_W);
-    else if (beyond)  // F_x row longer than the LDS row of the epilogue: read in place (JS = 1)
-      hipLaunchKernelGGL(predict_epilogue_kernel<false>, dim3((unsigned)B), dim3(256), 0, ctx->stream, part,
-                         part + B * (int64_t)D, d_gq, B, N, D, 1, d_E, d_F);
-    else
-      hipLaunchKernelGGL(predict_epilogue_kernel<true>, dim3((unsigned)B), dim3(256), (size_t)D * 8, ctx->stream, part,
-                         part + B * (int64_t)D, d_gq, B, N, D, 1, d_E, d_F);
-    ctx->launch_counter++;
-    HIP_CHECK(ctx, hipGetLastError());
-    return GDML_OK;
-  }
-  const bool bulk = !big && (B >= 256) && (D <= 256) && !ctx_opt_i(ctx, "predict.wave_only", 0);
-  const bool mfma = bulk && ctx_opt_i(ctx, "predict.mfma", 1);
-  int QB = max_qb_for(KPL);
-  while (QB > 1 && B < QB) QB >>= 1;  // do not waste query slots
-  {
-    // small batches: fewer queries per wavefront until the grid (query tiles x row splits) fills the chip
-    const int fill = ctx_opt_i(ctx, "predict.fill", 1024);
-    const int64_t js_cap = MP / 16 > 1 ? MP / 16 : 1;
-    while (QB > 1 && ((B + QB - 1) / QB) * js_cap < fill) QB >>= 1;
-  }
-  int64_t n_qt = mfma ? (B + MQ - 1) / MQ : bulk ? (B + PQ - 1) / PQ : (B + QB - 1) / QB;
-  int64_t JS = ((mfma ? 512 : bulk ? 2048 : 4096) + n_qt - 1) / n_qt;
-  int64_t max_js = bulk ? (MP / 64 > 1 ? MP / 64 : 1) : (MP / 16 > 1 ? MP / 16 : 1);
-  if (big) {  // one workgroup per (query, split)
-    n_qt = B;
-    JS = (1024 + B - 1) / B;
-    max_js = MP / 4 > 1 ? MP / 4 : 1;
-  }
-  if (JS > max_js) JS = max_js;
-  if (JS < 1) JS = 1;
-  if (mfma) {
-    // one workgroup per CU: pick the split count that minimises (rounds of workgroups) x (row tiles per
-    // workgroup + fixed per-workgroup cost of ~3 tiles)
-    const int64_t ncu = ctx->num_cus;
-    int64_t best = 1, best_cost = INT64_MAX;
-    for (int64_t js = 1; js <= 64 && js <= max_js; ++js) {
-      const int64_t rows = (((MP + js - 1) / js) + MR - 1) / MR * MR;
-      const int64_t js_eff = (MP + rows - 1) / rows;
-      const int64_t rounds = (n_qt * js_eff + ncu - 1) / ncu;
-      const int64_t cost = rounds * (rows / MR + 3);
-      if (cost < best_cost) {
-        best_cost = cost;
-        best = js;
-      }
-    }
-    JS = best;
-  }
-  int64_t rps = (MP + JS - 1) / JS;
-  if (bulk) rps = (rps + PR - 1) / PR * PR;
-  JS = (MP + rps - 1) / rps;
+  PredPlanIn in;
+  in.D = D; in.N = N; in.MP = MP; in.B = B; in.num_cus = ctx->num_cus; in.want_virial = d_W != nullptr;
+  in.wave_only = ctx_opt_i(ctx, "predict.wave_only", 0);
+  in.mfma = ctx_opt_i(ctx, "predict.mfma", 1);
+  in.mfma_wide = ctx_opt_i(ctx, "predict.mfma_wide", 1);
+  in.fill = ctx_opt_i(ctx, "predict.fill", 1024);
+  const PredPlan p = predict_plan(in);
 
-  int64_t need = (JS * B * (int64_t)D + JS * B) * 8;
   double* part;
-  GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, need, &part));
-
+  GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, p.ws_bytes, &part));
   PredArgs A;
   A.xq = d_xq; A.xp = md.xp; A.jap = md.jap; A.aE = md.has_aE ? md.aE : nullptr;
-  A.B = B; A.MP = MP; A.D = D; A.sig = md.sig; A.JS = (int)JS; A.rows_per_split = rps;
-  A.part_F = part; A.part_E = part + JS * B * (int64_t)D;
+  A.B = B; A.MP = MP; A.D = D; A.sig = md.sig; A.JS = p.JS; A.rows_per_split = p.rows_per_split;
+  A.part_F = part; A.part_E = part + p.JS * B * (int64_t)D;
+
+  static int (*const launch[])(gdml_ctx*, const PredArgs&, const PredPlan&) = {launch_wave, launch_big, launch_bulk, launch_mfma,
+                                                                               launch_wide};  // in the order of PredRoute
   const int slot = ktime_begin(ctx);
-  if (mfma) {
-    double* stats;
-    GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_STATS, 2 * MP * 8, &stats));
-    hipLaunchKernelGGL(row_stats_kernel, dim3(ceil_div(MP, 4)), dim3(256), 0, ctx->stream, md.xp, md.jap, MP,
-                       D, stats, stats + MP);
-    dim3 grid((unsigned)n_qt, (unsigned)JS);
-    const int nt = 2 * ((D + 31) / 32);  // even number of 16-column tiles
-    const size_t lds_bytes = (size_t)4 * MR * (16 * nt + 2) * 8;
-    switch (nt) {
-#define MC(v)                                                                                         \
-  case v:                                                                                             \
-    hipFuncSetAttribute((const void*)predict_mfma_kernel<v>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                        (int)lds_bytes);                                                              \
-    hipLaunchKernelGGL(predict_mfma_kernel<v>, grid, dim3(256), lds_bytes, ctx->stream, A, stats,      \
-                       stats + MP);                                                                   \
-    break;
-      MC(2) MC(4) MC(6) MC(8) MC(10) MC(12) MC(14) MC(16)
-#undef MC
-      default: return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "predict: bad tile count");
-    }
-    ctx->launch_counter++;
-  } else if (bulk) {
-    dim3 grid((unsigned)n_qt, (unsigned)JS);
-    const int nch = (D + 31) / 32;
-    switch (nch) {
-#define BC(v) case v: hipLaunchKernelGGL(predict_bulk_kernel<v>, grid, dim3(256), 0, ctx->stream, A); break;
-      BC(1) BC(2) BC(3) BC(4) BC(5) BC(6) BC(7) default: hipLaunchKernelGGL(predict_bulk_kernel<8>, grid, dim3(256), 0, ctx->stream, A); break;
-#undef BC
-    }
-  } else if (big) {
-    dim3 grid((unsigned)B, (unsigned)JS);
-    if (D <= 4096) hipLaunchKernelGGL(predict_big_kernel<8>, grid, dim3(512), 0, ctx->stream, A);
-    else hipLaunchKernelGGL(predict_big_kernel<16>, grid, dim3(512), 0, ctx->stream, A);
-  } else {
-    switch (KPL) {
-      case 1: dispatch_qb<1>(ctx, A, QB); break;
-      case 2: dispatch_qb<2>(ctx, A, QB); break;
-      case 4: dispatch_qb<4>(ctx, A, QB); break;
-      case 8: dispatch_qb<8>(ctx, A, QB); break;
-      case 16: dispatch_qb<16>(ctx, A, QB); break;
-      default: dispatch_qb<32>(ctx, A, QB); break;
-    }
-  }
+  GDML_TRY(launch[p.route](ctx, A, p));
   // algorithmic work: ~10 D flops per (query, table row)
   ktime_end(ctx, slot, "predict", 10.0 * (double)D * (double)B * (double)MP);
-  ctx->launch_counter++;
+  if (p.route != PRED_WIDE) ctx->launch_counter++;  // the route's kernel; predict_wide_device has counted its own
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) {
-    if (d_W)
-      hipLaunchKernelGGL(predict_epilogue_virial_kernel<true>, dim3((unsigned)B), dim3(256), (size_t)D * 8,
-                         ctx->stream, A.part_F, A.part_E, d_xq, d_gq, B, N, D, (int)JS, d_E, d_F, d_W);
-    else
-      hipLaunchKernelGGL(predict_epilogue_kernel<true>, dim3((unsigned)B), dim3(256), (size_t)D * 8,
-                         ctx->stream, A.part_F, A.part_E, d_gq, B, N, D, (int)JS, d_E, d_F);
+    launch_epilogue(ctx, p, A, d_gq, N, d_E, d_F, d_W);
     ctx->launch_counter++;
     e = hipGetLastError();
   }
