@@ -25,10 +25,10 @@
 //   hess_fx_kernel        per query: the group partials of F_x, E', tau summed in order; F = J_x^T F_x.
 //   hess_epilogue_kernel  per (16-row block of H, query): split partials summed in order, + tau J_x^T J_x - sum F_x grad^2 x
 //                         (both block-sparse), the lower triangle mirrored; H written (B, 3N, 3N) row-major, both triangles.
-// Dispatch: D <= 512 (N <= 32): hess_proj_wave_kernel<KPL> (one wavefront per row group, KPL = D / 64 rounded up to a
-// power of two); otherwise hess_proj_kernel<KT>, KT = ceil(D / 256) rounded up to 1, 2, 4, 8, 16, 32, 48 (N <= 157); above
-// that, or with option predict.hess_generic = 1 (which also skips the wavefront variant), the KT = 0 variant.  d must fit the
-// LDS (D <= 19456, N <= 197): larger molecules are GDML_ERR_UNSUPPORTED.
+// Dispatch: D <= 512 (N <= 32): hess_proj_wave_kernel<KPL> (one wavefront per row group, KPL = D / 64 rounded up to 1, 2,
+// 4, 8); otherwise hess_proj_kernel<KT>, KT = ceil(D / 256) >= 3 rounded up to 4, 8, 16, 32, 48 (N <= 157); above that, or
+// with option predict.hess_generic = 1 (which also skips the wavefront variant), the KT = 0 variant.  d must fit the LDS
+// (D <= 19456, N <= 197): larger molecules are GDML_ERR_UNSUPPORTED.
 // Departure from one fused fp64-MFMA kernel with J_x in LDS: projection and rank-2 update are separate passes through
 // bounded panels, which keeps every N, P, lattice and energy-constraint case on one deterministic path; the rank-2 update
 // is VALU.  The projection pass is the measured bottleneck and the first thing to move onto the MFMA pipe.
@@ -522,18 +522,19 @@ int hess_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B
   double* tau = fx + nFX;
 
   const void* proj_fn = nullptr;
-  switch (KT) {
-#define HP(v) case v: proj_fn = (const void*)hess_proj_kernel<v>; break;
-    HP(0) HP(1) HP(2) HP(4) HP(8) HP(16) HP(32) HP(48)
-#undef HP
-    default: return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "hessian: bad register tile %d", KT);
-  }
-  if (wave) {
+  if (wave) {  // D <= 512: KPL <= 8
     switch (KPL) {
 #define HW(v) case v: proj_fn = (const void*)hess_proj_wave_kernel<v>; break;
-      HW(1) HW(2) HW(4) HW(8) HW(16) HW(32)
+      HW(1) HW(2) HW(4) HW(8)
 #undef HW
       default: return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "hessian: bad lane tile %d", KPL);
+    }
+  } else {  // D > 512 (KT >= 4), or forced KT = 0
+    switch (KT) {
+#define HP(v) case v: proj_fn = (const void*)hess_proj_kernel<v>; break;
+      HP(0) HP(4) HP(8) HP(16) HP(32) HP(48)
+#undef HP
+      default: return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "hessian: bad register tile %d", KT);
     }
   }
   if (lds_bytes > 64 * 1024) HIP_CHECK(ctx, hipFuncSetAttribute(proj_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -555,12 +556,12 @@ int hess_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B
       if (wave) {
         switch (KPL) {
 #define HL(v) case v: hipLaunchKernelGGL(hess_proj_wave_kernel<v>, pg, dim3(256), lds_bytes, ctx->stream, P); break;
-          HL(1) HL(2) HL(4) HL(8) HL(16) HL(32)
+          HL(1) HL(2) HL(4) HL(8)
 #undef HL
         }
       } else switch (KT) {
 #define HL(v) case v: hipLaunchKernelGGL(hess_proj_kernel<v>, pg, dim3(256), lds_bytes, ctx->stream, P); break;
-        HL(0) HL(1) HL(2) HL(4) HL(8) HL(16) HL(32) HL(48)
+        HL(0) HL(4) HL(8) HL(16) HL(32) HL(48)
 #undef HL
       }
       HessRank2Args R2;
