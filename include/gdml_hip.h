@@ -184,10 +184,11 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *                         32 = always 32.  The results do not depend on it
  *   predict.relax_fused (1)       gdml_relax_run with 1-8 geometries of a molecule with D <= 256: one launch per evaluation (0: the
  *                         general route of two pieces per evaluation)
- *   predict.relax_chunk_steps (32)  evaluations gdml_relax_run queues between two synchronisations (the host learns at a chunk's
- *                         end which replicas froze); the results do not depend on it
+ *   predict.relax_chunk_steps (32)  evaluations gdml_relax_run (and gdml_neb_run, gdml_ef_run) queues between two
+ *                         synchronisations (the host learns at a chunk's end which replicas froze); the results do not depend on it
  *   predict.vib_chunk (0)         geometries per chunk of gdml_vib_run (0 = as many as keep its Hessians and work matrices under
- *                         256 MiB); steps b to d of that entry do not depend on it
+ *                         256 MiB); steps b to d of that entry do not depend on it.  Also the geometries per slice of an
+ *                         evaluation of gdml_ef_run
  *   chol.loo_chunk (64)            training points per pass of gdml_loo (their rows of L^-T are 3N n doubles each; fewer when free
  *                         memory is short).  The results do not depend on it
  *   chol.extend_chunk (64)         points per pass of gdml_factor_extend (their 3N rows are assembled, solved and factored together;
@@ -667,6 +668,81 @@ typedef struct gdml_vib_params {
 } gdml_vib_params;       /* 48 bytes */
 int gdml_vib_run(gdml_ctx* ctx, const gdml_vib_params* params, const double* R, const double* masses, double* w2,
                  double* modes /* or NULL */, int64_t* n_rigid, int64_t* n_neg, double* E, double* F, int64_t* sweeps);
+
+/* Eigenvector following on the device: B independent geometries of the model's molecule move to a stationary point of the
+ * energy -- a minimum (order = 0) or a first-order saddle (order = 1) -- by quasi-Newton steps in the eigenbasis of the analytic
+ * Hessian (Cerjan, Miller, J. Chem. Phys. 75, 2800 (1981); Baker, J. Comput. Chem. 7, 385 (1986); the per-mode rational-function
+ * step in closed form), with a trust radius and mode tracking.  What follows gdml_neb_run with a climbing image (its saddle,
+ * tightened to any force threshold) and gdml_relax_run (quadratic convergence near the minimum).  Cartesian coordinates and
+ * unit masses, as in gdml_relax_run.  Positions, the state and the Hessians stay resident in device memory.  The reference has
+ * no counterpart.
+ * One evaluation t = 0, 1, ... of a geometry that is still active.  g = -f_scale F' (f_scale = std times the caller's unit factor):
+ *   1. E', F', H' = gdml_predict_hessian_dev of all B geometries (frozen ones included; their results are discarded).
+ *   2. gdml_vib_run's step b with unit masses and h_scale = f_scale: D_s = P D P + Lambda Q^T Q (project as there).
+ *   3. gdml_sym_eig_dev's kernel on D_s: w ascending, v_i as rows.  The top n_rigid pairs are the rigid modes at Lambda; the
+ *      first nv = 3N - n_rigid pairs are the vibrational set, the only ones the step uses.  n_neg and tau as in gdml_vib_run.
+ *   4. One kernel, one workgroup of 256 threads per geometry:
+ *      a. f_atom = the largest atomic |g|.  E' and f_atom go into the history.  A non-finite r, F', E' or eigenvalue sets
+ *         first_bad_step (to t), as does a matrix the Jacobi loop cannot finish; such a geometry never counts as converged.
+ *      d. Followed mode k (order = 1): 0 without a follow vector t, else argmax_i |v_i . t| over i < nv, ties to the lowest i.
+ *         order = 0: k = 0.  w_follow_hist records w_k, k_follow_hist k.  E_end, F_end, w_end, n_rigid, n_neg and mode_end
+ *         (v_k; zeros for order = 0) take this evaluation's values.
+ *         f_atom < fmax: converged.  Otherwise t = max_steps: the budget of this call is used up.  Either way the geometry
+ *         freezes: R, t, trust, E_prev, dE_pred, flags and the outputs above are never written again (the state is the one this
+ *         evaluation started from, so a continuation repeats this evaluation and goes on).
+ *      b. Trust update, when flags bit 0 is set and |dE_pred| > 1e-8 max(|E'|, |E_prev|) f_scale (below that the ratio is the
+ *         predictor's rounding noise): rho = f_scale (E' - E_prev) / dE_pred;  rho < 0.25 or rho > 1.75: trust <- max(trust / 2,
+ *         trust_min);  0.75 < rho < 1.25 and bit 1 set: trust <- min(2 trust, trust_max).  No step is ever rejected.
+ *      c. gt_i = v_i . g for i < nv.
+ *      e. d_i = |w_i| + sqrt(w_i^2 + 4 gt_i^2);  s_i = -2 gt_i / d_i for a minimised mode, +2 gt_i / d_i for the maximised mode
+ *         k (order = 1), 0 when d_i = 0: Newton's step where the curvature has the wanted sign and the gradient is small, a
+ *         step along the right side of the gradient where it has not.
+ *      f. |s|_2 > trust: s <- s (trust / |s|_2), bit 1 set; otherwise bit 1 cleared.
+ *      g. dE_pred <- sum_i gt_i s_i + w_i s_i^2 / 2 (the scaled s);  E_prev <- E';  bit 0 set;  R <- R + sum_i s_i v_i;
+ *         t <- v_k (order = 1 with a follow vector).
+ *   Sums over modes: per-thread partial sums in index order (mode i, i + 256, ...), then gdml_md_run's 256-slot tree; v_i . g
+ *   and v_i . t: one wavefront per row, lanes stride the columns, the xor butterfly; the back-projection sums over i ascending.
+ *   No atomics.  A call makes at most max_steps + 1 evaluations per geometry; E_end, F_end, w_end are always those of R.
+ * The driver is gdml_relax_run's general route: plain launches queued back to back, the host synchronises once per chunk
+ *   (predict.relax_chunk_steps evaluations, at most predict.md_chunk_frames frames / 64 MiB when R is recorded), reads the
+ *   status words and first_bad_step flags and stops when no geometry is active.  When B Hessians and work matrices exceed
+ *   gdml_vib_run's 256 MiB, every evaluation walks the geometries in slices (predict.vib_chunk).  No persistent kernel, no
+ *   graph, no waiting between workgroups.
+ * Arguments.  R (B,3N), trust, E_prev, dE_pred (B), flags (B, int64; bit 0 = a previous step exists, bit 1 = that step was
+ *   clipped), t (B,3N) or NULL (the follow vector, e.g. gdml_neb_run's tangent at i_climb; any length): the state, the start on
+ *   entry and the end on return.  A fresh start: trust = the first radius, E_prev = dE_pred = 0, flags = 0.  Passing the end
+ *   state back continues the run as if it had not been cut (max_steps is the budget of one call).
+ *   status (B,2), first_bad_step (B), n_made, record_every, R_rec: exactly as in gdml_relax_run.  E_hist, fmax_hist,
+ *   w_follow_hist (max_steps + 1, B): rows 0 .. n_made - 1 are written, E' UNSCALED; a frozen geometry repeats its last value.
+ *   k_follow_hist (max_steps + 1, B) int64 or NULL: the same for the followed index.  E_end (B), F_end (B,3N): E', F' UNSCALED
+ *   at R.  w_end (B,3N): the spectrum at R in gdml_vib_run's layout (vibrational entries ascending, then n_rigid zeros), with
+ *   n_rigid, n_neg (B).  mode_end (B,3N).  The caller checks n_neg == order; the search does not enforce it.
+ * Bit-identical: the same call repeated; n steps then a continuation against 2 n steps; any chunk length; any record_every;
+ *   steps 2-4 never depend on the batch or the slice, so neither do the results as far as gdml_predict_hessian_dev returns the
+ *   same bits for a geometry; w_end is gdml_vib_run's w2 at R with unit masses; E_end, F_end are gdml_predict_hessian_dev's.
+ * GDML_ERR_INVALID before any launch (ctx may be NULL for these checks): NULL params, max_steps < 0, record_every < 0 (< 1 with
+ *   R_rec), B < 0, N < 1, f_scale <= 0 or not finite, fmax <= 0 or not finite, order outside {0, 1}, trust_min <= 0,
+ *   trust_max < trust_min, project outside 0 .. 2, exactly one of lat / lat_inv, project = 2 with a lattice, a follow vector
+ *   with order = 0, a NULL state or output array (k_follow_hist, R_rec, t and first_bad_step may be NULL), a trust outside
+ *   [trust_min, trust_max], flags outside 0 .. 3, a non-finite E_prev or dE_pred where bit 0 is set, a non-finite coordinate or
+ *   follow vector entry; N different from the model's.  GDML_ERR_UNSUPPORTED for N > 197 (the Hessian's limit).  GDML_ERR_STATE
+ *   without a model. */
+typedef struct gdml_ef_params {
+  int64_t B;
+  int N;
+  int order;             /* 0 minimum, 1 first-order saddle */
+  double f_scale;        /* g = -f_scale * F', D = f_scale * H' */
+  const double* lat;
+  const double* lat_inv; /* both or neither */
+  double fmax;           /* converged when the largest |g_atom| is below it */
+  double trust_min, trust_max;
+  int project;           /* 0 none, 1 translations, 2 translations + rotations */
+} gdml_ef_params;        /* 72 bytes */
+int gdml_ef_run(gdml_ctx* ctx, const gdml_ef_params* params, double* R, double* trust, double* E_prev, double* dE_pred,
+                int64_t* flags, double* t /* or NULL */, int64_t max_steps, int64_t record_every, double* R_rec /* or NULL */,
+                double* E_hist, double* fmax_hist, double* w_follow_hist, int64_t* k_follow_hist /* or NULL */, double* E_end,
+                double* F_end, double* w_end, int64_t* n_rigid, int64_t* n_neg, double* mode_end, int64_t* status,
+                int64_t* first_bad_step);
 
 /* Posterior force covariance of the Gaussian process behind the model (active learning, leaving the training distribution):
  *   cov F(x*) = k(x*,x*) - K*^T (K + lam I)^-1 K*.  The reference has no counterpart (its solve runs on the host and drops the

@@ -53,6 +53,12 @@ class VibParams(C.Structure):
     _fields_ = [('B', C.c_int64), ('N', C.c_int), ('h_scale', C.c_double), ('lat', _vp), ('lat_inv', _vp), ('project', C.c_int)]
 
 
+class EfParams(C.Structure):
+    """gdml_ef_params (include/gdml_hip.h)."""
+    _fields_ = [('B', C.c_int64), ('N', C.c_int), ('order', C.c_int), ('f_scale', C.c_double), ('lat', _vp), ('lat_inv', _vp),
+                ('fmax', C.c_double), ('trust_min', C.c_double), ('trust_max', C.c_double), ('project', C.c_int)]
+
+
 # name -> (restype, argtypes).  Must list every symbol declared in include/gdml_hip.h.
 SIGNATURES = {
     'gdml_abi_version': (C.c_int, []),
@@ -98,6 +104,8 @@ SIGNATURES = {
     'gdml_sym_eig': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
     'gdml_sym_eig_dev': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
     'gdml_vib_run': (C.c_int, [_vp, C.POINTER(VibParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_ef_run': (C.c_int, [_vp, C.POINTER(EfParams), _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gdml_uncert_prepare': (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_int)]),
     'gdml_uncert_release': (C.c_int, [_vp]),
     'gdml_uncert_cross': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
@@ -849,6 +857,52 @@ class Context(object):
         out = dict(w2=w2, n_rigid=n_rigid, n_neg=n_neg, sweeps=sweeps, E=E, F=F)
         if modes:
             out['modes'] = md
+        return out
+
+    def ef_run(self, R, fmax, max_steps, state, order=1, trust_min=1e-4, trust_max=0.3, project=2, f_scale=1.0, record_every=0,
+               lat_and_inv=None):
+        """gdml_ef_run: B geometries (R: (B,3N)) follow the Hessian's eigenvectors to a minimum (order=0) or a first-order saddle
+        (order=1) on the device, at most max_steps steps each.  state: dict with 'trust', 'E_prev', 'dE_pred' (B), 'flags' (B,
+        int) and 't' ((B,3N) follow vector, or None).  Returns a dict: 'R_end', 'E_end' (B; unscaled E'), 'F_end' (B,3N;
+        unscaled), 'w_end' (B,3N), 'n_rigid', 'n_neg' (B), 'mode_end' (B,3N), the end 'state', 'status' (B,2; see the header),
+        'n_made', 'E_hist', 'fmax_hist', 'w_follow_hist', 'k_follow_hist' (n_made,B), the frames 'R' (only with record_every > 0)
+        and 'first_bad_step' (B; -1 = every value stayed finite)."""
+        n3 = 3 * self.model_n_atoms
+        R = np.array(R, dtype=np.float64).reshape(-1, n3)
+        B = R.shape[0]
+        trust, E_prev, dE_pred = (np.array(state[k], dtype=np.float64).ravel() for k in ('trust', 'E_prev', 'dE_pred'))
+        flags = np.array(state['flags'], dtype=np.int64).ravel()
+        for k, a in (('trust', trust), ('E_prev', E_prev), ('dE_pred', dE_pred), ('flags', flags)):
+            if a.shape != (B,):
+                raise ValueError("state['{}'] must have one entry per geometry ({}), got shape {}".format(k, B, a.shape))
+        t = state.get('t')
+        if t is not None:
+            t = np.array(t, dtype=np.float64)
+            if t.shape != R.shape:
+                raise ValueError("state['t'] must have the shape of R {}, got {}".format(R.shape, t.shape))
+        lat, lat_inv = _lat_pair(lat_and_inv)
+        max_steps, record_every = int(max_steps), int(record_every)
+        n_eval = max(max_steps, 0) + 1
+        R_rec = np.empty((max(max_steps, 0) // record_every + 1, B, n3)) if record_every > 0 else None
+        E_hist, f_hist, w_hist = np.empty((n_eval, B)), np.empty((n_eval, B)), np.empty((n_eval, B))
+        k_hist = np.zeros((n_eval, B), dtype=np.int64)
+        E_end, F_end, w_end, mode_end = np.empty(B), np.empty((B, n3)), np.empty((B, n3)), np.empty((B, n3))
+        n_rigid, n_neg = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+        status = np.full((B, 2), -1, dtype=np.int64)
+        bad = np.full(B, -1, dtype=np.int64)
+        prm = EfParams(B, self.model_n_atoms, int(order), float(f_scale), _ptr(lat), _ptr(lat_inv), float(fmax), float(trust_min),
+                       float(trust_max), int(project))
+        self._check(self._lib.gdml_ef_run(self._h, C.byref(prm), _ptr(R), _ptr(trust), _ptr(E_prev), _ptr(dE_pred), _ptr(flags),
+                                          _ptr(t), max_steps, record_every, _ptr(R_rec), _ptr(E_hist), _ptr(f_hist), _ptr(w_hist),
+                                          _ptr(k_hist), _ptr(E_end), _ptr(F_end), _ptr(w_end), _ptr(n_rigid), _ptr(n_neg),
+                                          _ptr(mode_end), _ptr(status), _ptr(bad)))
+        n_made = int(status[:, 1].max()) + 1 if B and (status[:, 1] >= 0).all() else 0
+        out = dict(R_end=R, E_end=E_end, F_end=F_end, w_end=w_end, n_rigid=n_rigid, n_neg=n_neg, mode_end=mode_end, status=status,
+                   first_bad_step=bad, n_made=n_made, E_hist=E_hist[:n_made], fmax_hist=f_hist[:n_made],
+                   w_follow_hist=w_hist[:n_made], k_follow_hist=k_hist[:n_made],
+                   state=dict(trust=trust, E_prev=E_prev, dE_pred=dE_pred, flags=flags, t=t))
+        if R_rec is not None:
+            out['R'] = R_rec[:(n_made + record_every - 1) // record_every]
         return out
 
     def uncert_prepare(self, sig, lam):

@@ -88,6 +88,8 @@ struct Model {
 //                     requests SLOT_PANEL_TRSM only.  gdml_factor_extend / gdml_factor_remove release both: they were sized for n
 //   SLOT_VIB_WS       gdml_sym_eig, gdml_sym_eig_dev and gdml_vib_run carve it anew and call none of the others; the Hessian call
 //                     inside gdml_vib_run holds the scratch buffer and SLOT_PREDICT_WS only
+//   SLOT_EF_WS        gdml_ef_run alone: its state lives there for the whole call, across the Hessian calls of every evaluation
+//                     (which hold the scratch buffer and SLOT_PREDICT_WS only)
 enum CtxSlot {
   SLOT_PREDICT_WS = 0,      // row-split partials of F_x and E (predict_device, predict_fused); workspace of hess_device
   SLOT_MATVEC_OUT = 1,      // forces and energies of this rank's query points (matvec_device)
@@ -105,6 +107,7 @@ enum CtxSlot {
   SLOT_GRAM_WS = 13,        // queries / coefficients, partial Gram tiles, staged output (gram_workspace)
   SLOT_GRAM_ROWS = 14,      // the (3N x chunk, padded to 128 rows) x K_ld row buffer (gram_workspace)
   SLOT_VIB_WS = 15,         // matrices, spectra and the eigensolver's work matrices of a chunk (gdml_sym_eig*, gdml_vib_run)
+  SLOT_EF_WS = 16,          // state, end-of-run outputs, histories and a slice's matrices of gdml_ef_run
   SLOT_COUNT
 };
 

@@ -559,6 +559,96 @@ class GDMLPredict(object):
         out['freq'] = np.sign(out['w2']) * np.sqrt(np.abs(out['w2']))
         return out
 
+    # ---- eigenvector following on the device (gdml_ef_run, csrc/vib.hip)
+
+    def stationary_point(self, R0, fmax, order=1, follow=None, max_steps=100, trust_start=0.1, trust_max=0.3, trust_min=1e-4,
+                         project=None, state=None, lattice=None, f_unit=1.0, record_every=0):
+        """Move B independent geometries to a stationary point of the energy on the device by eigenvector following: a minimum
+        (order=0) or a first-order saddle (order=1), e.g. the climbing image of neb() tightened to any fmax.  Every evaluation
+        takes the analytic Hessian of predict_hessian(), projects the rigid-body motion out as vibrations() does with unit
+        masses (project: 'rigid' without a lattice, 'trans' with one, 'none'), diagonalises it and steps in its eigenbasis by
+        the per-mode rational-function rule -- downhill along every mode, uphill along the followed one for order=1 -- inside
+        a trust radius (trust_start, halved or doubled between trust_min and trust_max by the ratio of actual to predicted
+        energy change; no step is rejected).  Gradient g = -f_unit * F with F the forces of predict(); Cartesian coordinates.
+        R0: (B,3N) or (3N,).  follow: None (the lowest mode is maximised) or a (B,3N) direction, e.g. neb()'s tangent at
+        i_climb: the mode of largest overlap is followed, and tracked from step to step.  A geometry is converged when its
+        largest atomic |g| is below fmax; each takes at most max_steps steps in this call and stops on its own.
+        state: the 'state' of an earlier call, passed back with its R_end, continues that run bit for bit.  lattice: as in
+        predict().  record_every > 0 also returns 'R'.
+        Returns a dict: 'R_end' (B,3N), 'E_end' (B) and 'F_end' (B,3N) scaled like predict(), 'fmax_end' (B), 'n_steps' (B),
+        'converged' (B, bool), 'w_end' (B,3N; the spectrum at R_end in vibrations()' layout), 'n_rigid', 'n_neg' (B; the caller
+        checks n_neg == order, the search does not enforce it), 'mode_end' (B,3N; the followed eigenvector, zeros for
+        order=0), 'E_hist', 'fmax_hist', 'w_follow_hist', 'k_follow_hist' (evaluations made, B) and 'state'.  Runs on the
+        predictor's first device.  ValueError for non-finite or out-of-range arguments before anything is launched;
+        FloatingPointError naming geometry and evaluation when a value stops being finite."""
+        n3 = 3 * self.n_atoms
+        R0 = _as_batch(R0, n3)
+        B = R0.shape[0]
+        if not np.isfinite(R0).all():
+            raise ValueError('R0 must be finite')
+        _check_finite(('fmax', fmax), ('trust_start', trust_start), ('trust_max', trust_max), ('trust_min', trust_min),
+                      ('f_unit', f_unit))
+        if not float(fmax) > 0.0:
+            raise ValueError('fmax must be positive')
+        if not float(f_unit) > 0.0:
+            raise ValueError('f_unit must be positive')
+        if order not in (0, 1):
+            raise ValueError('order must be 0 (minimum) or 1 (first-order saddle), got {!r}'.format(order))
+        if int(max_steps) != max_steps or int(record_every) != record_every or max_steps < 0 or record_every < 0:
+            raise ValueError('max_steps and record_every must be non-negative integers')
+        if not 0.0 < float(trust_min) <= float(trust_start) <= float(trust_max):
+            raise ValueError('need 0 < trust_min <= trust_start <= trust_max')
+        lat_and_inv = self._lat_and_inv(lattice)
+        if project is None:
+            project = 'rigid' if lat_and_inv is None else 'trans'
+        if project not in self._VIB_PROJECT:
+            raise ValueError("project must be None, 'none', 'trans' or 'rigid', got {!r}".format(project))
+        if project == 'rigid' and lat_and_inv is not None:
+            raise ValueError("project='rigid' with a lattice: rotations are no symmetry of a periodic cell (use 'trans')")
+        if follow is not None:
+            if order == 0:
+                raise ValueError('follow names the mode to maximise: it needs order=1')
+            follow = _as_batch(follow)
+            if follow.shape != R0.shape:
+                raise ValueError('follow must have the shape of R0 {}, got {}'.format(R0.shape, follow.shape))
+            if not np.isfinite(follow).all() or not (np.abs(follow).max(axis=1) > 0.0).all():
+                raise ValueError('follow must be finite and non-zero for every geometry')
+        if state is None:
+            state = dict(trust=np.full(B, float(trust_start)), E_prev=np.zeros(B), dE_pred=np.zeros(B),
+                         flags=np.zeros(B, dtype=np.int64), t=follow)
+        else:
+            missing = [k for k in ('trust', 'E_prev', 'dE_pred', 'flags', 't') if k not in state]
+            if missing:
+                raise ValueError('state lacks {}'.format(missing))
+            if follow is not None:
+                raise ValueError('follow starts a run; a continuation carries its own vector in state')
+            if state['t'] is not None and order == 0:
+                raise ValueError('state carries a follow vector: it needs order=1')
+            for k in ('trust', 'E_prev', 'dE_pred', 'flags'):
+                if np.shape(state[k]) != (B,):
+                    raise ValueError("state['{}'] must have one entry per geometry ({})".format(k, B))
+            if state['t'] is not None and np.shape(state['t']) != R0.shape:
+                raise ValueError("state['t'] must have the shape of R0 {}, got {}".format(R0.shape, np.shape(state['t'])))
+            tr = np.asarray(state['trust'], dtype=np.float64)
+            if not all(np.isfinite(np.asarray(state[k], dtype=np.float64)).all() for k in ('trust', 'E_prev', 'dE_pred')):
+                raise ValueError('state must be finite')
+            if not ((tr >= float(trust_min)) & (tr <= float(trust_max))).all():
+                raise ValueError("state['trust'] must lie in [trust_min, trust_max]")
+        out = self._ctx.ef_run(R0, fmax, max_steps, state, order=order, trust_min=trust_min, trust_max=trust_max,
+                               project=self._VIB_PROJECT[project], f_scale=self.std * float(f_unit),
+                               record_every=record_every, lat_and_inv=lat_and_inv)
+        _raise_first_bad(out.pop('first_bad_step'), 'geometry', 'evaluation')
+        status = out.pop('status')
+        out.pop('n_made')
+        out['F_end'] *= self.std
+        for k in ('E_end', 'E_hist'):
+            out[k] *= self.std
+            out[k] += self.c
+        out['n_steps'] = status[:, 1].copy()
+        out['converged'] = status[:, 0] == 1
+        out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
+        return out
+
     @staticmethod
     def harmonic_thermo(w2_vib, kT, hbar):
         """Quantum harmonic oscillators of squared frequencies w2_vib (the vibrational entries of vibrations()['w2'], any
