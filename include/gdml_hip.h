@@ -86,7 +86,10 @@ int gdml_phase_ms(gdml_ctx* ctx, const char* phase, double* ms_out, int64_t* lau
 /* Per-kernel timing for roofline reports: after gdml_profile(ctx, 1) every launch of the hot
  * kernels is bracketed by HIP events on the compute stream; gdml_kernel_stat returns the summed
  * launch duration, the launch count and the summed ALGORITHMIC work (flops for "gemm_nt_sub",
- * bytes for "assemble" and "predict") since profiling was enabled.  Off by default. */
+ * bytes for "assemble" and "predict") since profiling was enabled.  Off by default.
+ * "gemm_nt_sub_diag" covers every trailing-update launch that carries a diagonal block, the composed launches of
+ * chol.deep included.  "gemm_nt_sub_deep" is a COUNT only: launches that held far tiles and those tiles' flops, with
+ * ms = 0 (their time is part of "gemm_nt_sub_diag"): do not form a rate from it. */
 int gdml_profile(gdml_ctx* ctx, int enable);
 int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t* launches_out,
                      double* work_out);
@@ -136,6 +139,11 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *   chol.outer (1024)     panel pairs: K = 2 nb trailing update in two launches (= chol.nb, or chol.nb not a multiple of 128:
  *                         single panels only)
  *   chol.outer_min_rows (16384)  trailing rows below which new panels are single again
+ *   chol.deep (4096)      W > 0 (a multiple of chol.outer): columns in blocks of W; the trailing tiles right of the current block
+ *                         receive the block in ONE pass of depth W, which rides in the launches of the next block's outer steps
+ *                         (csrc/tile_sched.h: chol_plan_build).  Same factor bit for bit.  0: every outer step updates the
+ *                         whole trailing matrix
+ *   chol.deep_min_rows (26624)  trailing rows below which the deep schedule hands over to the one-level one
  *   gemm.balance (1)      lower (SYRK-shaped) trailing updates: tile list dealt evenly over the 8 XCDs, no empty workgroups
  *                         (csrc/tile_sched.h); 0: the 8 x 8 super-tile enumeration with 64 block slots per super tile.  Same factor bit for bit
  *   trsm.debug (0)        timing-only ablation mask of the row-local panel solve (results are wrong when set)

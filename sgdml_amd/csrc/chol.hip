@@ -20,9 +20,13 @@
 // The round-1 schedule (step chain on a second stream with one panel of look-ahead; profiles/r02_panel_fusion_ab.txt), the
 // CU-masked / split-stream / chunked variants of rounds 1-2 (profiles/r01_chol_timeline_split.txt, r02_sched_probe.txt) and the
 // two-level, persistent and narrow-tile forms of round 6 were measured slower and are gone.
+// While the trailing matrix is large (chol.deep, chol.deep_min_rows) the tiles right of the current block of 4096 columns do
+// not take part in every outer step: they receive the block in one pass of depth 4096 that rides, as further segments, in the
+// launches of the next block's outer steps (gemm_nt_sub_seg_kernel; the plan is chol_plan_build in tile_sched.h).
 #include "common.h"
 #include "tile_sched.h"
 #include <array>
+#include <memory>
 #include <type_traits>
 #include <utility>
 
@@ -402,8 +406,10 @@ struct TileSchedEntry {
   TileSched S;
   const uint32_t* dev[2] = {nullptr, nullptr};
 };
+struct CholPlanEntry;
 struct TileSchedCache {
   std::map<std::array<int64_t, 7>, TileSchedEntry> entries;
+  std::vector<std::pair<std::array<int64_t, 8>, std::shared_ptr<CholPlanEntry>>> plans;  // plans with composed launches
   char* block = nullptr;
   size_t cap = 0, used = 0;
 };
@@ -865,6 +871,70 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_sub_diag_kernel(GemmArgs g) {
     return;
   }
   gemm_block<false>(g, lds, (int64_t)blockIdx.x - 1);
+}
+
+// Composed launch of the deep schedule (tile_sched.h, chol.deep): up to three segments with their own A, B, C, M, N, K; a
+// workgroup reads its (segment, ti, tj) from its XCD's list -- ONE scalar load whose address depends on kernel arguments
+// only -- and runs the production tile body on it.  The host lists only tiles that exist (lower, inside M x N): nothing is
+// decided per tile but which body, as in gemm_block.  Workgroup 0 is the diagonal-block role of gemm_nt_sub_diag_kernel.
+struct SegArgs {
+  const double* A[3];
+  const double* B[3];
+  double* C[3];
+  int64_t M[3], N[3], K[3];
+  int64_t ld;
+  const uint32_t* table;  // [8][stride]
+  int stride;
+  uint64_t cnt[4];        // entries per XCD, 32 bits each
+  double* diagA;
+  int diag_nbw;
+  int64_t diag_off;
+  int* diag_info;
+  int* ready;
+  int ready_target;
+};
+
+__global__ void __launch_bounds__(256, 2) gemm_nt_sub_seg_kernel(SegArgs s) {
+  __shared__ __attribute__((aligned(16))) double lds[2][2][GT * GPITCH];
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) {
+      int spins = 0;
+      while (__hip_atomic_load(s.ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < s.ready_target) {
+        __builtin_amdgcn_s_sleep(8);
+        if (++spins > (1 << 24)) {
+          atomicExch(s.ready + 1, 1);
+          break;
+        }
+      }
+    }
+    __syncthreads();
+    __threadfence();
+    diag_block_role(s.diagA, s.ld, s.diag_nbw, s.diag_off, s.diag_info, &lds[0][0][0]);
+    return;
+  }
+  const int64_t b = (int64_t)blockIdx.x - 1;
+  const int x = (int)(b & 7);
+  const int64_t pos = b >> 3;
+  if (pos >= (int64_t)((s.cnt[x >> 1] >> (32 * (x & 1))) & 0xffffffffu)) return;
+  const uint32_t v = __builtin_amdgcn_readfirstlane(s.table[(int64_t)x * s.stride + pos]);
+  const int si = TS_SEG_ID(v);
+  GemmArgs h;
+  h.A = s.A[0]; h.B = s.B[0]; h.C = s.C[0]; h.M = s.M[0]; h.N = s.N[0]; h.K = s.K[0];
+  if (si == 1) { h.A = s.A[1]; h.B = s.B[1]; h.C = s.C[1]; h.M = s.M[1]; h.N = s.N[1]; h.K = s.K[1]; }
+  if (si == 2) { h.A = s.A[2]; h.B = s.B[2]; h.C = s.C[2]; h.M = s.M[2]; h.N = s.N[2]; h.K = s.K[2]; }
+  h.lda = h.ldb = h.ldc = s.ld;
+  const int64_t row0 = TS_SEG_TI(v) * GT, col0 = TS_SEG_TJ(v) * GT;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(h.A) | reinterpret_cast<uintptr_t>(h.B)) & 15) == 0 && (s.ld % 2 == 0);
+  const bool full = (row0 + GT <= h.M) && (col0 + GT <= h.N) && ((h.K & (GBK - 1)) == 0) && aligned;
+  if (full)
+    gemm_tile_body<true, false>(h, lds, row0, col0);
+  else
+    gemm_tile_body<false, false>(h, lds, row0, col0);
+  if (TS_SEG_COUNTED(v)) {  // publish the tile (release: every thread's stores, then one count)
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(s.ready, 1);
+  }
 }
 
 __global__ void __launch_bounds__(64) potrf64_kernel(double* __restrict__ A, int64_t ld, int w,
@@ -1349,6 +1419,97 @@ __global__ void __launch_bounds__(256) rank64_update_kernel(const double* __rest
         if (crow[i][r] < m && ccol[j] < ncols) C[(int64_t)crow[i][r] * ld + ccol[j]] = acc[i][j][r];
 }
 
+// ---- the factorisation's plan (tile_sched.h).  A plan with composed launches is cached per (n, rows, options) together with
+// its launch tables, which live in a device allocation of their own, sized from the plan (2.8 MB at n = 63 000, 36 MB at
+// 150 000); the few most recent ones are kept.  A plan without composed launches (every small factorisation) is a short list
+// of operations, built per call and not kept.
+struct CholPlanEntry {
+  CholPlan plan;
+  uint32_t* block = nullptr;         // device tables of all composed launches
+  std::vector<const uint32_t*> dev;  // per composed launch: [8][stride]
+  std::vector<int> stride;
+  ~CholPlanEntry() {
+    if (block) (void)hipFree(block);  // (waits for the device: nothing in flight reads the tables any more)
+  }
+};
+
+static int chol_plan_get(gdml_ctx* ctx, hipStream_t st, int64_t n, int64_t n_rows, CholPlanOpts po, std::shared_ptr<CholPlanEntry>* out) {
+  if (!ctx->tile_sched) ctx->tile_sched = new TileSchedCache();
+  TileSchedCache* c = ctx->tile_sched;
+  const std::array<int64_t, 8> key = {n, n_rows, po.NB, po.OB, po.outer_min_rows, po.fused_min_rows, po.deep, po.deep_min_rows};
+  for (auto& kv : c->plans)
+    if (kv.first == key) { *out = kv.second; return GDML_OK; }
+  auto e = std::make_shared<CholPlanEntry>();
+  chol_plan_build(n, n_rows, po, &e->plan);
+  *out = e;
+  if (e->plan.segs.empty()) return GDML_OK;
+  std::vector<uint32_t> host;
+  std::vector<size_t> at;
+  for (const PlanSegLaunch& L : e->plan.segs) {
+    const size_t stride = plan_launch_stride(L);
+    at.push_back(host.size());
+    e->stride.push_back((int)stride);
+    host.resize(host.size() + plan_launch_words(L), 0);
+    for (int x = 0; x < 8; ++x) std::copy(L.xcd[x].begin(), L.xcd[x].end(), host.begin() + at.back() + x * stride);
+  }
+  if (hipMalloc((void**)&e->block, host.size() * 4) != hipSuccess) {
+    // no room for the tables beside the matrix: the one-level schedule needs none and computes the same factor
+    (void)hipGetLastError();
+    e->block = nullptr;
+    po.deep = 0;
+    e->plan = CholPlan();
+    e->stride.clear();
+    chol_plan_build(n, n_rows, po, &e->plan);
+    return GDML_OK;
+  }
+  HIP_CHECK(ctx, hipMemcpyAsync(e->block, host.data(), host.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_CHECK(ctx, hipStreamSynchronize(st));  // once per plan: the host copy goes out of scope
+  for (size_t o : at) e->dev.push_back(e->block + o);
+  if (c->plans.size() >= 4) c->plans.erase(c->plans.begin());  // oldest first
+  c->plans.emplace_back(key, e);
+  return GDML_OK;
+}
+
+static int launch_gemm_seg(gdml_ctx* ctx, hipStream_t st, double* A, int64_t ld, const CholPlanEntry& pe, int idx, int ready_target) {
+  const PlanSegLaunch& L = pe.plan.segs[idx];
+  SegArgs s = {};
+  for (int i = 0; i < 3; ++i) {
+    const PlanSeg& g = L.seg[i];
+    s.A[i] = A + g.origin * ld + g.a_col0;
+    s.B[i] = s.A[i];
+    s.C[i] = A + g.origin * ld + g.origin;
+    s.M[i] = g.M; s.N[i] = g.N; s.K[i] = g.K;
+  }
+  s.ld = ld;
+  s.table = pe.dev[idx];
+  s.stride = pe.stride[idx];
+  int64_t mx = 0;
+  for (int x = 0; x < 8; ++x) {
+    const int64_t cnt = (int64_t)L.xcd[x].size();
+    s.cnt[x >> 1] |= (uint64_t)cnt << (32 * (x & 1));
+    if (cnt > mx) mx = cnt;
+  }
+  s.diagA = A + L.diag0 * ld + L.diag0;
+  s.diag_nbw = L.diag_nbw;
+  s.diag_off = L.diag0;
+  s.diag_info = ctx->d_info;
+  s.ready = ctx->d_info + 6;
+  s.ready_target = ready_target;
+  const int slot = (st == (ctx->kt_stream ? ctx->kt_stream : ctx->stream)) ? ktime_begin(ctx) : -1;
+  hipLaunchKernelGGL(gemm_nt_sub_seg_kernel, dim3((unsigned)(8 * mx + 1)), dim3(256), 0, st, s);
+  // the composed launches are trailing-update launches like the paired ones: timed under the same name, flops counted from
+  // the tiles they hold; the far tiles' share is kept under a name of its own (launches and flops, no time)
+  ktime_end(ctx, slot, "gemm_nt_sub_diag", L.flops);
+  if (slot >= 0 && L.far_tiles > 0) {
+    KernelStat& k = ctx->kstats["gemm_nt_sub_deep"];
+    k.launches += 1;
+    k.work += L.far_flops;
+  }
+  ctx->launch_counter++;
+  HIP_CHECK(ctx, hipGetLastError());
+  return GDML_OK;
+}
+
 // Factor one panel: columns [k0, k0+nb), rows [k0, n), 64-wide sub-steps (potrf_trsm64 / rank-64 update).
 int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int64_t ld, int64_t k0, int64_t nb);
 
@@ -1443,67 +1604,78 @@ int chol_factor_device(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int* inf
   // The diagonal-block workgroup counts finished GT x GT tiles of its block, so pairs need NB % GT == 0 (a block of a
   // ragged NB would be factored before its last update arrived): other NB run single panels.  Once the bulk gets too
   // short (n - t1 < chol.outer_min_rows) new panels are single NB-wide ones again.
-  int64_t OB = (int64_t)ctx_opt(ctx, "chol.outer", 1024);
-  if (OB != 2 * NB || NB % GT != 0) OB = NB;
   const int64_t outer_min_rows = (int64_t)ctx_opt(ctx, "chol.outer_min_rows", 16384);
-  auto width_at = [&](int64_t c0) -> int64_t {  // width of the panel that starts at column c0
-    const int64_t left = n - (c0 + OB);  // trailing matrix behind the pair
-    const int64_t w = (OB > NB && left > 0 && left >= outer_min_rows) ? OB : NB;
-    return (n - c0 < w) ? n - c0 : w;
-  };
-  // first panel: nothing to hide its diagonal block behind
-  int64_t k0 = 0, nb = (n < NB) ? n : NB;
+  // The schedule itself is a pure host function (chol_plan_build, tile_sched.h: tested without a GPU); this loop runs its
+  // operations.  chol.deep = W > 0: far trailing tiles receive a whole block of W columns in one pass that rides in the
+  // launches of the next block's outer steps (OP_SEG); 0: the one-level schedule.
+  CholPlanOpts po;
+  po.NB = NB; po.OB = (int64_t)ctx_opt(ctx, "chol.outer", 1024); po.outer_min_rows = outer_min_rows; po.fused_min_rows = min_rows;
+  po.deep = (int64_t)ctx_opt(ctx, "chol.deep", 4096);
+  po.deep_min_rows = (int64_t)ctx_opt(ctx, "chol.deep_min_rows", 26624);
+  std::shared_ptr<CholPlanEntry> pe;
+  GDML_TRY(chol_plan_get(ctx, st, n, n_rows, po, &pe));
   int ready_count = 0;  // cumulative target of the tile counter d_info[6]
   HIP_CHECK(ctx, hipMemsetAsync(ctx->d_info + 6, 0, 2 * sizeof(int), ctx->stream));  // counter, wait-timeout flag
-  GDML_TRY(panel_factor(ctx, st, A, n_rows, ld, 0, nb));
-  for (;;) {
-    const int64_t t0 = k0 + nb;
-    if (t0 >= n) break;
-    const int64_t nb2 = width_at(t0);
-    const int64_t t1 = t0 + nb2;
+  const int block_tiles = (int)((NB / GT) * (NB / GT + 1) / 2);  // lower GT x GT tiles of a diagonal block
+  for (const CholOp& c : pe->plan.ops) {
+    const int64_t k0 = c.k0, nb = c.nb, t0 = c.t0, nb2 = c.nb2, t1 = t0 + nb2;
     const double* P = A + t0 * ld + k0;
-    const bool fuse = (nb2 % 64 == 0) && (n - t1 >= min_rows) && (n_rows - t1 > 0);
-    if (fuse && nb2 == 2 * NB) {
-      // The first super-tile column of the SYRK is exactly the columns of a | b (2 NB = 8 tiles): it is enumerated first,
-      // workgroup 0 of the first launch waits for the 10 tiles of block a (counter) and factors it while the rest runs.
-      const int64_t ta = t0 + NB;  // first row / column of b
-      const int64_t sm = (ceil_div(n_rows - t0, GT) + 7) / 8, n_super_all = sm * (sm + 1) / 2;
-      int64_t s_split = n_super_all / 2;
-      if (s_split < sm) s_split = sm;
-      const double fs = ((double)s_split + 0.5) / (double)n_super_all;
-      DiagJob dj;
-      dj.A = A + t0 * ld + t0; dj.nbw = (int)(NB / 64); dj.off = t0;
-      dj.col0_first = true;
-      dj.ready = ctx->d_info + 6;
-      const int block_tiles = (int)((NB / GT) * (NB / GT + 1) / 2);  // lower GT x GT tiles of a diagonal block
-      ready_count += block_tiles;
-      dj.ready_target = ready_count;
-      dj.next_M2 = n_rows - ta; dj.next_N2 = NB; dj.next_K2 = NB;
-      GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, 0.0, fs, true,
-                                       &dj));
-      double* Xa = A + ta * ld + t0;  // rows below block a (they include b's rows of the outer panel)
-      GDML_TRY(launch_panel_trsm(ctx, st, A + t0 * ld + t0, Xa, ld, (int)NB, n_rows - ta));
-      // second launch: the K = NB update of b's columns by panel a rides in front of the remaining SYRK tiles; workgroup 0
-      // waits for the tiles of block b and factors it
-      dj.A = A + ta * ld + ta; dj.off = ta;
-      dj.A2 = Xa; dj.B2 = Xa; dj.C2 = A + ta * ld + ta; dj.M2 = n_rows - ta; dj.N2 = NB; dj.K2 = NB;
-      ready_count += block_tiles;
-      dj.ready_target = ready_count;
-      GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, fs, 1.0, true,
-                                       &dj));
-      GDML_TRY(launch_panel_trsm(ctx, st, A + ta * ld + ta, A + t1 * ld + ta, ld, (int)NB, n_rows - t1));
-    } else {
-      GDML_TRY(launch_gemm_nt_sub(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, nb2, nb, 0));
-      const double* P1 = A + t1 * ld + k0;
-      if (fuse) {
+    const double* P1 = A + t1 * ld + k0;
+    switch (c.kind) {
+      case OP_PANEL:  // first panel (nothing to hide its diagonal block behind) and the last one
+        GDML_TRY(panel_factor(ctx, st, A, n_rows, ld, t0, nb2));
+        break;
+      case OP_TRSM:
+        GDML_TRY(launch_panel_trsm(ctx, st, A + t0 * ld + t0, A + t1 * ld + t0, ld, (int)nb2, n_rows - t1));
+        break;
+      case OP_PAIR1:
+      case OP_PAIR2: {
+        // The first super-tile column of the SYRK is exactly the columns of a | b (2 NB = 8 tiles): it is enumerated first,
+        // workgroup 0 of the first launch waits for the 10 tiles of block a (counter) and factors it while the rest runs.
+        // Second launch: the K = NB update of b's columns by panel a rides in front of the remaining SYRK tiles; workgroup 0
+        // waits for the tiles of block b and factors it.
+        const int64_t ta = t0 + NB;  // first row / column of b
+        const int64_t sm = (ceil_div(n_rows - t0, GT) + 7) / 8, n_super_all = sm * (sm + 1) / 2;
+        int64_t s_split = n_super_all / 2;
+        if (s_split < sm) s_split = sm;
+        const double fs = ((double)s_split + 0.5) / (double)n_super_all;
+        DiagJob dj;
+        dj.nbw = (int)(NB / 64);
+        dj.col0_first = true;
+        dj.ready = ctx->d_info + 6;
+        ready_count += block_tiles;
+        dj.ready_target = ready_count;
+        dj.next_M2 = n_rows - ta; dj.next_N2 = NB; dj.next_K2 = NB;
+        if (c.kind == OP_PAIR1) {
+          dj.A = A + t0 * ld + t0; dj.off = t0;
+          GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, 0.0, fs, true,
+                                           &dj));
+        } else {
+          double* Xa = A + ta * ld + t0;  // rows below block a (they include b's rows of the outer panel)
+          dj.A = A + ta * ld + ta; dj.off = ta;
+          dj.A2 = Xa; dj.B2 = Xa; dj.C2 = A + ta * ld + ta; dj.M2 = n_rows - ta; dj.N2 = NB; dj.K2 = NB;
+          GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, fs, 1.0, true,
+                                           &dj));
+        }
+        break;
+      }
+      case OP_SEG:
+        ready_count += block_tiles;
+        GDML_TRY(launch_gemm_seg(ctx, st, A, ld, *pe, c.seg, ready_count));
+        break;
+      case OP_RECT:
+        GDML_TRY(launch_gemm_nt_sub(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, nb2, nb, 0));
+        break;
+      case OP_FUSED: {
         DiagJob dj;
         dj.A = A + t0 * ld + t0;
         dj.nbw = (int)(nb2 / 64);
         dj.off = t0;
         GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P1, ld, P1, ld, A + t1 * ld + t1, ld, n_rows - t1, n - t1, nb, 1, 0.0,
                                          1.0, true, &dj));
-        GDML_TRY(launch_panel_trsm(ctx, st, A + t0 * ld + t0, A + t1 * ld + t0, ld, (int)nb2, n_rows - t1));
-      } else if (t1 < n) {
+        break;
+      }
+      case OP_TAIL: {
         // tail: the SYRK is too short to hide the single-workgroup block factorisation; the multi-workgroup step chain and
         // the row-local solve of panel k+1 run on the high-priority stream next to the (small) SYRK grid of panel k
         hipStream_t sp = ctx->stream2;
@@ -1513,12 +1685,9 @@ int chol_factor_device(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int* inf
         HIP_CHECK(ctx, hipEventRecord(ctx->ev_la[1], sp));
         GDML_TRY(launch_gemm_nt_sub(ctx, st, P1, ld, P1, ld, A + t1 * ld + t1, ld, n_rows - t1, n - t1, nb, 1));
         HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_la[1], 0));
-      } else {
-        GDML_TRY(panel_factor(ctx, st, A, n_rows, ld, t0, nb2));
+        break;
       }
     }
-    k0 = t0;
-    nb = nb2;
   }
   HIP_CHECK(ctx, hipGetLastError());
   int info8[8] = {0};

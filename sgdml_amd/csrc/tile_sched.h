@@ -298,3 +298,346 @@ inline double tile_sched_flops(const TileSched& S, int l, int64_t M, int64_t K, 
   for (int i = 0; i < l; ++i) before += tile_sched_counted_flops(S, i, M, K, tiles_m, gt);
   return (double)M * (double)(M + 1) * (double)K - before;
 }
+
+// ---- the factorisation's launch plan (host only) and the composed launches of the deep schedule (chol.deep) ------
+// chol_plan_build restates the schedule of chol_factor_device as a list of operations; chol_factor_device runs that
+// list.  With chol.deep = 0 the list is the one-level schedule: panel pairs, fused single panels, tail.  With chol.deep = W
+// the columns form blocks [0, NB + W), [NB + W, NB + 2 W), ...  Inside block b the K = 2 NB update of an outer step covers
+// only the tile columns of block b (near band); the tiles right of it receive the whole block in ONE pass of depth W (far
+// pass) that has no launch of its own: its tiles ride in the launches of block b + 1's outer steps, as further SEGMENTS
+// of those launches (own A, B, C, M, N, K).  A launch is then a per-XCD table of (segment, ti, tj) entries; a full 8 x 8 super
+// tile stays whole on one XCD, single tiles are dealt in contiguous runs so that the XCDs carry the same cost.  The last
+// tile row, when it is ragged, takes the guarded tile body, which rounds C - (A B^T) instead of accumulating into -C: it
+// stays in the near band of every step, so that the factor is bit for bit the one-level factor.
+// The deep regime ends at the first outer step whose trailing matrix is shorter than chol.deep_min_rows (or whose successor
+// is no panel pair any more): that step's two launches carry whatever is pending, then the one-level schedule goes on.
+#define TS_SEG_TI(v) ((int64_t)((v) & 0x3fffu))
+#define TS_SEG_TJ(v) ((int64_t)(((v) >> 14) & 0x3fffu))
+#define TS_SEG_ID(v) ((int)(((v) >> 28) & 7u))
+#define TS_SEG_COUNTED(v) ((v) >> 31)
+
+struct CholPlanOpts {
+  int64_t NB = 512, OB = 1024, outer_min_rows = 16384, fused_min_rows = 12288, deep = 0, deep_min_rows = 26624;
+};
+struct PlanSeg {      // C[origin:, origin:] -= A[origin:, a_col0 : a_col0 + K] (same rows of the matrix)^T, M x N
+  int64_t origin = 0, a_col0 = 0, M = 0, N = 0, K = 0;
+  int kind = 0;       // 0 near band, 1 far pass, 2 second problem (columns of panel b updated by panel a)
+};
+struct PlanSegLaunch {
+  PlanSeg seg[3];
+  std::vector<uint32_t> xcd[8];  // ti | tj << 14 | segment << 28 | counted << 31, tile indices relative to the segment's origin
+  int64_t diag0 = 0;             // first row of the diagonal block workgroup 0 factors
+  int diag_nbw = 0, counted = 0;
+  int64_t tiles = 0, far_tiles = 0;
+  double flops = 0.0, far_flops = 0.0, cost = 0.0;
+};
+enum { OP_PANEL = 0, OP_RECT, OP_PAIR1, OP_PAIR2, OP_FUSED, OP_TRSM, OP_TAIL, OP_SEG };
+struct CholOp {
+  int kind = 0;
+  int64_t k0 = 0, nb = 0;   // finished panel: columns [k0, k0 + nb)
+  int64_t t0 = 0, nb2 = 0;  // next panel (OP_TRSM: the diagonal block and its width)
+  int seg = -1;             // OP_SEG: index into CholPlan::segs
+};
+struct CholPlan {
+  std::vector<CholOp> ops;
+  std::vector<PlanSegLaunch> segs;
+  int64_t NB = 0, OB = 0, deep = 0, deep_end = 0;  // deep_end: first column of the step that leaves the deep regime (0: never entered)
+};
+
+namespace cp_detail {
+const int GT_ = 128;
+const int64_t TURNOVER = 66;  // tile turnover in units of k: 0.885 of the peak at K = 1024 and 0.927 at K = 4096
+// one tile (v = ti | tj << 14) or one full 8 x 8 super tile (v = its first tile): no storage of its own
+struct Unit {
+  uint32_t v = 0;
+  int64_t K = 0;
+  uint8_t seg = 0, kind = 0;
+  bool full = false, ragged = false, first = false;
+  int tiles() const { return full ? 64 : 1; }
+  int64_t cost() const { return (int64_t)tiles() * (K + TURNOVER); }
+  uint32_t tile(int i) const { return full ? v + (uint32_t)(i >> 3) + ((uint32_t)(i & 7) << 14) : v; }
+};
+// the lower tiles of an M x N problem that pred accepts, super row by super row; 64 accepted tiles of one super tile form
+// one unit, everything else (and every super tile that reaches into a ragged last tile row) single tiles
+// (only super columns [tj_lo / 8, ceil(tj_hi / 8)) are visited, and the last super row over all its columns when last_row is
+// set: pred still decides, the range only spares the visit of super tiles it would reject anyway)
+template <class Pred>
+inline void gen_units(int seg, const PlanSeg& s, Pred pred, bool first, std::vector<Unit>* out, int tj_lo = 0, int tj_hi = 1 << 30,
+                      bool last_row = false) {
+  const int tiles_m = (int)((s.M + GT_ - 1) / GT_), tiles_n = (int)((s.N + GT_ - 1) / GT_);
+  const bool ragged = (s.M % GT_) != 0 || (s.N % GT_) != 0;
+  const int sm = (tiles_m + 7) / 8;
+  Unit u;
+  u.seg = (uint8_t)seg; u.kind = (uint8_t)s.kind; u.K = s.K; u.first = first;
+  const int sj_lo = tj_lo / 8, sj_hi = tj_hi > (1 << 29) ? (1 << 29) : (tj_hi + 7) / 8;
+  for (int SI = 0; SI < sm; ++SI)
+    for (int SJ = 0; SJ <= SI; ++SJ) {
+      if ((SJ < sj_lo || SJ >= sj_hi) && !(last_row && SI == sm - 1)) continue;
+      uint32_t got[64];
+      int ng = 0;
+      for (int r = 0; r < 8; ++r)
+        for (int c = 0; c < 8; ++c) {
+          const int ti = SI * 8 + r, tj = SJ * 8 + c;
+          if (ti < tiles_m && tj < tiles_n && tj <= ti && pred(ti, tj)) got[ng++] = (uint32_t)ti | ((uint32_t)tj << 14);
+        }
+      if (ng == 64 && !(ragged && SI * 8 + 7 == tiles_m - 1)) {
+        u.full = true; u.ragged = false; u.v = got[0];
+        out->push_back(u);
+        continue;
+      }
+      for (int i = 0; i < ng; ++i) {
+        u.full = false; u.v = got[i];
+        u.ragged = ragged && (int)TS_SEG_TI(got[i]) == tiles_m - 1;
+        out->push_back(u);
+      }
+    }
+}
+inline int64_t units_cost(const std::vector<Unit>& v, size_t from = 0) {
+  int64_t c = 0;
+  for (size_t i = from; i < v.size(); ++i) c += v[i].cost();
+  return c;
+}
+// Classes in the order of an XCD's list: 0 first-column tiles (the counted ones lead), 1 far pass, 2 ragged last row (guarded
+// body, not at the very end), 3 near full super tiles, 4 the rest.  Long tiles ahead of short ones: the launch ends on
+// short tiles (with the far tiles behind the near ones 12 of the 15 ms the schedule gains are lost, profiles/chol_deep.txt).
+inline void deal_launch(const std::vector<Unit>& units, int counted_seg, int counted_rows, PlanSegLaunch* L) {
+  std::vector<Unit> cls[5];
+  for (const Unit& u : units) cls[u.first ? 0 : (u.kind == 1 ? 1 : (u.ragged ? 2 : (u.full ? 3 : 4)))].push_back(u);
+  int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  auto put = [&](int x, const Unit& u) {
+    const PlanSeg& s = L->seg[u.seg];
+    for (int i = 0; i < u.tiles(); ++i) {
+      const uint32_t v = u.tile(i);
+      const int64_t ti = TS_SEG_TI(v), tj = TS_SEG_TJ(v);
+      const bool cnt = u.seg == counted_seg && ti < counted_rows && tj < counted_rows;
+      L->xcd[x].push_back(v | ((uint32_t)u.seg << 28) | (cnt ? 0x80000000u : 0u));
+      const double r = (double)(s.M - ti * GT_ < GT_ ? s.M - ti * GT_ : GT_), c = (double)(s.N - tj * GT_ < GT_ ? s.N - tj * GT_ : GT_);
+      const double fl = (double)s.K * ((ti == tj && s.kind != 2) ? r * (r + 1.0) : 2.0 * r * c);
+      L->flops += fl; ++L->tiles;
+      if (s.kind == 1) { L->far_flops += fl; ++L->far_tiles; }
+    }
+    load[x] += u.cost();
+  };
+  std::vector<Unit> fulls, singles;
+  for (int c = 0; c < 5; ++c) {
+    // full super tiles in rounds of eight, one per XCD (least loaded first); the < 8 that fill no round become single
+    // tiles, and the single tiles are dealt in contiguous runs that even out what the XCDs carry so far
+    fulls.clear(); singles.clear();
+    size_t n_full = 0, nf = 0;
+    for (const Unit& u : cls[c]) n_full += u.full ? 1 : 0;
+    const size_t keep = n_full - n_full % 8;
+    for (const Unit& u : cls[c]) {
+      if (u.full && nf++ < keep) { fulls.push_back(u); continue; }
+      Unit w = u;
+      w.full = false;
+      for (int i = 0; i < u.tiles(); ++i) { w.v = u.tile(i); singles.push_back(w); }
+    }
+    auto deal_full = [&]() {
+      for (const Unit& u : fulls) {
+        int best = 0;
+        for (int x = 1; x < 8; ++x) if (load[x] < load[best]) best = x;
+        put(best, u);
+      }
+    };
+    if (c != 0) deal_full();
+    int64_t tot = 0;
+    for (const Unit& u : singles) tot += u.cost();
+    for (int x = 0; x < 8; ++x) tot += load[x];
+    const double mean = (double)tot / 8.0;
+    size_t i = 0;
+    for (int x = 0; x < 8; ++x) {
+      double want = mean - (double)load[x];
+      while (i < singles.size() && (x == 7 || want >= 0.5 * (double)singles[i].cost())) {
+        want -= (double)singles[i].cost();
+        put(x, singles[i++]);
+      }
+    }
+    if (c == 0) deal_full();
+  }
+  int64_t mx = 0;
+  for (int x = 0; x < 8; ++x) if (load[x] > mx) mx = load[x];
+  L->cost = (double)mx;
+}
+}  // namespace cp_detail
+
+// 32-bit words of a composed launch's device table: [8][stride], stride = the longest XCD list, padded to 64 words
+inline size_t plan_launch_stride(const PlanSegLaunch& L) {
+  size_t mx = 0;
+  for (int x = 0; x < 8; ++x) mx = L.xcd[x].size() > mx ? L.xcd[x].size() : mx;
+  return mx;
+}
+inline size_t plan_launch_words(const PlanSegLaunch& L) { return (8 * plan_launch_stride(L) + 63) & ~(size_t)63; }
+
+inline void chol_plan_build(int64_t n, int64_t n_rows, CholPlanOpts o, CholPlan* P) {
+  using namespace cp_detail;
+  *P = CholPlan();
+  if (n_rows < n) n_rows = n;
+  int64_t NB = o.NB;
+  if (NB < 64 || NB % 64 || NB > 512) NB = 512;
+  int64_t min_rows = o.fused_min_rows < 1 ? 1 : o.fused_min_rows;
+  int64_t OB = o.OB;
+  if (OB != 2 * NB || NB % GT_ != 0) OB = NB;
+  P->NB = NB; P->OB = OB;
+  auto width_at = [&](int64_t c0) -> int64_t {
+    const int64_t left = n - (c0 + OB);
+    const int64_t w = (OB > NB && left > 0 && left >= o.outer_min_rows) ? OB : NB;
+    return (n - c0 < w) ? n - c0 : w;
+  };
+  auto fuse_at = [&](int64_t t0) {
+    const int64_t nb2 = width_at(t0), t1 = t0 + nb2;
+    return (nb2 % 64 == 0) && (n - t1 >= min_rows) && (n_rows - t1 > 0);
+  };
+  auto paired = [&](int64_t t0) { return t0 < n && OB == 2 * NB && width_at(t0) == 2 * NB && fuse_at(t0); };
+  // deep regime: outer steps t0 = NB, NB + OB, ... < X are composed, the step at X carries what is pending and leaves
+  int64_t W = (OB == 2 * NB) ? o.deep : 0;
+  if (W > 0) W -= W % OB;
+  int64_t X = NB;
+  if (W >= OB && n_rows / GT_ < 0x3ff0) {
+    while (paired(X) && paired(X + OB) && n - X >= o.deep_min_rows) X += OB;
+  }
+  const bool has_deep = X > NB;
+  P->deep = has_deep ? W : 0;
+  P->deep_end = has_deep ? X : 0;
+  const int OBt = (int)(OB / GT_), NBt = (int)(NB / GT_);
+  const int block_tiles = NBt * (NBt + 1) / 2;
+  auto op = [&](int kind, int64_t k0, int64_t nb, int64_t t0, int64_t nb2, int seg = -1) {
+    CholOp c;
+    c.kind = kind; c.k0 = k0; c.nb = nb; c.t0 = t0; c.nb2 = nb2; c.seg = seg;
+    P->ops.push_back(c);
+  };
+  // ---- state of the deep regime
+  int64_t S = 0, E = NB + W;        // current block
+  PlanSeg pool_seg;                 // the pending pass
+  std::vector<Unit> pool;           // its tiles not yet dealt, in order
+  size_t pool_at = 0;
+  int64_t span_cost = 0;
+  int span_left = 0;
+  auto near_seg = [&](int64_t t0, int64_t k0, int64_t nb) {
+    PlanSeg s;
+    s.origin = t0; s.a_col0 = k0; s.M = n_rows - t0; s.N = n - t0; s.K = nb; s.kind = 0;
+    return s;
+  };
+  auto second_seg = [&](int64_t t0) {
+    PlanSeg s;
+    s.origin = t0 + NB; s.a_col0 = t0; s.M = n_rows - (t0 + NB); s.N = NB; s.K = NB; s.kind = 2;
+    return s;
+  };
+  auto near_bound = [&](int64_t t0, int64_t blockS, int64_t blockE) -> int { return (t0 == blockS && blockS > 0) ? 0 : (int)((blockE - t0) / GT_); };
+  auto near_pred = [&](const PlanSeg& s, int bound) {
+    const int tiles_m = (int)((s.M + GT_ - 1) / GT_);
+    const bool ragged = (s.M % GT_) != 0 || (s.N % GT_) != 0;
+    return [=](int ti, int tj) { return tj < bound || (ragged && ti == tiles_m - 1); };
+  };
+  auto far_pred = [&](const PlanSeg& s) {
+    const int tiles_m = (int)((s.M + GT_ - 1) / GT_);
+    const bool ragged = (s.M % GT_) != 0 || (s.N % GT_) != 0;
+    return [=](int ti, int tj) { return !(ragged && ti == tiles_m - 1); };
+  };
+  auto step_fixed_cost = [&](int64_t t0, int64_t nb, int64_t blockS, int64_t blockE) {
+    std::vector<Unit> u;
+    const PlanSeg s = near_seg(t0, t0 - nb, nb), s2 = second_seg(t0);
+    const int bound = near_bound(t0, blockS, blockE);
+    gen_units(0, s, near_pred(s, bound), false, &u, 0, bound, true);
+    gen_units(2, s2, [](int, int) { return true; }, true, &u, 0, NBt);
+    return units_cost(u);
+  };
+
+  int64_t k0 = 0, nb = (n < NB) ? n : NB;
+  op(OP_PANEL, 0, 0, 0, nb);
+  for (;;) {
+    const int64_t t0 = k0 + nb;
+    if (t0 >= n) break;
+    const int64_t nb2 = width_at(t0), t1 = t0 + nb2;
+    const bool fuse = fuse_at(t0);
+    if (fuse && nb2 == 2 * NB && has_deep && t0 <= X) {
+      const int64_t ta = t0 + NB;
+      int must = 0;  // tile columns of the pending pass that the first launch must hold
+      if (t0 == E) {  // block boundary: block [S, E) becomes the pending far pass, its tiles ride in the next block's steps
+        pool_seg = PlanSeg();
+        pool_seg.origin = E; pool_seg.a_col0 = S; pool_seg.M = n_rows - E; pool_seg.N = n - E; pool_seg.K = E - S; pool_seg.kind = 1;
+        S = E; E = S + W;
+        int m = 0;
+        int64_t fixed = 0;
+        for (int64_t t = t0; t < E && (t < X || t == t0); t += OB) { ++m; fixed += step_fixed_cost(t, t == t0 ? nb : OB, S, E); }
+        must = (m > 1) ? (int)(W / GT_) : OBt;
+        pool.clear(); pool_at = 0;
+        const auto fp = far_pred(pool_seg);
+        gen_units(1, pool_seg, [&](int ti, int tj) { return fp(ti, tj) && tj < OBt; }, true, &pool, 0, OBt);
+        gen_units(1, pool_seg, [&](int ti, int tj) { return fp(ti, tj) && tj >= OBt && tj < must; }, false, &pool, OBt, must);
+        gen_units(1, pool_seg, [&](int ti, int tj) { return fp(ti, tj) && tj >= must; }, false, &pool, must);
+        span_cost = fixed + units_cost(pool);
+        span_left = 2 * m;
+      } else if (t0 == X) {  // leaving inside block [S, E): the block's finished panels [S, X) go to the tiles right of E now
+        pool.clear(); pool_at = 0;
+        pool_seg = PlanSeg();
+        if (E < n) {
+          pool_seg.origin = E; pool_seg.a_col0 = S; pool_seg.M = n_rows - E; pool_seg.N = n - E; pool_seg.K = X - S; pool_seg.kind = 1;
+          gen_units(1, pool_seg, far_pred(pool_seg), false, &pool);
+        }
+        span_cost = step_fixed_cost(t0, nb, S, E) + units_cost(pool);
+        span_left = 2;
+      } else if (span_left == 0) {
+        span_cost = step_fixed_cost(t0, nb, S, E);
+        span_left = 2;
+      }
+      const PlanSeg ns = near_seg(t0, k0, nb);
+      const int bound = near_bound(t0, S, E);
+      const auto np_ = near_pred(ns, bound);
+      std::vector<Unit> rest;  // near tiles right of the first columns: either launch of the step
+      size_t rest_at = 0;
+      for (int l = 0; l < 2; ++l) {
+        PlanSegLaunch L;
+        L.seg[0] = ns;
+        L.seg[1] = pool_seg;
+        if (l == 1) L.seg[2] = second_seg(t0);
+        std::vector<Unit> u;
+        if (l == 0) {
+          gen_units(0, ns, [&](int ti, int tj) { return np_(ti, tj) && tj < OBt; }, true, &u, 0, OBt);
+          while (pool_at < pool.size() && must > 0 && (int)TS_SEG_TJ(pool[pool_at].v) < must) u.push_back(pool[pool_at++]);
+          rest.clear(); rest_at = 0;
+          gen_units(0, ns, [&](int ti, int tj) { return np_(ti, tj) && tj >= OBt; }, false, &rest, OBt, bound, true);
+        } else {
+          gen_units(2, L.seg[2], [](int, int) { return true; }, true, &u, 0, NBt);
+        }
+        int64_t cost = units_cost(u);
+        const int64_t target = span_cost / span_left;
+        if (l == 0) {
+          while (rest_at < rest.size() && cost + rest[rest_at].cost() / 2 <= target) { cost += rest[rest_at].cost(); u.push_back(rest[rest_at++]); }
+        } else {
+          while (rest_at < rest.size()) { cost += rest[rest_at].cost(); u.push_back(rest[rest_at++]); }
+        }
+        while (pool_at < pool.size() && (span_left == 1 || cost + pool[pool_at].cost() / 2 <= target)) {
+          cost += pool[pool_at].cost();
+          u.push_back(pool[pool_at++]);
+        }
+        span_cost -= cost;
+        --span_left;
+        L.diag0 = (l == 0) ? t0 : ta;
+        L.diag_nbw = (int)(NB / 64);
+        L.counted = block_tiles;
+        const bool counted_in_pool = (l == 0) && bound == 0;  // at a block boundary the diagonal block's tiles are far tiles
+        deal_launch(u, l == 1 ? 2 : (counted_in_pool ? 1 : 0), NBt, &L);
+        P->segs.push_back(std::move(L));
+        op(OP_SEG, k0, nb, t0, nb2, (int)P->segs.size() - 1);
+        op(OP_TRSM, 0, 0, l == 0 ? t0 : ta, NB);
+      }
+    } else if (fuse && nb2 == 2 * NB) {
+      op(OP_PAIR1, k0, nb, t0, nb2);
+      op(OP_TRSM, 0, 0, t0, NB);
+      op(OP_PAIR2, k0, nb, t0, nb2);
+      op(OP_TRSM, 0, 0, t0 + NB, NB);
+    } else {
+      op(OP_RECT, k0, nb, t0, nb2);
+      if (fuse) {
+        op(OP_FUSED, k0, nb, t0, nb2);
+        op(OP_TRSM, 0, 0, t0, nb2);
+      } else if (t1 < n) {
+        op(OP_TAIL, k0, nb, t0, nb2);
+      } else {
+        op(OP_PANEL, 0, 0, t0, nb2);
+      }
+    }
+    k0 = t0;
+    nb = nb2;
+  }
+}

@@ -7,8 +7,17 @@ tile_decode_super (csrc/tile_sched.h): block b runs on XCD b % 8 (round-robin de
 dispatch"), an XCD has 64 workgroup slots, a launch ends when its most loaded XCD ends.  Per launch: tiles, rounds
 (tiles / 512), the most loaded XCD's excess over the mean in rounds, and the time that excess would cost at the tile time of
 the launch's depth (225 us at K = 1024).  With two rocprofv3 kernel-trace CSVs (one factorisation or more per file; the last
-one is taken) the measured duration of each launch under gemm.balance = 0 and 1 is printed beside the prediction."""
+one is taken) the measured duration of each launch under gemm.balance = 0 and 1 is printed beside the prediction.
+
+  python tools/xcd_balance_model.py --deep DRIVER [n] [n_rows] [W] [deep_min_rows] [trace.csv]
+
+models the COMPOSED launches of the deep schedule (chol.deep = W), whose near tiles (K = 1024 / 512) and far tiles (K = W) differ
+in length: DRIVER is tests/chol_plan_driver.cpp compiled with the host compiler; it prints the plan chol_factor_device runs.
+A tile costs K + 66 in units of k (66 = tile turnover, fitted to 0.885 of the peak at K = 1024 and 0.927 at K = 4096); this is
+the cost chol_plan_build sizes the launches' shares and deals the XCDs by.  Per launch: tiles, far tiles, the most and least
+loaded XCD, the predicted time (most loaded XCD / 64 slots) and, with a kernel-trace CSV, the measured duration and rate."""
 import csv
+import subprocess
 import sys
 
 GT, TILE_US_K1024 = 128, 225.0
@@ -107,8 +116,45 @@ def last_factorisation(rows, seq):
     return out
 
 
+def deep_main(args):
+    exe = args[0]
+    n = int(args[1]) if len(args) > 1 else 63000
+    n_rows = int(args[2]) if len(args) > 2 else n + 1
+    W = int(args[3]) if len(args) > 3 else 4096
+    deep_min = int(args[4]) if len(args) > 4 else 26624
+    out = subprocess.run([exe] + [str(v) for v in (n, n_rows, 512, 1024, 16384, 12288, W, deep_min)], capture_output=True, text=True,
+                         check=True).stdout
+    S = []
+    for ln in out.split('\n'):
+        f = ln.split()
+        if f and f[0] == 'S':
+            S.append({f[i]: float(f[i + 1]) for i in range(1, len(f), 2)})
+    meas = []
+    if len(args) > 5:
+        with open(args[5]) as f:
+            rows = sorted((int(r['Start_Timestamp']), (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) * 1e-6)
+                          for r in csv.DictReader(f) if 'gemm_nt_sub_seg_kernel' in r['Kernel_Name'])
+        meas = [d for _, d in rows][-len(S):]
+    us_per_k = TILE_US_K1024 / (1024 + 66)
+    print('# n = %d, rows = %d, chol.deep = %d, chol.deep_min_rows = %d: %d composed launches' % (n, n_rows, W, deep_min, len(S)))
+    print('# %3s %7s %7s %9s %9s %8s %8s' % ('i', 'tiles', 'far', 'xcd_max', 'xcd_min', 'TFLOP', 'pred_ms') + (' %8s %7s' % ('meas_ms', 'TF/s') if meas else ''))
+    tp = tm = tf = 0.0
+    for i, s in enumerate(S):
+        pred = s['xcd_cost_max'] / 64.0 * us_per_k * 1e-3
+        line = '  %3d %7d %7d %9d %9d %8.4f %8.2f' % (i, s['tiles'], s['far'], s['xcd_cost_max'], s['xcd_cost_min'], s['flops'] * 1e-12, pred)
+        tp += pred
+        tf += s['flops']
+        if meas:
+            line += ' %8.2f %7.2f' % (meas[i], s['flops'] / meas[i] * 1e-9)
+            tm += meas[i]
+        print(line)
+    print('# predicted %.1f ms' % tp + ('; measured %.1f ms, %.2f TFLOP/s over the composed launches' % (tm, tf / tm * 1e-9) if meas else ''))
+
+
 def main():
     args = sys.argv[1:]
+    if args and args[0] == '--deep':
+        return deep_main(args[1:])
     n = int(args[0]) if args else 63000
     n_rows = int(args[1]) if len(args) > 1 else n + 1
     seq = launches(n, n_rows)
