@@ -22,7 +22,13 @@
 // two-level, persistent and narrow-tile forms of round 6 were measured slower and are gone.
 // While the trailing matrix is large (chol.deep, chol.deep_min_rows) the tiles right of the current block of 4096 columns do
 // not take part in every outer step: they receive the block in one pass of depth 4096 that rides, as further segments, in the
-// launches of the next block's outer steps (gemm_nt_sub_seg_kernel; the plan is chol_plan_build in tile_sched.h).
+// launches of the next block's outer steps (gemm_nt_sub_seg_kernel).
+//
+// Host side, one path: plan -> launch description -> launcher.  chol_plan_build (tile_sched.h, host only: the CPU tests walk
+// what runs) clamps the options and lists the operations, every fused launch with its full description (PlanLowerLaunch
+// one-level, PlanSegLaunch composed) and the tile counter's target; launch_gemm_lower / launch_gemm_seg turn a description
+// into kernel arguments; chol_factor_device runs the list, one call per operation.  The public launch_gemm_nt_sub / _neg /
+// _cyclic share launch_gemm_plain.  The triangular solves and the C entries are in chol_solve.hip.
 #include "common.h"
 #include "tile_sched.h"
 #include <array>
@@ -379,26 +385,6 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_neg_kernel(GemmArgs g) {
   gemm_block<true>(g, lds, blockIdx.x);
 }
 
-// f0, f1: the launch covers the super tiles [f0 * n_super, f1 * n_super) (whole update: 0, 1);
-// timed: bracket with the per-kernel timers (only launches on the timing stream)
-struct DiagJob {
-  double* A = nullptr;  // top-left of the next panel's diagonal block
-  int nbw = 0;
-  int64_t off = 0;
-  // merged launch: the block's own tiles are part of this launch (GemmArgs::col0_first); they count into *ready
-  int* ready = nullptr;
-  int ready_target = 0;
-  bool col0_first = false;
-  // second problem of the launch (GemmArgs::A2 ...)
-  const double* A2 = nullptr;
-  const double* B2 = nullptr;
-  double* C2 = nullptr;
-  int64_t M2 = 0, N2 = 0, K2 = 0;
-  // first launch of a list cut in two: the second problem that the list's last launch will carry (its blocks are other
-  // work on their XCDs when the tile list is dealt)
-  int64_t next_M2 = 0, next_N2 = 0, next_K2 = 0;
-};
-
 // ---- balanced tile lists (tile_sched.h), cached per context --------------------------------------------------------
 // One entry per (tiles_m, tiles_n, first-column-first, launches, second problem): built on first use, its tables uploaded
 // once into one device block; a sigma sweep or repeated training at one size builds nothing and copies nothing.
@@ -421,26 +407,17 @@ void tile_sched_cache_free(gdml_ctx* ctx) {
   ctx->tile_sched = nullptr;
 }
 
-static int second_blocks(int64_t M2, int64_t N2, bool* compact) {
-  const int64_t tm2 = ceil_div(M2, GT), tn2 = ceil_div(N2, GT);
-  *compact = tm2 >= tn2;
-  return (int)(tm2 * tn2 - (*compact ? tn2 * (tn2 - 1) / 2 : 0));
-}
-
+// the balanced list of a lower launch (tile_sched.h: plan_lower_key names it, plan_lower_sched builds it);
 // *out = null: no balanced form for this shape (the caller keeps the super-tile enumeration)
-static int tile_sched_get(gdml_ctx* ctx, hipStream_t st, int tiles_m, int tiles_n, bool col0_first, int n_launch, int lead2,
-                          int64_t K2, int64_t K, const TileSchedEntry** out) {
+static int tile_sched_get(gdml_ctx* ctx, hipStream_t st, const PlanLowerLaunch& L, const TileSchedEntry** out) {
   *out = nullptr;
   if (!ctx->tile_sched) ctx->tile_sched = new TileSchedCache();
   TileSchedCache* c = ctx->tile_sched;
-  const std::array<int64_t, 7> key = {tiles_m, tiles_n, col0_first ? 1 : 0, n_launch, lead2, lead2 ? K2 : 0, lead2 ? K : 0};
+  const std::array<int64_t, 7> key = plan_lower_key(L);
   auto it = c->entries.find(key);
   if (it == c->entries.end()) {
     TileSchedEntry e;
-    // the second problem's block q sits lead2 - q blocks in front of the list's block 0: XCD label (q - lead2) mod 8
-    double base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int q = 0; q < lead2; ++q) base[((q - lead2) % 8 + 8) % 8] += (double)K2 / (double)K;
-    tile_sched_build(tiles_m, tiles_n, col0_first, n_launch, base, &e.S);
+    plan_lower_sched(L, &e.S);
     if (e.S.ok) {
       const size_t b0 = (e.S.table[0].size() * 4 + 255) & ~(size_t)255, b1 = (e.S.table[1].size() * 4 + 255) & ~(size_t)255;
       const size_t block_bytes = (size_t)8 << 20;
@@ -471,103 +448,105 @@ static int tile_sched_get(gdml_ctx* ctx, hipStream_t st, int tiles_m, int tiles_
   return GDML_OK;
 }
 
-static int launch_gemm_nt_sub_part(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda,
-                                   const double* B, int64_t ldb, double* C, int64_t ldc, int64_t M,
-                                   int64_t N, int64_t K, int lower, double f0, double f1, bool timed,
-                                   const DiagJob* diag = nullptr, const CyclicLower* cyc = nullptr, bool overwrite = false) {
-  if (M <= 0 || N <= 0 || K <= 0) return GDML_OK;
-  GemmArgs g;
-  g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.lower = lower;
-  g.diagA = nullptr; g.diag_nbw = 0; g.diag_off = 0; g.diag_info = nullptr;
-  g.cyc_W = 0; g.cyc_rank = 0; g.cyc_lb0 = 0; g.cyc_nb = 0; g.cyc_col0 = 0; g.cyc_block_rows = 0;
-  g.col0_first = (diag && diag->col0_first) ? 1 : 0;
-  g.ready = nullptr; g.ready_target = 0; g.ready_rows = 0;
-  g.A2 = g.B2 = nullptr; g.C2 = nullptr; g.M2 = g.N2 = g.K2 = 0; g.tiles2 = 0; g.second_compact = 0;
-  g.bal = 0; g.tl = TileLaunch();
-  if (cyc) { g.cyc_W = cyc->W; g.cyc_rank = cyc->rank; g.cyc_lb0 = cyc->lb0; g.cyc_nb = cyc->nb; g.cyc_col0 = cyc->col0; g.cyc_block_rows = cyc->block_rows; }
-  g.aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 &&
-              (lda % 2 == 0) && (ldb % 2 == 0);
-  g.tiles_m = (int)((M + GT - 1) / GT);
-  g.tiles_n = (int)((N + GT - 1) / GT);
-  int64_t sm = (g.tiles_m + 7) / 8, sn = (g.tiles_n + 7) / 8;
+// ---- host side of the GEMM launches: launch_gemm_plain (the public wrappers) and launch_gemm_lower (the plan's fused
+// launches).  A lower update takes its tiles from the balanced list of its description where gemm.balance (default 1)
+// allows and the shape has one, from the super-tile enumeration otherwise.
+// the shape part of the kernel argument; the tile range is the whole super-tile enumeration
+static GemmArgs gemm_args(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, int64_t M, int64_t N,
+                          int64_t K, int lower) {
+  GemmArgs g = {};
+  g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.lower = lower;
+  g.aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && (lda % 2 == 0) && (ldb % 2 == 0);
+  g.tiles_m = (int)((M + GT - 1) / GT); g.tiles_n = (int)((N + GT - 1) / GT);
+  const int64_t sm = (g.tiles_m + 7) / 8, sn = (g.tiles_n + 7) / 8;
   g.super_n = (int)sn;
-  const int64_t n_super_all = lower ? sm * (sm + 1) / 2 : sm * sn;
-  g.s_begin = (int64_t)(f0 * (double)n_super_all);
-  g.n_super = (f1 >= 1.0) ? n_super_all : (int64_t)(f1 * (double)n_super_all);
-  const bool has_diag = diag && diag->A;
-  const bool second = has_diag && diag->A2 && diag->M2 > 0;
-  // lower, non-cyclic launches: the balanced tile list (gemm.balance, default 1); (f0, f1) then only say which launch
-  // of the list this is -- (0, 1) the only one, (0, f) the first of two, (f, 1) the second
-  const TileSchedEntry* te = nullptr;
-  const int tl_i = f0 > 0.0 ? 1 : 0;
-  if (lower && !cyc && !overwrite && ctx_opt(ctx, "gemm.balance", 1) != 0) {
-    const int64_t M2s = second ? diag->M2 : (diag ? diag->next_M2 : 0), N2s = second ? diag->N2 : (diag ? diag->next_N2 : 0);
-    const int64_t K2s = second ? diag->K2 : (diag ? diag->next_K2 : 0);
-    bool compact = false;
-    const int lead2 = (M2s > 0 && N2s > 0) ? second_blocks(M2s, N2s, &compact) : 0;
-    GDML_TRY(tile_sched_get(ctx, st, g.tiles_m, g.tiles_n, g.col0_first != 0, (f0 > 0.0 || f1 < 1.0) ? 2 : 1, compact ? lead2 : 0,
-                            K2s, K, &te));
-  }
-  int64_t blocks;
-  if (te) {
-    g.bal = 1;
-    g.tl = te->S.L[tl_i];
-    g.tl.table = te->dev[tl_i];
-    g.s_begin = g.n_super = 0;
-    blocks = te->S.blocks[tl_i];
-    if (blocks == 0 && !has_diag) return GDML_OK;
-  } else {
-    if (g.n_super <= g.s_begin) {
-      if (!has_diag) return GDML_OK;
-      g.n_super = g.s_begin;  // empty tile range: the launch still carries the diagonal-block workgroup
-    }
-    const int64_t groups = (g.n_super - g.s_begin + 7) / 8;  // each group of 8 super tiles = 8 XCDs x 64 blocks
-    blocks = groups * 512;
-  }
-  const int slot = (timed && st == (ctx->kt_stream ? ctx->kt_stream : ctx->stream)) ? ktime_begin(ctx) : -1;
-  if (has_diag) {
-    g.diagA = diag->A; g.diag_nbw = diag->nbw; g.diag_off = diag->off; g.diag_info = ctx->d_info;
-    if (diag->ready) { g.ready = diag->ready; g.ready_target = diag->ready_target; g.ready_rows = diag->nbw * 64 / GT; }
-    if (second) {
-      g.A2 = diag->A2; g.B2 = diag->B2; g.C2 = diag->C2; g.M2 = diag->M2; g.N2 = diag->N2; g.K2 = diag->K2;
-      g.tiles2 = (int)(ceil_div(g.M2, GT) * ceil_div(g.N2, GT));
-      if (te) {  // no empty workgroups in front of a balanced list either
-        bool compact = false;
-        const int lead2 = second_blocks(g.M2, g.N2, &compact);
-        if (compact) { g.tiles2 = lead2; g.second_compact = 1; }
-      }
-    }
-    hipLaunchKernelGGL(gemm_nt_sub_diag_kernel, dim3((unsigned)(blocks + 1 + g.tiles2)), dim3(256), 0, st, g);
-  } else if (overwrite)
-    hipLaunchKernelGGL(gemm_nt_neg_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g);
-  else
-    hipLaunchKernelGGL(gemm_nt_sub_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g);
-  const double part = (double)(g.n_super - g.s_begin) / (double)n_super_all;  // share of the tile list in this launch
-  // algorithmic flops: a balanced list counts the tiles the launch really holds, the super-tile enumeration its share of the list
-  const double flops = te ? tile_sched_flops(te->S, tl_i, M, K, g.tiles_m, GT)
-                          : part * (lower ? (double)M * (double)(M + 1) * (double)K : 2.0 * (double)M * (double)N * (double)K);
-  // the fused launches (trailing update + diagonal-block workgroup) are the dominant kernel: timed under their own name
-  ktime_end(ctx, slot, has_diag ? "gemm_nt_sub_diag" : "gemm_nt_sub", flops + 2.0 * (double)g.M2 * (double)g.N2 * (double)g.K2);
+  g.n_super = lower ? sm * (sm + 1) / 2 : sm * sn;
+  return g;
+}
+
+// launch `launch` of the balanced list te takes the place of the super-tile range; returns its grid
+static int64_t gemm_use_list(GemmArgs* g, const TileSchedEntry* te, int launch) {
+  g->bal = 1;
+  g->tl = te->S.L[launch];
+  g->tl.table = te->dev[launch];
+  g->s_begin = g->n_super = 0;
+  return te->S.blocks[launch];
+}
+
+// grid workgroups of kern under the per-kernel timer `name` (only launches on the timing stream are timed)
+static int gemm_issue(gdml_ctx* ctx, hipStream_t st, void (*kern)(GemmArgs), int64_t grid, const GemmArgs& g, const char* name,
+                      double flops) {
+  const int slot = (st == (ctx->kt_stream ? ctx->kt_stream : ctx->stream)) ? ktime_begin(ctx) : -1;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, st, g);
+  ktime_end(ctx, slot, name, flops);
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
   return GDML_OK;
 }
 
-int launch_gemm_nt_sub(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda,
-                              const double* B, int64_t ldb, double* C, int64_t ldc, int64_t M,
-                              int64_t N, int64_t K, int lower) {
-  return launch_gemm_nt_sub_part(ctx, st, A, lda, B, ldb, C, ldc, M, N, K, lower, 0.0, 1.0, true);
+// cyc: block-row-cyclic lower structure (GemmArgs::cyc_W ...); overwrite: C = -A B^T, C not read
+static int launch_gemm_plain(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb, double* C,
+                             int64_t ldc, int64_t M, int64_t N, int64_t K, int lower, const CyclicLower* cyc, bool overwrite) {
+  if (M <= 0 || N <= 0 || K <= 0) return GDML_OK;
+  GemmArgs g = gemm_args(A, lda, B, ldb, C, ldc, M, N, K, lower);
+  if (cyc) { g.cyc_W = cyc->W; g.cyc_rank = cyc->rank; g.cyc_lb0 = cyc->lb0; g.cyc_nb = cyc->nb; g.cyc_col0 = cyc->col0; g.cyc_block_rows = cyc->block_rows; }
+  const TileSchedEntry* te = nullptr;
+  if (lower && !cyc && !overwrite && ctx_opt(ctx, "gemm.balance", 1) != 0) GDML_TRY(tile_sched_get(ctx, st, plan_lower_plain(M, N, K), &te));
+  const int64_t blocks = te ? gemm_use_list(&g, te, 0) : (g.n_super + 7) / 8 * 512;  // each group of 8 super tiles = 8 XCDs x 64 blocks
+  if (blocks == 0) return GDML_OK;
+  const double flops = lower ? (double)M * (double)(M + 1) * (double)K : 2.0 * (double)M * (double)N * (double)K;  // algorithmic
+  return gemm_issue(ctx, st, overwrite ? gemm_nt_neg_kernel : gemm_nt_sub_kernel, blocks, g, "gemm_nt_sub", flops);
+}
+
+// Fused launch of the factorisation: the lower update L.upd of the matrix A (leading dimension ld; one launch of its tile
+// list), in front of it the second problem where this launch carries it, and as workgroup 0 the diagonal block at L.diag0,
+// which waits for ready_target counted tiles where L.counted says that they are part of this launch.
+static int launch_gemm_lower(gdml_ctx* ctx, hipStream_t st, double* A, int64_t ld, const PlanLowerLaunch& L, int ready_target) {
+  const PlanSeg &u = L.upd, &s2 = L.second;
+  if (u.M <= 0 || u.N <= 0 || u.K <= 0) return GDML_OK;  // (the plan asks for none: chol.fused_min_rows is clamped there)
+  const double* P = A + u.origin * ld + u.a_col0;
+  GemmArgs g = gemm_args(P, ld, P, ld, A + u.origin * ld + u.origin, ld, u.M, u.N, u.K, 1);
+  g.col0_first = L.col0_first;
+  g.diagA = A + L.diag0 * ld + L.diag0; g.diag_nbw = L.diag_nbw; g.diag_off = L.diag0; g.diag_info = ctx->d_info;
+  if (L.counted) { g.ready = ctx->d_info + 6; g.ready_target = ready_target; g.ready_rows = L.diag_nbw * 64 / GT; }
+  const int64_t n_super_all = g.n_super;
+  plan_lower_range(L, &g.s_begin, &g.n_super);
+  const double part = (double)(g.n_super - g.s_begin) / (double)n_super_all;  // share of the super-tile list in this launch
+  const TileSchedEntry* te = nullptr;
+  if (ctx_opt(ctx, "gemm.balance", 1) != 0) GDML_TRY(tile_sched_get(ctx, st, L, &te));
+  const int64_t blocks = te ? gemm_use_list(&g, te, L.launch) : (g.n_super - g.s_begin + 7) / 8 * 512;
+  if (L.carries_second && s2.M > 0) {
+    g.A2 = g.B2 = A + s2.origin * ld + s2.a_col0; g.C2 = A + s2.origin * ld + s2.origin;
+    g.M2 = s2.M; g.N2 = s2.N; g.K2 = s2.K;
+    bool compact = false;
+    const int lead2 = plan_second_blocks(s2.M, s2.N, &compact);
+    g.tiles2 = (int)(ceil_div(s2.M, GT) * ceil_div(s2.N, GT));
+    if (te && compact) { g.tiles2 = lead2; g.second_compact = 1; }  // no empty workgroups in front of a balanced list either
+  }
+  // algorithmic flops: a balanced list counts the tiles the launch holds, the super-tile enumeration its share of the list,
+  // a launch whose range is the whole list M (M + 1) K either way.  (Of two launches that is the first one where the update
+  // has at most 8 tile rows; the second then reports the list's rest once more, 2 K flops too many where a carried row
+  // stands alone in the last tile row.  Kept as it was: tests/test_chol_launch_stats_gpu.py holds the recorded counts.)
+  const double flops = (te && part < 1.0) ? tile_sched_flops(te->S, L.launch, u.M, u.K, g.tiles_m, GT)
+                                          : part * ((double)u.M * (double)(u.M + 1) * (double)u.K);
+  // the fused launches (trailing update + diagonal-block workgroup) are the dominant kernel: timed under their own name
+  return gemm_issue(ctx, st, gemm_nt_sub_diag_kernel, blocks + 1 + g.tiles2, g, "gemm_nt_sub_diag",
+                    flops + 2.0 * (double)g.M2 * (double)g.N2 * (double)g.K2);
+}
+
+int launch_gemm_nt_sub(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb, double* C,
+                       int64_t ldc, int64_t M, int64_t N, int64_t K, int lower) {
+  return launch_gemm_plain(ctx, st, A, lda, B, ldb, C, ldc, M, N, K, lower, nullptr, false);
 }
 
 int launch_gemm_nt_neg(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb,
                        double* C, int64_t ldc, int64_t M, int64_t N, int64_t K) {  // C = -A B^T, C not read
-  return launch_gemm_nt_sub_part(ctx, st, A, lda, B, ldb, C, ldc, M, N, K, 0, 0.0, 1.0, true, nullptr, nullptr, true);
+  return launch_gemm_plain(ctx, st, A, lda, B, ldb, C, ldc, M, N, K, 0, nullptr, true);
 }
 
 int launch_gemm_nt_sub_cyclic(gdml_ctx* ctx, hipStream_t st, const double* A, int64_t lda, const double* B, int64_t ldb,
                               double* C, int64_t ldc, int64_t M, int64_t N, int64_t K, const CyclicLower& cyc) {
-  return launch_gemm_nt_sub_part(ctx, st, A, lda, B, ldb, C, ldc, M, N, K, 0, 0.0, 1.0, true, nullptr, &cyc);
+  return launch_gemm_plain(ctx, st, A, lda, B, ldb, C, ldc, M, N, K, 0, &cyc, false);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -848,25 +827,33 @@ __device__ __forceinline__ void diag_block_role(double* __restrict__ D, int64_t 
 }
 
 
+// Workgroup 0 of a fused launch waits until `target` tiles of its diagonal block have counted themselves into *ready (they
+// are computed by workgroups of the same launch, dispatched right behind this one).  Bounded: a target that can never be
+// reached must not hang the GPU (flag ready[1] -> GDML_ERR_HIP).  MAYBE_NONE: ready may be null (the block is complete
+// before the launch: nothing to wait for).
+template <bool MAYBE_NONE>
+__device__ __forceinline__ void wait_for_tiles(int* ready, int target) {
+  if (MAYBE_NONE && !ready) return;
+  if (threadIdx.x == 0) {
+    int spins = 0;
+    while (__hip_atomic_load(ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+      __builtin_amdgcn_s_sleep(8);
+      if (++spins > (1 << 24)) {
+        atomicExch(ready + 1, 1);
+        break;
+      }
+    }
+  }
+  __syncthreads();
+  __threadfence();
+}
+
 // Trailing update + (workgroup 0) the next panel's diagonal block.
 __global__ void __launch_bounds__(256, 2) gemm_nt_sub_diag_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) double lds[2][2][GT * GPITCH];
   static_assert(sizeof(double) * 2 * 2 * GT * GPITCH >= sizeof(double) * (2 * 64 * 65 + 64 + 128), "LDS of the diagonal role");
   if (blockIdx.x == 0) {
-    if (g.ready) {  // the block's tiles are computed by workgroups of this launch (dispatched right behind this one)
-      if (threadIdx.x == 0) {
-        int spins = 0;  // bounded: a target that can never be reached must not hang the GPU (flag -> GDML_ERR_HIP)
-        while (__hip_atomic_load(g.ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < g.ready_target) {
-          __builtin_amdgcn_s_sleep(8);
-          if (++spins > (1 << 24)) {
-            atomicExch(g.ready + 1, 1);
-            break;
-          }
-        }
-      }
-      __syncthreads();
-      __threadfence();
-    }
+    wait_for_tiles<true>(g.ready, g.ready_target);
     diag_block_role(g.diagA, g.ldc, g.diag_nbw, g.diag_off, g.diag_info, &lds[0][0][0]);
     return;
   }
@@ -897,18 +884,7 @@ struct SegArgs {
 __global__ void __launch_bounds__(256, 2) gemm_nt_sub_seg_kernel(SegArgs s) {
   __shared__ __attribute__((aligned(16))) double lds[2][2][GT * GPITCH];
   if (blockIdx.x == 0) {
-    if (threadIdx.x == 0) {
-      int spins = 0;
-      while (__hip_atomic_load(s.ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < s.ready_target) {
-        __builtin_amdgcn_s_sleep(8);
-        if (++spins > (1 << 24)) {
-          atomicExch(s.ready + 1, 1);
-          break;
-        }
-      }
-    }
-    __syncthreads();
-    __threadfence();
+    wait_for_tiles<false>(s.ready, s.ready_target);
     diag_block_role(s.diagA, s.ld, s.diag_nbw, s.diag_off, s.diag_info, &lds[0][0][0]);
     return;
   }
@@ -1333,18 +1309,6 @@ int launch_panel_trsm(gdml_ctx* ctx, hipStream_t st, const double* L, double* X,
   return GDML_OK;
 }
 
-// A <- -A + lam I on the lower triangle (analytic.py:65,82), tiled copy-free.
-__global__ void __launch_bounds__(256) negate_shift_kernel(double* __restrict__ A, int64_t n,
-                                                           int64_t ld, double lam) {
-  const int64_t r = blockIdx.x;
-  double* row = A + r * ld;
-  for (int64_t c = threadIdx.x; c <= r; c += 256) {
-    double v = -row[c];
-    if (c == r) v += lam;
-    row[c] = v;
-  }
-}
-
 int launch_trsm64(gdml_ctx* ctx, hipStream_t st, const double* Ld, double* X, int64_t ld, int w,
                   int64_t m, int64_t ldl) {
   if (m <= 0) return GDML_OK;
@@ -1583,40 +1547,21 @@ int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int6
 int chol_factor_device(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int* info_out, int64_t n_rows) {
   if (n_rows < n) n_rows = n;
   HIP_CHECK(ctx, hipMemsetAsync(ctx->d_info, 0, sizeof(int), ctx->stream));
-  int64_t NB = (int64_t)ctx_opt(ctx, "chol.nb", 512);  // outer panel width (multiple of 64)
-  if (NB < 64 || NB % 64 || NB > 512) NB = 512;  // the diagonal-block role and the row-local solve hold at most 8 x 64 columns
-  // ONE stream.  Per panel k:  GEMM1 (columns of panel k+1)  ->  SYRK of the rest, whose workgroup 0 factors the diagonal
-  // block of panel k+1 meanwhile  ->  row-local solve of panel k+1's rows.  The 64-wide step chain of the diagonal block is
-  // hidden inside the SYRK launch; only the row-local solve (one launch) stays between two GEMM launches.  Near the end (SYRK
-  // shorter than the single-workgroup block factorisation) the block is factored by the multi-workgroup step chain instead.
+  // ONE stream; the per-panel flow is in the file header.  The schedule is a pure host function (chol_plan_build,
+  // tile_sched.h: panel pairs while the trailing matrix is large, then single fused panels, then the tail; chol.deep = W > 0:
+  // far trailing tiles receive a whole block of W columns in one pass that rides in the next block's launches, OP_SEG).  It
+  // clamps the options and states every fused launch in full: this loop only turns origins into pointers.
   hipStream_t st = ctx->stream;
-  int64_t min_rows = (int64_t)ctx_opt(ctx, "chol.fused_min_rows", 12288);
-  // a fused launch needs a trailing matrix to ride in: with 0 the last panel of a matrix with a carried right-hand-side
-  // row (n - t1 = 0, n_rows - t1 = 1) asked for a fused launch with an empty update, which launch_gemm_nt_sub_part skips
-  // together with its diagonal-block workgroup -- the block was never factored
-  if (min_rows < 1) min_rows = 1;
-  // Panel PAIRS: while the trailing matrix is large, two NB-wide panels a | b form an outer panel of OB = 2 NB columns
-  // and the bulk of the trailing update runs with K = OB, which halves the C read-modify-write traffic per flop of the
-  // SYRK (its epilogue is ~6 % of the launch at K = 512).  ONE lower SYRK covers everything right of the finished panel, in
-  // two launches of its super-tile list, so that each of the two NB x NB diagonal blocks has a long launch to hide behind:
-  //   bulk half 1 + [block a]  ->  solve rows below a  ->  bulk half 2 + K = NB update of b's columns by a + [block b]
-  //   ->  solve rows below b.
-  // The diagonal-block workgroup counts finished GT x GT tiles of its block, so pairs need NB % GT == 0 (a block of a
-  // ragged NB would be factored before its last update arrived): other NB run single panels.  Once the bulk gets too
-  // short (n - t1 < chol.outer_min_rows) new panels are single NB-wide ones again.
-  const int64_t outer_min_rows = (int64_t)ctx_opt(ctx, "chol.outer_min_rows", 16384);
-  // The schedule itself is a pure host function (chol_plan_build, tile_sched.h: tested without a GPU); this loop runs its
-  // operations.  chol.deep = W > 0: far trailing tiles receive a whole block of W columns in one pass that rides in the
-  // launches of the next block's outer steps (OP_SEG); 0: the one-level schedule.
   CholPlanOpts po;
-  po.NB = NB; po.OB = (int64_t)ctx_opt(ctx, "chol.outer", 1024); po.outer_min_rows = outer_min_rows; po.fused_min_rows = min_rows;
+  po.NB = (int64_t)ctx_opt(ctx, "chol.nb", 512);  // outer panel width (multiple of 64)
+  po.OB = (int64_t)ctx_opt(ctx, "chol.outer", 1024);
+  po.outer_min_rows = (int64_t)ctx_opt(ctx, "chol.outer_min_rows", 16384);
+  po.fused_min_rows = (int64_t)ctx_opt(ctx, "chol.fused_min_rows", 12288);
   po.deep = (int64_t)ctx_opt(ctx, "chol.deep", 4096);
   po.deep_min_rows = (int64_t)ctx_opt(ctx, "chol.deep_min_rows", 26624);
   std::shared_ptr<CholPlanEntry> pe;
   GDML_TRY(chol_plan_get(ctx, st, n, n_rows, po, &pe));
-  int ready_count = 0;  // cumulative target of the tile counter d_info[6]
-  HIP_CHECK(ctx, hipMemsetAsync(ctx->d_info + 6, 0, 2 * sizeof(int), ctx->stream));  // counter, wait-timeout flag
-  const int block_tiles = (int)((NB / GT) * (NB / GT + 1) / 2);  // lower GT x GT tiles of a diagonal block
+  HIP_CHECK(ctx, hipMemsetAsync(ctx->d_info + 6, 0, 2 * sizeof(int), ctx->stream));  // tile counter, wait-timeout flag
   for (const CholOp& c : pe->plan.ops) {
     const int64_t k0 = c.k0, nb = c.nb, t0 = c.t0, nb2 = c.nb2, t1 = t0 + nb2;
     const double* P = A + t0 * ld + k0;
@@ -1629,52 +1574,16 @@ int chol_factor_device(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int* inf
         GDML_TRY(launch_panel_trsm(ctx, st, A + t0 * ld + t0, A + t1 * ld + t0, ld, (int)nb2, n_rows - t1));
         break;
       case OP_PAIR1:
-      case OP_PAIR2: {
-        // The first super-tile column of the SYRK is exactly the columns of a | b (2 NB = 8 tiles): it is enumerated first,
-        // workgroup 0 of the first launch waits for the 10 tiles of block a (counter) and factors it while the rest runs.
-        // Second launch: the K = NB update of b's columns by panel a rides in front of the remaining SYRK tiles; workgroup 0
-        // waits for the tiles of block b and factors it.
-        const int64_t ta = t0 + NB;  // first row / column of b
-        const int64_t sm = (ceil_div(n_rows - t0, GT) + 7) / 8, n_super_all = sm * (sm + 1) / 2;
-        int64_t s_split = n_super_all / 2;
-        if (s_split < sm) s_split = sm;
-        const double fs = ((double)s_split + 0.5) / (double)n_super_all;
-        DiagJob dj;
-        dj.nbw = (int)(NB / 64);
-        dj.col0_first = true;
-        dj.ready = ctx->d_info + 6;
-        ready_count += block_tiles;
-        dj.ready_target = ready_count;
-        dj.next_M2 = n_rows - ta; dj.next_N2 = NB; dj.next_K2 = NB;
-        if (c.kind == OP_PAIR1) {
-          dj.A = A + t0 * ld + t0; dj.off = t0;
-          GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, 0.0, fs, true,
-                                           &dj));
-        } else {
-          double* Xa = A + ta * ld + t0;  // rows below block a (they include b's rows of the outer panel)
-          dj.A = A + ta * ld + ta; dj.off = ta;
-          dj.A2 = Xa; dj.B2 = Xa; dj.C2 = A + ta * ld + ta; dj.M2 = n_rows - ta; dj.N2 = NB; dj.K2 = NB;
-          GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, n - t0, nb, 1, fs, 1.0, true,
-                                           &dj));
-        }
+      case OP_PAIR2:
+      case OP_FUSED:
+        GDML_TRY(launch_gemm_lower(ctx, st, A, ld, pe->plan.lowers[c.lower], c.ready_target));
         break;
-      }
       case OP_SEG:
-        ready_count += block_tiles;
-        GDML_TRY(launch_gemm_seg(ctx, st, A, ld, *pe, c.seg, ready_count));
+        GDML_TRY(launch_gemm_seg(ctx, st, A, ld, *pe, c.seg, c.ready_target));
         break;
       case OP_RECT:
         GDML_TRY(launch_gemm_nt_sub(ctx, st, P, ld, P, ld, A + t0 * ld + t0, ld, n_rows - t0, nb2, nb, 0));
         break;
-      case OP_FUSED: {
-        DiagJob dj;
-        dj.A = A + t0 * ld + t0;
-        dj.nbw = (int)(nb2 / 64);
-        dj.off = t0;
-        GDML_TRY(launch_gemm_nt_sub_part(ctx, st, P1, ld, P1, ld, A + t1 * ld + t1, ld, n_rows - t1, n - t1, nb, 1, 0.0,
-                                         1.0, true, &dj));
-        break;
-      }
       case OP_TAIL: {
         // tail: the SYRK is too short to hide the single-workgroup block factorisation; the multi-workgroup step chain and
         // the row-local solve of panel k+1 run on the high-priority stream next to the (small) SYRK grid of panel k
@@ -1697,369 +1606,4 @@ int chol_factor_device(gdml_ctx* ctx, double* A, int64_t n, int64_t ld, int* inf
     return gdml_fail(ctx, GDML_ERR_HIP, "Cholesky: the diagonal-block workgroup gave up waiting for its tiles (schedule bug)");
   if (info_out) *info_out = info8[0];
   return GDML_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Triangular solves with the factor (cho_solve, analytic.py:97-99), blocked by 64.
-// Forward  L z = b : per block J the kernel first solves the 64x64 diagonal system in LDS (every
-// workgroup redundantly: 32 KB from L2), then updates its rows below: b[r] -= L[r,J] z_J.
-// Backward L^T x = z : per block I (from the bottom) solve L_II^T x_I = z_I, then
-// z[c] -= sum_{r in I} L[r,c] x[r] for the columns c left of the block (one thread per column).
-// ------------------------------------------------------------------------------------------
-// 64x64 triangular solve by ONE wavefront, operands in registers.
-//   TRANS = false: L z = b, lane r holds row r of L;    TRANS = true: L^T x = b, lane c holds column c.
-// Ls: LDS copy of the block ([64][65], identity-padded), b: this lane's right-hand side entry.
-template <bool TRANS>
-__device__ __forceinline__ double tri_solve64_wave(const double* Ls, double b, int lane) {
-  double v[64];
-#pragma unroll
-  for (int k = 0; k < 64; ++k) v[k] = TRANS ? Ls[k * 65 + lane] : Ls[lane * 65 + k];
-  double sol = 0.0;
-  if (!TRANS) {
-#pragma unroll
-    for (int c = 0; c < 64; ++c) {
-      const double t = b / v[c];            // meaningful on lane c
-      const double zc = __shfl(t, c, 64);
-      if (lane == c) sol = zc;
-      b -= v[c] * zc;                       // lanes r > c use it; others ignore their b afterwards
-    }
-  } else {
-#pragma unroll
-    for (int r = 63; r >= 0; --r) {
-      const double t = b / v[r];            // lane r: v[r] = L[r][r]
-      const double xr = __shfl(t, r, 64);
-      if (lane == r) sol = xr;
-      b -= v[r] * xr;                       // lane c < r: L[r][c] x_r
-    }
-  }
-  return sol;
-}
-
-__device__ __forceinline__ void load_block64(const double* __restrict__ L, int64_t ld, int64_t c0,
-                                             int w, double* Ls, int tid, int T) {
-  for (int e = tid; e < 64 * 64; e += T) {
-    int r = e >> 6, c = e & 63;
-    double v = (r == c) ? 1.0 : 0.0;
-    if (r < w && c < w && c <= r) v = L[(c0 + r) * ld + c0 + c];
-    Ls[r * 65 + c] = v;
-  }
-}
-
-__global__ void __launch_bounds__(256) trsv_fwd_kernel(const double* __restrict__ L, int64_t ld,
-                                                       int64_t n, int64_t c0, int w,
-                                                       double* __restrict__ b,
-                                                       double* __restrict__ z_out) {
-  __shared__ __attribute__((aligned(16))) double Ls[64 * 65];
-  __shared__ double z[64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  load_block64(L, ld, c0, w, Ls, tid, 256);
-  __syncthreads();
-  if (wave == 0) {
-    const double bi = lane < w ? b[c0 + lane] : 0.0;
-    const double zi = tri_solve64_wave<false>(Ls, bi, lane);
-    z[lane] = zi;
-    if (blockIdx.x == 0 && lane < w) z_out[c0 + lane] = zi;
-  }
-  __syncthreads();
-  // rows below: one wave per row, lanes over the w columns
-  const int64_t first = c0 + w;
-  const double zl = lane < w ? z[lane] : 0.0;
-  for (int64_t r = first + (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
-    double v = lane < w ? L[r * ld + c0 + lane] * zl : 0.0;
-    v = wave_sum(v);
-    if (lane == 0) b[r] -= v;
-  }
-}
-
-__global__ void __launch_bounds__(256) trsv_bwd_kernel(const double* __restrict__ L, int64_t ld,
-                                                       int64_t c0, int w, double* __restrict__ b,
-                                                       double* __restrict__ x_out) {
-  __shared__ __attribute__((aligned(16))) double Ls[64 * 65];
-  __shared__ double x[64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  load_block64(L, ld, c0, w, Ls, tid, 256);
-  __syncthreads();
-  if (wave == 0) {
-    const double bi = lane < w ? b[c0 + lane] : 0.0;
-    const double xi = tri_solve64_wave<true>(Ls, bi, lane);
-    x[lane] = xi;
-    if (blockIdx.x == 0 && lane < w) x_out[c0 + lane] = xi;
-  }
-  __syncthreads();
-  // columns left of the block: z[c] -= sum_{r in block} L[r,c] x[r]   (one thread per column)
-  for (int64_t c = (int64_t)blockIdx.x * 256 + tid; c < c0; c += (int64_t)gridDim.x * 256) {
-    double s = 0.0;
-    for (int r = 0; r < w; ++r) s += L[(c0 + r) * ld + c] * x[r];
-    b[c] -= s;
-  }
-}
-
-// d_b: right-hand side (destroyed), d_z: scratch (n), d_x: solution (n).  All device vectors.
-static int chol_fwd_device(gdml_ctx* ctx, const double* L, int64_t n, int64_t ld, double* d_b, double* d_z) {
-  for (int64_t c0 = 0; c0 < n; c0 += 64) {
-    int w = (int)((n - c0 < 64) ? n - c0 : 64);
-    int64_t rows = n - c0 - w;
-    int grid = (int)((rows + 3) / 4);
-    if (grid < 1) grid = 1;
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(trsv_fwd_kernel, dim3(grid), dim3(256), 0, ctx->stream, L, ld, n, c0, w, d_b,
-                       d_z);
-    ctx->launch_counter++;
-  }
-  return GDML_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Backward substitution L^T x = z as ONE persistent launch (default for n >= 2048; option trsv.persist = 0
-// restores the per-block launches).  Left-looking: the workgroup that owns 64-block k accumulates
-//   s = sum_{c > k} L[c,k]^T x_c      (rows below the block, 512-byte row segments, 4 wavefronts over the blocks c)
-// as the x_c become available, then solves the transposed diagonal block and publishes x_k.  Blocks are
-// owned cyclically (from the bottom) by one workgroup per CU, all resident at once.  The solution vector itself is the
-// availability signal: it is pre-filled with a NaN sentinel, x_k is published with relaxed agent-scope 8-byte stores and
-// the consumers poll the elements they need (x crosses
-// XCDs, i.e. L2s).  Blocks are dealt round-robin, so a workgroup also waits for blocks of workgroups with a HIGHER
-// index (workgroup 0 at round 2 needs the last workgroup's block of round 1): all min(nbk, CUs) workgroups must
-// be resident at once.  One workgroup per CU on an otherwise idle stream satisfies that; where it does not (GPU
-// shared with another process) the bounded spins give up, `err` is set and the host falls back to the
-// per-block launches below.
-// ------------------------------------------------------------------------------------------
-// Sentinel of "not yet solved" in the solution vector of the persistent backward substitution: a quiet NaN with a
-// payload no arithmetic produces (hardware NaNs are 0x7FF8000000000000 / 0xFFF8...).
-#define TRSV_PENDING 0x7FF8A5A5C3C30001ull
-
-__global__ void __launch_bounds__(256) trsv_fill_pending_kernel(unsigned long long* __restrict__ x, int64_t n) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t < n) x[t] = TRSV_PENDING;
-}
-
-__global__ void __launch_bounds__(256) trsv_bwd_persist_kernel(const double* __restrict__ L, int64_t ld,
-                                                               int64_t n, int nbk, const double* __restrict__ z,
-                                                               double* x, int* err) {
-  __shared__ __attribute__((aligned(16))) double Ls[64 * 65];
-  __shared__ double part[4][64];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  unsigned long long* xb = reinterpret_cast<unsigned long long*>(x);
-  for (int kk = blockIdx.x; kk < nbk; kk += gridDim.x) {  // kk counts blocks from the bottom
-    const int k = nbk - 1 - kk;
-    const int64_t c0 = (int64_t)k * 64;
-    const int wk = (int)((n - c0 < 64) ? n - c0 : 64);
-    load_block64(L, ld, c0, wk, Ls, tid, 256);  // diagonal block (independent of x): overlaps the waiting
-    __syncthreads();
-    const double rdiag = 1.0 / Ls[lane * 65 + lane];  // reciprocal pivots off the critical path (identity on padding)
-    double acc = 0.0;
-    for (int cc = wv; cc < kk; cc += 4) {  // blocks below, bottom first; this wavefront takes every 4th
-      const int c = nbk - 1 - cc;
-      const int64_t r0 = (int64_t)c * 64;
-      const int rows = (int)((n - r0 < 64) ? n - r0 : 64);
-      // the L block does not depend on x: its 64 row segments are in flight while the wavefront waits for x_c
-      const double* Lp = L + r0 * ld + c0 + (lane < wk ? lane : 0);
-      double lreg[64];
-#pragma unroll
-      for (int i = 0; i < 64; ++i) lreg[i] = (i < rows) ? Lp[(int64_t)i * ld] : 0.0;
-      // x_c is published element by element (relaxed agent-scope stores of the 8-byte values over the sentinel): the
-      // consumer polls the data itself -- one memory round trip, no separate flag, no fences
-      unsigned long long xv = 0;
-      int spins = 0;
-      for (;;) {
-        xv = (lane < rows) ? __hip_atomic_load(xb + r0 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-        if (!__any(xv == TRSV_PENDING)) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > (1 << 26)) {  // ~1 min: only reachable if the GPU is shared with another process for that long
-          if (lane == 0) atomicExch(err, 1);
-          xv = 0;
-          break;
-        }
-      }
-      const double xd = __longlong_as_double((long long)xv);
-#pragma unroll
-      for (int i = 0; i < 64; ++i) acc += lreg[i] * __shfl(xd, i, 64);
-    }
-    part[wv][lane] = (lane < wk) ? acc : 0.0;
-    __syncthreads();
-    if (wv == 0) {
-      const double s = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
-      double bi = lane < wk ? z[c0 + lane] - s : 0.0;
-      // transposed 64 x 64 solve, row r of L broadcast from lane r: x_r = b_r / L_rr; b_c -= L_rc x_r (c < r)
-      double sol = 0.0;
-#pragma unroll
-      for (int r = 63; r >= 0; --r) {
-        const double xr = __shfl(bi * rdiag, r, 64);
-        if (lane == r) sol = xr;
-        bi -= Ls[r * 65 + lane] * xr;
-      }
-      if (lane < wk)
-        __hip_atomic_store(xb + c0 + lane, (unsigned long long)__double_as_longlong(sol), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-  }
-}
-
-// d_z is destroyed
-int chol_bwd_device(gdml_ctx* ctx, const double* L, int64_t n, int64_t ld, double* d_z, double* d_x) {
-  const int persist = ctx_opt_i(ctx, "trsv.persist", 1);
-  if (persist && n >= 2048) {
-    const int nbk = (int)((n + 63) / 64);
-    int* err = ctx->d_info + 5;
-    HIP_CHECK(ctx, hipMemsetAsync(err, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(trsv_fill_pending_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, ctx->stream,
-                       reinterpret_cast<unsigned long long*>(d_x), n);
-    const int grid = nbk < ctx->num_cus ? nbk : ctx->num_cus;  // one workgroup per CU, all resident
-    hipLaunchKernelGGL(trsv_bwd_persist_kernel, dim3(grid), dim3(256), 0, ctx->stream, L, ld, n, nbk, d_z, d_x, err);
-    ctx->launch_counter++;
-    int h_err = 0;
-    HIP_CHECK(ctx, hipMemcpyAsync(&h_err, err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (h_err == 0) return GDML_OK;
-    // a workgroup gave up waiting (the persistent launch needs all its workgroups co-resident: not guaranteed when
-    // the GPU is shared): d_z was only read so far, redo the substitution with one launch per block
-  }
-  int64_t last = ((n - 1) / 64) * 64;
-  for (int64_t c0 = last; c0 >= 0; c0 -= 64) {
-    int w = (int)((n - c0 < 64) ? n - c0 : 64);
-    int grid = (int)((c0 + 255) / 256);
-    if (grid < 1) grid = 1;
-    if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(trsv_bwd_kernel, dim3(grid), dim3(256), 0, ctx->stream, L, ld, c0, w, d_z,
-                       d_x);
-    ctx->launch_counter++;
-  }
-  HIP_CHECK(ctx, hipGetLastError());
-  return GDML_OK;
-}
-
-int chol_solve_device(gdml_ctx* ctx, const double* L, int64_t n, int64_t ld, double* d_b,
-                      double* d_z, double* d_x) {
-  GDML_TRY(chol_fwd_device(ctx, L, n, ld, d_b, d_z));
-  return chol_bwd_device(ctx, L, n, ld, d_z, d_x);
-}
-
-// ------------------------------------------------------------------------------------------
-extern "C" int gdml_chol_set_rhs(gdml_ctx* ctx, const double* y, int64_t n) {
-  if (!ctx || !y) return GDML_ERR_INVALID;
-  if (!ctx->K || ctx->K_rows != ctx->K_cols)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_chol_set_rhs: assemble a square K first");
-  if (ctx->K_factored) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_chol_set_rhs: K is already factored");
-  if (ctx->K_extra < 1)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_chol_set_rhs: K was assembled without an extra row");
-  if (n != ctx->K_rows) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_chol_set_rhs: n mismatch");
-  HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (ctx->d_rhs) GDML_TRY(ctx_free(ctx, ctx->d_rhs));
-  ctx->d_rhs = nullptr;
-  GDML_TRY(ctx_alloc(ctx, (void**)&ctx->d_rhs, n * 8));
-  HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_rhs, y, n * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_CHECK(ctx, hipMemcpyAsync(ctx->K + n * ctx->K_ld, ctx->d_rhs, n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-  HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // y is a pageable host array owned by the caller
-  ctx->K_rhs_row = true;
-  return GDML_OK;
-}
-
-extern "C" int gdml_chol_factor(gdml_ctx* ctx, double lam, int* info) {
-  if (!ctx) return GDML_ERR_INVALID;
-  if (!ctx->K) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_chol_factor: assemble K first");
-  if (ctx->K_rows != ctx->K_cols)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_chol_factor: resident K is %lld x %lld, not square",
-                     (long long)ctx->K_rows, (long long)ctx->K_cols);
-  if (ctx->K_factored) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_chol_factor: already factored");
-  if (ctx->K_destroyed)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_chol_factor: the resident matrix was consumed by a failed factorisation: assemble again");
-  HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const int64_t n = ctx->K_rows;
-  if (ctx->K_is_A && lam != ctx->K_lam)
-    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_chol_factor: lam (%g) differs from the one gdml_assemble_A used (%g)",
-                     lam, ctx->K_lam);
-  phase_begin(ctx);
-  if (!ctx->K_is_A) {  // un-negated K from gdml_assemble_K: A = -K + lam I on the lower triangle (analytic.py:65,82)
-    hipLaunchKernelGGL(negate_shift_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, ctx->K, n,
-                       ctx->K_ld, lam);
-    ctx->launch_counter++;
-  }
-  int inf = 0;
-  GDML_TRY(chol_factor_device(ctx, ctx->K, n, ctx->K_ld, &inf, ctx->K_rhs_row ? n + 1 : n));
-  GDML_TRY(phase_end(ctx, "factor"));
-  if (info) *info = inf;
-  ctx->K_lam = lam;
-  if (inf != 0) {
-    ctx->K_factored = false;
-    ctx->K_destroyed = true;
-    return gdml_fail(ctx, GDML_ERR_NOT_PD,
-                     "%d-th leading minor of the array is not positive definite", inf);
-  }
-  ctx->K_factored = true;
-  return GDML_OK;
-}
-
-__global__ void __launch_bounds__(256) scale_kernel(double* __restrict__ x, int64_t n, double s) {
-  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) x[t] *= s;
-}
-__global__ void __launch_bounds__(256) axpy_kernel(double* __restrict__ y, const double* __restrict__ x,
-                                                   int64_t n, double a) {
-  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) y[t] += a * x[t];
-}
-// r = y - (-(Kx - lam x))... helper: r = y + kv  where kv = K x - lam x  (A x = -(K x - lam x))
-__global__ void __launch_bounds__(256) resid_kernel(const double* __restrict__ y,
-                                                    const double* __restrict__ kv, int64_t n,
-                                                    double* __restrict__ r) {
-  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < n) r[t] = y[t] + kv[t];
-}
-
-int operator_model_from_trainset(gdml_ctx* ctx, double sig);
-
-extern "C" int gdml_chol_solve(gdml_ctx* ctx, const double* y, int64_t n, int n_refine,
-                               double* alphas_out) {
-  if (!ctx || !alphas_out) return GDML_ERR_INVALID;
-  if (!ctx->K || !ctx->K_factored)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_chol_solve: no Cholesky factor resident");
-  if (!y && !ctx->K_rhs_row)
-    return gdml_fail(ctx, GDML_ERR_STATE, "gdml_chol_solve(y = NULL) needs gdml_chol_set_rhs before the factorisation");
-  if (n != ctx->K_rows) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_chol_solve: n mismatch");
-  HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  void* buf = nullptr;
-  GDML_TRY(ctx_alloc(ctx, &buf, 6 * n * 8));
-  double* dx = (double*)buf;   // solution
-  double* dy = dx + n;         // right-hand side (kept)
-  double* db = dy + n;         // work copy of a right-hand side (destroyed by the solve)
-  double* dz = db + n;         // forward-substitution result
-  double* dr = dz + n;         // refinement correction
-  double* dkv = dr + n;        // K x - lam x
-  int rc = GDML_OK;
-  hipError_t e;
-  if (y) {
-    e = hipMemcpyAsync(dy, y, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(db, dy, n * 8, hipMemcpyDeviceToDevice, ctx->stream);
-  } else {  // forward substitution already done by the factorisation: z is row n of the factor buffer
-    e = hipMemcpyAsync(dy, ctx->d_rhs, n * 8, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(dz, ctx->K + n * ctx->K_ld, n * 8, hipMemcpyDeviceToDevice, ctx->stream);
-  }
-  if (e != hipSuccess) rc = gdml_fail(ctx, GDML_ERR_HIP, "copy: %s", hipGetErrorString(e));
-  if (rc == GDML_OK) {
-    phase_begin(ctx);
-    rc = y ? chol_solve_device(ctx, ctx->K, n, ctx->K_ld, db, dz, dx)
-           : chol_bwd_device(ctx, ctx->K, n, ctx->K_ld, dz, dx);
-  }
-  if (rc == GDML_OK && n_refine > 0) rc = operator_model_from_trainset(ctx, ctx->K_sig);
-  for (int it = 0; rc == GDML_OK && it < n_refine; ++it) {
-    // r = y - A x,  A x = -(K x - lam x)  =>  r = y + (K x - lam x)
-    rc = matvec_device(ctx, ctx->K_lam, ctx->K_use_E, dx, n, dkv);
-    if (rc != GDML_OK) break;
-    hipLaunchKernelGGL(resid_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, ctx->stream, dy, dkv, n, db);
-    rc = chol_solve_device(ctx, ctx->K, n, ctx->K_ld, db, dz, dr);
-    if (rc != GDML_OK) break;
-    hipLaunchKernelGGL(axpy_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, ctx->stream, dx, dr, n, 1.0);
-  }
-  if (rc == GDML_OK) {
-    hipLaunchKernelGGL(scale_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, ctx->stream, dx, n, -1.0);
-    rc = phase_end(ctx, "solve");
-  }
-  if (rc == GDML_OK) {
-    e = hipMemcpyAsync(alphas_out, dx, n * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = gdml_fail(ctx, GDML_ERR_HIP, "D2H: %s", hipGetErrorString(e));
-  }
-  int rc2 = ctx_free(ctx, buf);
-  return rc != GDML_OK ? rc : rc2;
 }

@@ -15,6 +15,7 @@
 //                       that are not in a round form the head, everything else the tail.
 // The schedule of an outer step (one list, one or two launches) is built on the host by tile_sched_build.
 #pragma once
+#include <array>
 #include <math.h>
 #include <stdint.h>
 #include <vector>
@@ -135,6 +136,7 @@ struct TileSched {
   TileLaunch L[2] = {};          // L[l].table is left null: the caller points it at its copy of table[l]
   std::vector<uint32_t> table[2];
   int64_t blocks[2] = {0, 0};    // grid of the tile list (multiple of 8)
+  double base_last[8] = {};      // the other work the list was dealt around (tile_sched_build's argument)
   int64_t tiles[2] = {0, 0};
   // tiles per launch by kind, for the flop count: off-diagonal / diagonal, above / in the last tile row
   int64_t off_int[2] = {0, 0}, off_last[2] = {0, 0}, diag_int[2] = {0, 0}, diag_last[2] = {0, 0};
@@ -182,6 +184,7 @@ inline void deal(const std::vector<uint32_t>& tiles, const int64_t prior[8], con
 inline void tile_sched_build(int tiles_m, int tiles_n, bool col0_first, int n_launch, const double base_last[8], TileSched* S) {
   *S = TileSched();
   S->n_launch = n_launch;
+  for (int x = 0; x < 8 && base_last; ++x) S->base_last[x] = base_last[x];
   const int sm = (tiles_m + 7) / 8, fm = tiles_m / 8;
   if (tiles_m < 1 || tiles_n < 1 || tiles_n > tiles_m || tiles_m > 0xffff || (n_launch != 1 && n_launch != 2)) return;
   if (fm >= 2 && (fm - 1) * 8 > tiles_n) return;  // a "full" super tile would be cut by the column bound
@@ -300,8 +303,9 @@ inline double tile_sched_flops(const TileSched& S, int l, int64_t M, int64_t K, 
 }
 
 // ---- the factorisation's launch plan (host only) and the composed launches of the deep schedule (chol.deep) ------
-// chol_plan_build restates the schedule of chol_factor_device as a list of operations; chol_factor_device runs that
-// list.  With chol.deep = 0 the list is the one-level schedule: panel pairs, fused single panels, tail.  With chol.deep = W
+// chol_plan_build states the schedule as a list of operations, each fused launch with its full description (PlanLowerLaunch
+// one-level, PlanSegLaunch composed); chol_factor_device (chol.hip) runs that list and derives nothing of its own.  With
+// chol.deep = 0 the list is the one-level schedule: panel pairs, fused single panels, tail.  With chol.deep = W
 // the columns form blocks [0, NB + W), [NB + W, NB + 2 W), ...  Inside block b the K = 2 NB update of an outer step covers
 // only the tile columns of block b (near band); the tiles right of it receive the whole block in ONE pass of depth W (far
 // pass) that has no launch of its own: its tiles ride in the launches of block b + 1's outer steps, as further SEGMENTS
@@ -331,18 +335,74 @@ struct PlanSegLaunch {
   int64_t tiles = 0, far_tiles = 0;
   double flops = 0.0, far_flops = 0.0, cost = 0.0;
 };
+// One-level fused launch (OP_PAIR1, OP_PAIR2, OP_FUSED): launch `launch` of the n_launch (1 or 2) that share the tile list of
+// the lower update upd; workgroup 0 factors the diagonal block at diag0 meanwhile.  A lower update without a diagonal block
+// (the public launch_gemm_nt_sub, lower) is the same description with only upd set.
+struct PlanLowerLaunch {
+  PlanSeg upd;                   // kind 0
+  int col0_first = 0;            // super column 0 (the outer panel's own columns) leads the list and lies in launch 0
+  int launch = 0, n_launch = 1;
+  PlanSeg second;                // kind 2 (M = 0: none): led by the list's LAST launch, as workgroups in front of its tiles
+  int carries_second = 0;        // this launch carries it (0: a later one will; the list is dealt around it all the same)
+  int64_t diag0 = 0;             // first row of the diagonal block
+  int diag_nbw = 0;              // its width / 64 (0: no block)
+  int counted = 0;               // its tiles are in this launch (the leading tiles of upd, or of second where carried) and
+                                 // count themselves: their number (0: the block is complete before the launch)
+};
 enum { OP_PANEL = 0, OP_RECT, OP_PAIR1, OP_PAIR2, OP_FUSED, OP_TRSM, OP_TAIL, OP_SEG };
 struct CholOp {
   int kind = 0;
   int64_t k0 = 0, nb = 0;   // finished panel: columns [k0, k0 + nb)
   int64_t t0 = 0, nb2 = 0;  // next panel (OP_TRSM: the diagonal block and its width)
   int seg = -1;             // OP_SEG: index into CholPlan::segs
+  int lower = -1;           // OP_PAIR1, OP_PAIR2, OP_FUSED: index into CholPlan::lowers
+  int ready_target = 0;     // launches with counted tiles: what the tile counter, which is never reset, shows when they are all in
 };
 struct CholPlan {
   std::vector<CholOp> ops;
   std::vector<PlanSegLaunch> segs;
+  std::vector<PlanLowerLaunch> lowers;
   int64_t NB = 0, OB = 0, deep = 0, deep_end = 0;  // deep_end: first column of the step that leaves the deep regime (0: never entered)
 };
+
+// ---- what a PlanLowerLaunch means for the launcher (chol.hip) and for tests/tile_balance_driver.cpp
+inline PlanLowerLaunch plan_lower_plain(int64_t M, int64_t N, int64_t K) {
+  PlanLowerLaunch L;
+  L.upd.M = M; L.upd.N = N; L.upd.K = K;
+  return L;
+}
+// workgroups of a second problem in front of a launch; *compact: each of them holds a tile (tile_decode_second)
+inline int plan_second_blocks(int64_t M2, int64_t N2, bool* compact) {
+  const int64_t tm2 = (M2 + 127) / 128, tn2 = (N2 + 127) / 128;
+  *compact = tm2 >= tn2;
+  return (int)(tm2 * tn2 - (*compact ? tn2 * (tn2 - 1) / 2 : 0));
+}
+// everything the balanced list depends on: tiles_m, tiles_n, col0_first, n_launch, and of a (compact) second problem its
+// workgroups and the two depths
+inline std::array<int64_t, 7> plan_lower_key(const PlanLowerLaunch& L) {
+  bool compact = false;
+  const int lead2 = (L.second.M > 0 && L.second.N > 0) ? plan_second_blocks(L.second.M, L.second.N, &compact) : 0;
+  const bool has2 = compact && lead2 > 0;
+  return {(L.upd.M + 127) / 128, (L.upd.N + 127) / 128, L.col0_first ? 1 : 0, L.n_launch, has2 ? lead2 : 0, has2 ? L.second.K : 0,
+          has2 ? L.upd.K : 0};
+}
+// the balanced list (all its launches); !S->ok: the shape has none and keeps the super-tile enumeration
+inline void plan_lower_sched(const PlanLowerLaunch& L, TileSched* S) {
+  const std::array<int64_t, 7> k = plan_lower_key(L);
+  // the second problem's block q sits lead2 - q blocks in front of the list's block 0: XCD label (q - lead2) mod 8
+  const int lead2 = (int)k[4];
+  double base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int q = 0; q < lead2; ++q) base[((q - lead2) % 8 + 8) % 8] += (double)k[5] / (double)k[6];
+  tile_sched_build((int)k[0], (int)k[1], k[2] != 0, (int)k[3], base, S);
+}
+// super-tile enumeration: the super tiles [*s_begin, *n_super) of this launch.  Two launches cut the list in the middle, but
+// not inside super column 0.
+inline void plan_lower_range(const PlanLowerLaunch& L, int64_t* s_begin, int64_t* n_super) {
+  const int64_t sm = ((L.upd.M + 127) / 128 + 7) / 8, n_all = sm * (sm + 1) / 2;
+  const int64_t s_split = n_all / 2 < sm ? sm : n_all / 2;
+  *s_begin = (L.n_launch == 2 && L.launch == 1) ? s_split : 0;
+  *n_super = (L.n_launch == 2 && L.launch == 0) ? s_split : n_all;
+}
 
 namespace cp_detail {
 const int GT_ = 128;
@@ -472,9 +532,14 @@ inline void chol_plan_build(int64_t n, int64_t n_rows, CholPlanOpts o, CholPlan*
   using namespace cp_detail;
   *P = CholPlan();
   if (n_rows < n) n_rows = n;
+  // The options are clamped here and nowhere else.
   int64_t NB = o.NB;
-  if (NB < 64 || NB % 64 || NB > 512) NB = 512;
+  if (NB < 64 || NB % 64 || NB > 512) NB = 512;  // the diagonal-block role and the row-local solve hold at most 8 x 64 columns
+  // a fused launch needs a trailing matrix to ride in: with 0 the last panel of a matrix with a carried right-hand-side row
+  // (n - t1 = 0, n_rows - t1 = 1) asked for a fused launch with an empty update, which the launcher skips together with its
+  // diagonal-block workgroup -- the block was never factored
   int64_t min_rows = o.fused_min_rows < 1 ? 1 : o.fused_min_rows;
+  // pairs count finished 128 x 128 tiles of the diagonal block, so they need NB % 128 == 0: other NB run single panels
   int64_t OB = o.OB;
   if (OB != 2 * NB || NB % GT_ != 0) OB = NB;
   P->NB = NB; P->OB = OB;
@@ -540,6 +605,23 @@ inline void chol_plan_build(int64_t n, int64_t n_rows, CholPlanOpts o, CholPlan*
     gen_units(0, s, near_pred(s, bound), false, &u, 0, bound, true);
     gen_units(2, s2, [](int, int) { return true; }, true, &u, 0, NBt);
     return units_cost(u);
+  };
+
+  int ready = 0;  // the tile counter so far
+  auto counted_op = [&](int tiles) { P->ops.back().ready_target = (ready += tiles); };
+  // one-level fused launches: the pair of an outer step (one tile list of everything right of the finished panel, first
+  // columns first, cut in two; the second leads with the K = NB update of b's columns by panel a) and the single fused one
+  auto lower_op = [&](int kind, int64_t k0, int64_t nb, int64_t t0, int64_t nb2) {
+    PlanLowerLaunch L;
+    const bool pair = kind != OP_FUSED;
+    L.upd = near_seg(pair ? t0 : t0 + nb2, k0, nb);
+    if (pair) { L.col0_first = 1; L.n_launch = 2; L.launch = L.carries_second = (kind == OP_PAIR2) ? 1 : 0; L.second = second_seg(t0); }
+    L.diag0 = t0 + L.launch * NB; L.diag_nbw = (int)((pair ? NB : nb2) / 64);
+    L.counted = pair ? block_tiles : 0;
+    P->lowers.push_back(L);
+    op(kind, k0, nb, t0, nb2);
+    P->ops.back().lower = (int)P->lowers.size() - 1;
+    if (L.counted) counted_op(L.counted);
   };
 
   int64_t k0 = 0, nb = (n < NB) ? n : NB;
@@ -619,17 +701,18 @@ inline void chol_plan_build(int64_t n, int64_t n_rows, CholPlanOpts o, CholPlan*
         deal_launch(u, l == 1 ? 2 : (counted_in_pool ? 1 : 0), NBt, &L);
         P->segs.push_back(std::move(L));
         op(OP_SEG, k0, nb, t0, nb2, (int)P->segs.size() - 1);
+        counted_op(block_tiles);
         op(OP_TRSM, 0, 0, l == 0 ? t0 : ta, NB);
       }
     } else if (fuse && nb2 == 2 * NB) {
-      op(OP_PAIR1, k0, nb, t0, nb2);
+      lower_op(OP_PAIR1, k0, nb, t0, nb2);
       op(OP_TRSM, 0, 0, t0, NB);
-      op(OP_PAIR2, k0, nb, t0, nb2);
+      lower_op(OP_PAIR2, k0, nb, t0, nb2);
       op(OP_TRSM, 0, 0, t0 + NB, NB);
     } else {
       op(OP_RECT, k0, nb, t0, nb2);
       if (fuse) {
-        op(OP_FUSED, k0, nb, t0, nb2);
+        lower_op(OP_FUSED, k0, nb, t0, nb2);
         op(OP_TRSM, 0, 0, t0, nb2);
       } else if (t1 < n) {
         op(OP_TAIL, k0, nb, t0, nb2);

@@ -35,25 +35,27 @@ int main(int argc, char** argv) {
          (long long)P.deep, (long long)P.deep_end, words * 4, longest);
   const long long NB = P.NB, OB = P.OB, GT = 128;
   for (const CholOp& c : P.ops) {
-    const long long k0 = c.k0, nb = c.nb, t0 = c.t0, nb2 = c.nb2, t1 = t0 + nb2, ta = t0 + NB;
+    const long long k0 = c.k0, nb = c.nb, t0 = c.t0, nb2 = c.nb2, t1 = t0 + nb2;
     printf("OP %s %lld %lld %lld %lld\n", names[c.kind], k0, nb, t0, nb2);
     switch (c.kind) {
       case OP_PANEL: printf("P %lld %lld\n", t0, nb2); break;
       case OP_TRSM: printf("T %lld %lld\n", t0, nb2); break;
       case OP_RECT: printf("G %lld %lld %lld 0 %lld %lld\n", t0, t0, t1, k0, k0 + nb); break;
-      case OP_PAIR1:  // (which launch holds which tile right of the first columns is the balanced list's business)
-        printf("G %lld %lld %lld 1 %lld %lld\n", t0, t0, t0 + OB, k0, k0 + nb);
-        printf("D %lld %lld\n", t0, NB);
-        break;
+      case OP_PAIR1:
       case OP_PAIR2:
-        printf("G %lld %lld %lld 1 %lld %lld\n", t0, t0 + OB, (long long)n, k0, k0 + nb);
-        printf("G %lld %lld %lld 1 %lld %lld\n", ta, ta, ta + NB, t0, ta);
-        printf("D %lld %lld\n", ta, NB);
+      case OP_FUSED: {
+        // a list in two launches is shown as cut behind the outer panel's own columns, which the first launch must hold
+        // (which launch holds which tile right of them is the balanced list's business)
+        const PlanLowerLaunch& L = P.lowers[c.lower];
+        const PlanSeg &u = L.upd, &s = L.second;
+        const long long cut = u.origin + OB, c_lo = L.launch == 0 ? u.origin : cut, c_hi = L.launch + 1 < L.n_launch ? cut : u.origin + u.N;
+        printf("G %lld %lld %lld 1 %lld %lld\n", (long long)u.origin, c_lo, c_hi, (long long)u.a_col0, (long long)(u.a_col0 + u.K));
+        if (L.carries_second)
+          printf("G %lld %lld %lld 1 %lld %lld\n", (long long)s.origin, (long long)s.origin, (long long)(s.origin + s.N), (long long)s.a_col0,
+                 (long long)(s.a_col0 + s.K));
+        printf("D %lld %lld\n", (long long)L.diag0, 64LL * L.diag_nbw);
         break;
-      case OP_FUSED:
-        printf("G %lld %lld %lld 1 %lld %lld\n", t1, t1, (long long)n, k0, k0 + nb);
-        printf("D %lld %lld\n", t0, nb2);
-        break;
+      }
       case OP_TAIL:
         printf("P %lld %lld\n", t0, nb2);
         printf("G %lld %lld %lld 1 %lld %lld\n", t1, t1, (long long)n, k0, k0 + nb);

@@ -3,7 +3,10 @@ with the host compiler (address and undefined-behaviour sanitizers where the too
 main) and runs the kernels' decode for every block index of every launch of
   - tile lists of 1 .. 40, 320 and 481 tile rows (every tiles_m % 8, fewer than 8 super rows), with and without the
     first-column-first form, in one and two launches, with and without a second problem, with and without a carried row;
-  - every lower launch of the benchmark's factorisation (n = 63 000, 63 001 rows, default options).
+  - every lower launch of the plan (chol_plan_build, chol.deep = 0) of the benchmark's factorisation (n = 63 000, 63 001
+    rows) and of n = 2500, 2501 rows, at the default options and at chol.nb = 128 with the thresholds of
+    tests/test_tile_balance_gpu.py, through the launcher's own host functions (plan_lower_sched, plan_lower_range);
+  - the integer range of the super-tile list of a launch against the floating-point share it replaced.
 Per list it asserts: every lower tile exactly once and none above the diagonal; first-column tiles in the first launch and
 ahead of the rest on their XCD; exactly the diagonal block's tiles counted; per-XCD work within 8 tiles of the launch's mean
 (second problem at K2 / K); fewer than 8 empty blocks; the flop counts; and that the super-tile enumeration (gemm.balance = 0)
