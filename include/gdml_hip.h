@@ -604,6 +604,90 @@ int gdml_predict_virial(gdml_ctx* ctx, const double* R, int64_t B, const double*
 int gdml_predict_virial_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lat,
                             const double* lat_inv, double* E_dev, double* F_dev, double* W_dev);
 
+/* The same prediction with ONE LATTICE PER GEOMETRY: B independent cells, or the B volumes of an equation-of-state scan, as
+ * one batch.  lats, lat_invs (B,3,3): geometry b's lattice and its inverse, each row-major with the cell vectors in the
+ * COLUMNS like lat everywhere else; both are required (GDML_ERR_INVALID before any launch for a NULL R, lats or lat_invs;
+ * there is no training-set mode).  The inverse only feeds the rounding to the minimum image, as in every other entry.
+ * Outputs are UNSCALED: E_out (B), F_out (B,3N), W_out (B,3,3) as in gdml_predict_virial; E_out and F_out may be NULL.  W_out
+ * may be NULL as well (F_out then may not): the call is then a plain prediction with per-geometry lattices and runs
+ * gdml_predict's epilogue.
+ * On the general prediction route the lattice enters the descriptor kernel only; every route kernel (WAVE, BIG, BULK, MFMA,
+ * WIDE) and both epilogues work from the query tables.  So this entry runs desc_cells_kernel -- desc_kernel with geometry m
+ * reading lattice m from device memory, the minimum-image arithmetic being one shared device function -- and everything
+ * behind it unchanged: with B equal lattices E, F and W are bit-identical to gdml_predict_virial_dev (W_out = NULL:
+ * gdml_predict_dev) with that lattice, and row b of a call with distinct lattices equals row b of the one-lattice call on
+ * the whole batch with lattice b.  The host entry ALWAYS takes the general route, for one to eight geometries too: the
+ * single-launch predictor holds one lattice by value in its kernel argument.  Hence the host entry equals the _dev entry
+ * (device pointers throughout, lattices included) bit for bit, and the same call repeated gives the same bits. */
+int gdml_predict_virial_cells(gdml_ctx* ctx, const double* R, int64_t B, const double* lats, const double* lat_invs,
+                              double* E_out, double* F_out, double* W_out);
+int gdml_predict_virial_cells_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lats_dev,
+                                  const double* lat_invs_dev, double* E_dev, double* F_dev, double* W_dev);
+
+/* Variable-cell relaxation on the device: B independent periodic geometries relax atoms AND cell by FIRE, the whole state
+ * resident in device memory -- the equilibrium cell of a periodic model, its volume under pressure, an E(V) curve.  The model
+ * users know is ASE's FIRE(UnitCellFilter(atoms)); the reference has no counterpart.
+ * State.  Per geometry a fixed reference lattice L0, a deformation gradient Fd (3 x 3) and reference positions s_i, with
+ *   r_i = Fd s_i and lattice L = Fd L0 (cell vectors in the columns).  The generalised coordinates are the (N + 3) x 3 array
+ *   u = (s_1 ... s_N, C), C = cell_factor Fd (row-major; cell_factor makes the cell rows commensurate with atom rows, ASE
+ *   uses N).  ONE FIRE system per geometry over its 3N + 9 coordinates: v, dt, alpha, n_pos, n_taken as in gdml_relax_run.
+ *   A fresh start: s = R0, C = cell_factor I, v = 0.
+ * Evaluation t = 0, 1, ... of an active geometry:
+ *   1. Fd = C / cell_factor (entry by entry);  L = Fd L0;  r_i = Fd s_i;  Vol = |det L|.  All 3 x 3 algebra in fp64 WITHOUT
+ *      fused multiply-adds, every product sum from left to right: (A B)_ab = A_a0 B_0b + A_a1 B_1b + A_a2 B_2b.  Inverses by
+ *      the adjugate, for M = ((a,b,c),(d,e,f),(g,h,i)):  adj = (ei - fh, ch - bi, bf - ce;  fg - di, ai - cg, cd - af;
+ *      dh - eg, bg - ah, ae - bd),  det = a adj_00 + b adj_10 + c adj_20,  M^-1 = adj / det entry by entry.  A non-finite or
+ *      zero det L counts as a non-finite value of the geometry (first_bad_step).
+ *   2. E', F', W' = gdml_predict_virial_cells_dev for (r, L, L^-1) of all B geometries in one call (frozen ones included;
+ *      their results are discarded).
+ *   3. Generalised force in the caller's units, g = f_scale F':
+ *        G_i = Fd^T g_i;   T = mask o (f_scale W' + pressure Vol I);   G_cell = -T Fd^-T / cell_factor
+ *      mask: symmetric 3 x 3 of 0/1 (NULL: all ones) selecting the strain components that relax (in-plane only for a slab:
+ *      ones in the upper left 2 x 2).  With mask = 1, G = -dH/du of H = f_scale E' + pressure Vol (dE' = W' : dFd Fd^-1 and
+ *      dVol = Vol tr(dFd Fd^-1) at fixed s).
+ *   4. f_atom = max over the N + 3 rows of |G_row|.  E', Vol and f_atom go into the history.  Converged (f_atom < fmax),
+ *      budget (t = max_steps) and non-finite handling and freezing: gdml_relax_run's steps 1-3; the non-finite check covers
+ *      s, C, v, G (hence F' and W'), E' and det L.
+ *   5. otherwise gdml_relax_run's update 4, verbatim (the same device function), on u with G, over 3N + 9 coordinates.
+ * Launches per evaluation: the prediction (desc_cells_kernel, the route's kernels, the virial epilogue), then ONE kernel with
+ *   a workgroup of 256 per geometry: G, the FIRE update, the Cartesian r(t+1), L(t+1), L^-1(t+1) that the next prediction
+ *   reads, history, frame, and the end-of-run outputs.  One small launch before evaluation 0 makes r, L, L^-1 of the start.
+ *   Sums as in gdml_relax_run (per-thread partial sums in index order, the 256-slot tree); no floating-point atomics.  A
+ *   frozen geometry's workgroup returns on its status word; nothing of it is written again.  Chunks, recorder, status and
+ *   first_bad_step readback are gdml_relax_run's (predict.relax_chunk_steps, predict.md_chunk_frames / 64 MiB).  There is NO
+ *   single-launch route: the single-launch predictor holds one lattice by value in its kernel argument (FusedModel).
+ * Arguments.  S (B,3N), Cc (B,3,3), V (B,3N+9), dt, alpha (B), n_pos, n_taken (B, int64): the state, start on entry, end on
+ *   return; L0 (B,3,3) is read only.  Passing the end state back with the same L0 continues the run bit for bit.
+ *   R_end (B,3N), lat_end (B,3,3): Cartesian end positions Fd s and end lattice Fd L0.  E_end (B), F_end (B,3N), W_end
+ *   (B,3,3): UNSCALED, the bits of gdml_predict_virial_cells_dev(R_end, lat_end) at the same B.  vol_end (B) = |det lat_end|.
+ *   E_hist, vol_hist, fmax_hist (max_steps + 1, B), status (B,2), first_bad_step (B), record_every: as in gdml_relax_run.
+ *   R_rec (max_steps / record_every + 1, B, 3N), lat_rec (.., B, 3, 3): Cartesian frames; each may be NULL.
+ * Bit-identical: the same call repeated; n steps then a continuation against 2 n steps; any chunk length; any record_every.
+ *   With mask = 0, pressure = 0 and C = cell_factor I: gdml_relax_run's general route with lat = L0 (r = I s is exact and the
+ *   zero cell rows add exact zeros to every sum).
+ * GDML_ERR_INVALID before any launch (ctx may be NULL for these checks): everything gdml_relax_run rejects; a NULL L0 (a
+ *   cell relaxation needs a lattice per geometry), Cc or output array; an L0 or C that is not finite or singular (|det| at
+ *   most 1e-12 of the cube of its largest entry); mask entries other than 0 and 1 or an asymmetric mask; cell_factor <= 0 or
+ *   not finite; a non-finite pressure.  GDML_ERR_STATE without a model.
+ * Not offered: hydrostatic-only and constant-volume modes, the exponential (Frechet) cell parametrisation, L-BFGS, NPT. */
+typedef struct gdml_cell_relax_params {
+  int64_t B;
+  int N;
+  double f_scale;        /* g = f_scale * F', T = f_scale * W' + pressure Vol */
+  double fmax;           /* converged when the largest |G_row| is below it */
+  double dt_max, max_step;
+  double f_inc, f_dec, alpha_start, f_alpha;
+  int64_t n_min;
+  double pressure;       /* in units of (f_scale E') per length^3 */
+  double cell_factor;    /* C = cell_factor Fd */
+  const double* mask;    /* (3,3) of 0/1, symmetric; NULL = all ones */
+} gdml_cell_relax_params; /* 112 bytes */
+int gdml_cell_relax_run(gdml_ctx* ctx, const gdml_cell_relax_params* params, double* S, double* Cc, const double* L0, double* V,
+                        double* dt, double* alpha, int64_t* n_pos, int64_t* n_taken, int64_t max_steps, int64_t record_every,
+                        double* R_rec, double* lat_rec, double* E_hist, double* vol_hist, double* fmax_hist, double* R_end,
+                        double* lat_end, double* E_end, double* F_end, double* W_end, double* vol_end, int64_t* status,
+                        int64_t* first_bad_step);
+
 /* Analytic Hessians (force constants) H' = d^2 E' / dR^2 of B geometries, unscaled like gdml_predict (the caller
  * multiplies by std).  The reference has no counterpart: its users take finite differences of predict().
  * With the predictor's per-row quantities (d = x - X_rho, n = sqrt5 |d|, b = 5/(3 sig^3) exp(-n/sig), a = d . v_rho,

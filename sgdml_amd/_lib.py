@@ -40,6 +40,14 @@ class RelaxParams(C.Structure):
                 ('alpha_start', C.c_double), ('f_alpha', C.c_double), ('n_min', C.c_int64)]
 
 
+class CellRelaxParams(C.Structure):
+    """gdml_cell_relax_params (include/gdml_hip.h)."""
+    _fields_ = [('B', C.c_int64), ('N', C.c_int), ('f_scale', C.c_double), ('fmax', C.c_double), ('dt_max', C.c_double),
+                ('max_step', C.c_double), ('f_inc', C.c_double), ('f_dec', C.c_double), ('alpha_start', C.c_double),
+                ('f_alpha', C.c_double), ('n_min', C.c_int64), ('pressure', C.c_double), ('cell_factor', C.c_double),
+                ('mask', _vp)]
+
+
 class NebParams(C.Structure):
     """gdml_neb_params (include/gdml_hip.h)."""
     _fields_ = [('B', C.c_int64), ('N', C.c_int), ('P', C.c_int), ('f_scale', C.c_double), ('lat', _vp), ('lat_inv', _vp),
@@ -99,6 +107,10 @@ SIGNATURES = {
                                _vp, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_virial': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_virial_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_predict_virial_cells': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_predict_virial_cells_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_cell_relax_run': (C.c_int, [_vp, C.POINTER(CellRelaxParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64,
+                                      C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_sym_eig': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
@@ -797,6 +809,83 @@ class Context(object):
         lat, lat_inv = _lat_pair(lat_and_inv)
         self._check(self._lib.gdml_predict_virial_dev(self._h, R_dev, int(B), _ptr(lat), _ptr(lat_inv), E_dev, F_dev,
                                                       W_dev))
+
+    def predict_cells(self, R, lats, lat_invs, return_E=True, virial=True):
+        """gdml_predict_virial_cells: unscaled E' (B,) or None, F (B,3N) and, with virial, W (B,3,3) (else None) of geometries R
+        (B,3N), geometry b in lattice lats[b] with inverse lat_invs[b] (B,3,3; cell vectors in the columns).  Batches beyond
+        max_query_batch go through in slices, as in predict()."""
+        if R is None:
+            raise ValueError('per-geometry lattices need geometries (there is no training-set mode)')
+        n3 = 3 * self.model_n_atoms
+        R = f64(R).reshape(-1, n3)
+        B = R.shape[0]
+        lats, lat_invs = f64(lats), f64(lat_invs)
+        if lats.shape != (B, 3, 3) or lat_invs.shape != (B, 3, 3):
+            raise ValueError('lattices and inverses must be ({}, 3, 3), got {} and {}'.format(B, lats.shape, lat_invs.shape))
+        E = np.empty(B) if return_E else None
+        F = np.empty((B, n3))
+        W = np.empty((B, 3, 3)) if virial else None
+        for b0 in range(0, max(B, 1), self.max_query_batch):
+            b1 = min(B, b0 + self.max_query_batch)
+            self._check(self._lib.gdml_predict_virial_cells(
+                self._h, _ptr(R[b0:b1]), b1 - b0, _ptr(lats[b0:b1]), _ptr(lat_invs[b0:b1]),
+                None if E is None else _ptr(E[b0:b1]), _ptr(F[b0:b1]), None if W is None else _ptr(W[b0:b1])))
+        return E, F, W
+
+    def predict_cells_dev(self, R_dev, B, lats_dev, lat_invs_dev, E_dev, F_dev, W_dev):
+        """gdml_predict_virial_cells_dev on device pointers (ints or c_void_p; E_dev / F_dev / W_dev may be None)."""
+        self._check(self._lib.gdml_predict_virial_cells_dev(self._h, R_dev, int(B), lats_dev, lat_invs_dev, E_dev, F_dev, W_dev))
+
+    def cell_relax_run(self, S, Cc, L0, fmax, max_steps, state, dt_max, pressure=0.0, cell_factor=1.0, mask=None, max_step=0.2,
+                       n_min=5, f_inc=1.1, f_dec=0.5, alpha_start=0.1, f_alpha=0.99, f_scale=1.0, record_every=0):
+        """gdml_cell_relax_run: B periodic geometries relax atoms and cell by FIRE on the device.  S (B,3N): reference positions,
+        Cc (B,3,3): cell_factor times the deformation gradient, L0 (B,3,3): reference lattices; state: dict with 'V' (B,3N+9),
+        'dt', 'alpha' (B), 'n_pos', 'n_taken' (B, int).  Returns a dict: 'S', 'C' (the end coordinates), 'R_end' (B,3N;
+        Cartesian), 'lat_end' (B,3,3), 'E_end', 'F_end', 'W_end' (unscaled), 'vol_end', the end 'state', 'status' (B,2),
+        'n_made', 'E_hist', 'vol_hist', 'fmax_hist' (n_made,B), the frames 'R', 'lat' (only with record_every > 0) and
+        'first_bad_step' (B)."""
+        n3a = 3 * self.model_n_atoms
+        S = np.array(S, dtype=np.float64, order='C').reshape(-1, n3a)
+        B = S.shape[0]
+        Cc, L0 = np.array(Cc, dtype=np.float64, order='C'), f64(L0)  # (order: a broadcast view would keep its strides)
+        if Cc.shape != (B, 3, 3) or L0.shape != (B, 3, 3):
+            raise ValueError('C and L0 must be ({}, 3, 3), got {} and {}'.format(B, Cc.shape, L0.shape))
+        V = np.array(state['V'], dtype=np.float64, order='C')
+        if V.shape != (B, n3a + 9):
+            raise ValueError("state['V'] must be ({}, {}), got {}".format(B, n3a + 9, V.shape))
+        dt, alpha = (np.array(state[k], dtype=np.float64).ravel() for k in ('dt', 'alpha'))
+        n_pos, n_taken = (np.array(state[k], dtype=np.int64).ravel() for k in ('n_pos', 'n_taken'))
+        for k, a in (('dt', dt), ('alpha', alpha), ('n_pos', n_pos), ('n_taken', n_taken)):
+            if a.shape != (B,):
+                raise ValueError("state['{}'] must have one entry per geometry ({}), got shape {}".format(k, B, a.shape))
+        mask = None if mask is None else f64(mask)
+        if mask is not None and mask.shape != (3, 3):
+            raise ValueError('mask must be 3 x 3, got shape {}'.format(mask.shape))
+        max_steps, record_every = int(max_steps), int(record_every)
+        n_eval = max(max_steps, 0) + 1
+        n_rec = max(max_steps, 0) // record_every + 1 if record_every > 0 else 0
+        R_rec = np.empty((n_rec, B, n3a)) if record_every > 0 else None
+        lat_rec = np.empty((n_rec, B, 3, 3)) if record_every > 0 else None
+        E_hist, v_hist, f_hist = np.empty((n_eval, B)), np.empty((n_eval, B)), np.empty((n_eval, B))
+        R_end, lat_end = np.empty((B, n3a)), np.empty((B, 3, 3))
+        E_end, F_end, W_end, vol_end = np.empty(B), np.empty((B, n3a)), np.empty((B, 3, 3)), np.empty(B)
+        status = np.full((B, 2), -1, dtype=np.int64)
+        bad = np.full(B, -1, dtype=np.int64)
+        prm = CellRelaxParams(B, self.model_n_atoms, float(f_scale), float(fmax), float(dt_max), float(max_step), float(f_inc),
+                              float(f_dec), float(alpha_start), float(f_alpha), int(n_min), float(pressure), float(cell_factor),
+                              _ptr(mask))
+        self._check(self._lib.gdml_cell_relax_run(
+            self._h, C.byref(prm), _ptr(S), _ptr(Cc), _ptr(L0), _ptr(V), _ptr(dt), _ptr(alpha), _ptr(n_pos), _ptr(n_taken),
+            max_steps, record_every, _ptr(R_rec), _ptr(lat_rec), _ptr(E_hist), _ptr(v_hist), _ptr(f_hist), _ptr(R_end),
+            _ptr(lat_end), _ptr(E_end), _ptr(F_end), _ptr(W_end), _ptr(vol_end), _ptr(status), _ptr(bad)))
+        n_made = int(status[:, 1].max()) + 1 if B and (status[:, 1] >= 0).all() else 0
+        out = dict(S=S, C=Cc, R_end=R_end, lat_end=lat_end, E_end=E_end, F_end=F_end, W_end=W_end, vol_end=vol_end, status=status,
+                   first_bad_step=bad, n_made=n_made, E_hist=E_hist[:n_made], vol_hist=v_hist[:n_made], fmax_hist=f_hist[:n_made],
+                   state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken))
+        if record_every > 0:
+            n = (n_made + record_every - 1) // record_every
+            out['R'], out['lat'] = R_rec[:n], lat_rec[:n]
+        return out
 
     def hessian_batch(self):
         """Geometries per gdml_predict_hessian call: max_query_batch scaled down by the 3N-fold larger output (9N^2 vs 3N)."""

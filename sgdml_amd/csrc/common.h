@@ -285,6 +285,8 @@ __device__ __forceinline__ double wave_sum(double v) {
 // internal cross-TU entry points
 int desc_device(gdml_ctx* ctx, const double* d_R, int64_t M, int N, const double* lat,
                 const double* lat_inv, double* d_x, double* d_g);
+int desc_cells_device(gdml_ctx* ctx, const double* d_R, int64_t M, int N, const double* d_lats, const double* d_invs,
+                      double* d_x, double* d_g);  // a lattice per geometry, (M,3,3) in device memory
 int predict_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B, double* d_E,
                    double* d_F);
 int hess_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B, double* d_E, double* d_F,

@@ -36,6 +36,47 @@ __global__ void __launch_bounds__(256) desc_kernel(const double* __restrict__ R,
   g[t * 3 + 2] = d2 * inv3;
 }
 
+// desc_kernel with a lattice per geometry: geometry m reads lats[m] and invs[m] (3 x 3 row-major, cell vectors in the
+// columns) from device memory.  Everything else -- thread layout, pair order, the arithmetic -- is desc_kernel's, whose
+// text stays as it was: the minimum-image expression is a copy with desc_kernel's rounding points written out, so that equal
+// lattices give equal bits (tests/test_cells_gpu.py holds the two kernels to that).
+__global__ void __launch_bounds__(256) desc_cells_kernel(const double* __restrict__ R, int64_t M, int N, int D,
+                                                         const double* __restrict__ lats, const double* __restrict__ invs,
+                                                         double* __restrict__ x, double* __restrict__ g) {
+  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= M * (int64_t)D) return;
+  int64_t m = t / D;
+  int k = (int)(t - m * D);
+  int i = (int)((1.0 + sqrt(1.0 + 8.0 * (double)k)) * 0.5);
+  while (i * (i - 1) / 2 > k) --i;
+  while ((i + 1) * i / 2 <= k) ++i;
+  int j = k - i * (i - 1) / 2;
+  const double* ri = R + (m * N + i) * 3;
+  const double* rj = R + (m * N + j) * 3;
+  double d0 = ri[0] - rj[0], d1 = ri[1] - rj[1], d2 = ri[2] - rj[2];
+  const double* lat = lats + m * 9;
+  const double* inv = invs + m * 9;
+  double dist;
+  {
+    // desc_kernel's sums a0 b0 + a1 b1 + a2 b2 as the compiler fuses them there: a1 b1 rounded, then a0 b0 and a2 b2 fused in
+    // (for |d|^2: d0 d0 rounded, then d1 d1 and d2 d2).  Left to the compiler, this kernel's |d|^2 came out in another order
+    // -- one bit in the last place of x and g -- so the fused multiply-adds are written out and contraction is switched off.
+#pragma clang fp contract(off)
+    double c0 = rint(fma(inv[2], d2, fma(inv[0], d0, inv[1] * d1)));
+    double c1 = rint(fma(inv[5], d2, fma(inv[3], d0, inv[4] * d1)));
+    double c2 = rint(fma(inv[8], d2, fma(inv[6], d0, inv[7] * d1)));
+    d0 -= fma(lat[2], c2, fma(lat[0], c0, lat[1] * c1));
+    d1 -= fma(lat[5], c2, fma(lat[3], c0, lat[4] * c1));
+    d2 -= fma(lat[8], c2, fma(lat[6], c0, lat[7] * c1));
+    dist = sqrt(fma(d2, d2, fma(d1, d1, d0 * d0)));
+  }
+  double inv3 = 1.0 / (dist * dist * dist);
+  x[t] = 1.0 / dist;
+  g[t * 3 + 0] = d0 * inv3;
+  g[t * 3 + 1] = d1 * inv3;
+  g[t * 3 + 2] = d2 * inv3;
+}
+
 int desc_device(gdml_ctx* ctx, const double* d_R, int64_t M, int N, const double* lat,
                 const double* lat_inv, double* d_x, double* d_g) {
   Lattice L;
@@ -50,6 +91,19 @@ int desc_device(gdml_ctx* ctx, const double* d_R, int64_t M, int N, const double
   if (total == 0) return GDML_OK;
   hipLaunchKernelGGL(desc_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, ctx->stream, d_R, M, N,
                      D, L, d_x, d_g);
+  ctx->launch_counter++;
+  HIP_CHECK(ctx, hipGetLastError());
+  return GDML_OK;
+}
+
+// d_lats, d_invs: (M,3,3) in device memory, one lattice and inverse per geometry
+int desc_cells_device(gdml_ctx* ctx, const double* d_R, int64_t M, int N, const double* d_lats, const double* d_invs,
+                      double* d_x, double* d_g) {
+  int D = N * (N - 1) / 2;
+  int64_t total = M * (int64_t)D;
+  if (total == 0) return GDML_OK;
+  hipLaunchKernelGGL(desc_cells_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, ctx->stream, d_R, M, N, D, d_lats, d_invs,
+                     d_x, d_g);
   ctx->launch_counter++;
   HIP_CHECK(ctx, hipGetLastError());
   return GDML_OK;

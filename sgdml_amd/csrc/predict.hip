@@ -1316,9 +1316,13 @@ static int predict_fused(gdml_ctx* ctx, const double* R, int64_t B, const double
 }
 
 // W_out != nullptr: gdml_predict_virial (R given; E_out and F_out may be NULL).  W_out == nullptr: gdml_predict, as ever.
+// lats / lat_invs != nullptr (gdml_predict_virial_cells): a lattice per geometry, (B,3,3), where R is (host or device);
+// lat / lat_inv are then not used.  Such a call always takes the general route: the single launch holds ONE Lattice by value
+// (FusedModel, fused_core.h).  Staging and everything behind the descriptors are those of the one-lattice call.
 static int predict_common(gdml_ctx* ctx, const double* R, bool R_on_device, int64_t B,
                           const double* lat, const double* lat_inv, double* E_out, double* F_out,
-                          bool out_on_device, double* W_out = nullptr) {
+                          bool out_on_device, double* W_out = nullptr, const double* lats = nullptr,
+                          const double* lat_invs = nullptr) {
   Model& md = ctx->model;
   if (!md.xp) return gdml_fail(ctx, GDML_ERR_STATE, "gdml_predict: upload a model first");
   if (!F_out && !W_out) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict: F_out is NULL");
@@ -1326,7 +1330,7 @@ static int predict_common(gdml_ctx* ctx, const double* R, bool R_on_device, int6
     return gdml_fail(ctx, GDML_ERR_INVALID, "lattice and inverse must both be given or both NULL");
   HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const int N = md.N, D = md.D;
-  if (R != nullptr && !R_on_device && !out_on_device && B >= 1 && B <= FUSED_MAX_Q) {
+  if (R != nullptr && !lats && !R_on_device && !out_on_device && B >= 1 && B <= FUSED_MAX_Q) {
     int done = 0;
     GDML_TRY(predict_fused(ctx, R, B, lat, lat_inv, E_out, F_out, W_out, &done));
     if (done) return GDML_OK;
@@ -1354,7 +1358,8 @@ static int predict_common(gdml_ctx* ctx, const double* R, bool R_on_device, int6
     if (B == 0) return GDML_OK;
     const int64_t nW = W_out ? B * 9 : 0;  // W follows E and F in the work buffer and in the pinned block
     int64_t nR = B * N * 3, nx = B * (int64_t)D, ng = nx * 3, nout = out_on_device ? 0 : B + nR + nW;
-    GDML_TRY(ctx_scratch(ctx, (nR + nx + ng + nout) * 8, &buf));
+    const int64_t nL = lats && !R_on_device ? B * 18 : 0;  // host lattices and inverses are staged behind everything else
+    GDML_TRY(ctx_scratch(ctx, (nR + nx + ng + nout + nL) * 8, &buf));
     double* d_R = buf;
     double* dx = buf + nR;
     double* dg = dx + nx;
@@ -1395,8 +1400,19 @@ static int predict_common(gdml_ctx* ctx, const double* R, bool R_on_device, int6
       d_F = d_E + B;
       if (W_out) d_W = d_F + nR;
     }
+    const double *d_lats = lats, *d_invs = lat_invs;
+    if (nL) {
+      double* dl = dg + ng + nout;
+      HIP_CHECK(ctx, hipMemcpyAsync(dl, lats, B * 9 * 8, hipMemcpyHostToDevice, ctx->stream));
+      HIP_CHECK(ctx, hipMemcpyAsync(dl + B * 9, lat_invs, B * 9 * 8, hipMemcpyHostToDevice, ctx->stream));
+      d_lats = dl;
+      d_invs = dl + B * 9;
+    }
     phase_begin(ctx);
-    GDML_TRY(desc_device(ctx, R_on_device ? R : d_R, B, N, lat, lat_inv, dx, dg));
+    if (lats)
+      GDML_TRY(desc_cells_device(ctx, R_on_device ? R : d_R, B, N, d_lats, d_invs, dx, dg));
+    else
+      GDML_TRY(desc_device(ctx, R_on_device ? R : d_R, B, N, lat, lat_inv, dx, dg));
     d_xq = dx;
     d_gq = dg;
   }
@@ -1435,6 +1451,23 @@ extern "C" int gdml_predict_virial_dev(gdml_ctx* ctx, const double* R_dev, int64
   if (!R_dev) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_virial_dev: R_dev is NULL");
   if (!W_dev) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_virial_dev: W_dev is NULL");
   return predict_common(ctx, R_dev, true, B, lat, lat_inv, E_dev, F_dev, true, W_dev);
+}
+
+extern "C" int gdml_predict_virial_cells(gdml_ctx* ctx, const double* R, int64_t B, const double* lats, const double* lat_invs,
+                                         double* E_out, double* F_out, double* W_out) {
+  if (!ctx) return GDML_ERR_INVALID;
+  if (!R) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_virial_cells: R is NULL (there is no training-set mode)");
+  if (!lats || !lat_invs) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_virial_cells: lats or lat_invs is NULL");
+  return predict_common(ctx, R, false, B, nullptr, nullptr, E_out, F_out, false, W_out, lats, lat_invs);
+}
+
+extern "C" int gdml_predict_virial_cells_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, const double* lats_dev,
+                                             const double* lat_invs_dev, double* E_dev, double* F_dev, double* W_dev) {
+  if (!ctx) return GDML_ERR_INVALID;
+  if (!R_dev) return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_virial_cells_dev: R_dev is NULL");
+  if (!lats_dev || !lat_invs_dev)
+    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_predict_virial_cells_dev: lats_dev or lat_invs_dev is NULL");
+  return predict_common(ctx, R_dev, true, B, nullptr, nullptr, E_dev, F_dev, true, W_dev, lats_dev, lat_invs_dev);
 }
 
 extern "C" int gdml_predict(gdml_ctx* ctx, const double* R, int64_t B, const double* lat,

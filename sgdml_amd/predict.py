@@ -357,6 +357,38 @@ class GDMLPredict(object):
             return self.lat_and_inv  # the model's own cell: its stored inverse, hence the bits of the default
         return lat_and_inv
 
+    @staticmethod
+    def _lats_and_invs(lattices, B, lattice=None):
+        """Per-geometry lattices (B,3,3), cell vectors in the columns, and their inverses: each member validated like a
+        per-call lattice (check_lattice); mutually exclusive with lattice=."""
+        if lattice is not None:
+            raise ValueError('give either lattice (one for the call) or lattices (one per geometry), not both')
+        lats = np.array(lattices, dtype=np.float64)
+        if lats.shape != (B, 3, 3):
+            raise ValueError('lattices must be ({}, 3, 3), one 3 x 3 matrix per geometry, got shape {}'.format(B, lats.shape))
+        invs = np.empty_like(lats)
+        for b in range(B):
+            try:
+                invs[b] = check_lattice(lats[b])[1]
+            except ValueError as e:
+                raise ValueError('lattices[{}]: {}'.format(b, e))
+        return lats, invs
+
+    def _cells(self, R, lattices, lattice, return_E=True, virial=True):
+        """Unscaled (E, F, W, lattices) of geometries R with one lattice each (gdml_predict_virial_cells)."""
+        if R is None:
+            raise ValueError('per-geometry lattices need geometries R (there is no training-set mode)')
+        R = np.asarray(R, dtype=np.float64)
+        if R.ndim == 1:
+            R = R[None, :]
+        R = R.reshape(R.shape[0], -1)
+        lats, invs = self._lats_and_invs(lattices, R.shape[0], lattice)
+        parts = self._sharded(R.shape[0], lambda ctx, lo, hi: ctx.predict_cells(R[lo:hi], lats[lo:hi], invs[lo:hi],
+                                                                                return_E=return_E, virial=virial))
+        E, F, W = (parts[0] if len(parts) == 1 else
+                   [None if parts[0][i] is None else np.concatenate([p_[i] for p_ in parts]) for i in range(3)])
+        return E, F, W, lats
+
     def predict_hessian(self, R, lattice=None):
         """Energies (B,), forces (B,3N) and analytic Hessians d^2E/dR^2 (B,3N,3N) for geometries R (B,3N) or (3N,),
         scaled like predict() (E std + c, F std, H std).  No training-set mode: R is required.  lattice: as in predict()."""
@@ -378,12 +410,21 @@ class GDMLPredict(object):
 
     # ---- strain derivative and stress (gdml_predict_virial, csrc/predict.hip)
 
-    def predict_virial(self, R, lattice=None):
+    def predict_virial(self, R, lattice=None, lattices=None):
         """Energies (B,), forces (B,3N) and the strain derivative W = dE/d eps (B,3,3) for geometries R (B,3N) or (3N,): the
         change of the energy when atoms and cell are strained together, r -> (I + eps) r, lattice -> (I + eps) lattice.  E and
         F are those of predict(R, lattice=lattice), bit for bit; W is symmetric and scaled by std like F.  Works for
-        non-periodic models too (W = -sum_i f_i (x) r_i there).  lattice: as in predict().  No training-set mode."""
+        non-periodic models too (W = -sum_i f_i (x) r_i there).  lattice, lattices: as in predict().  No training-set mode."""
+        if lattices is not None:
+            return self._scaled(*self._cells(R, lattices, lattice)[:3])
         return self._virial(R, self._lat_and_inv(lattice))
+
+    def _scaled(self, E, F, W):
+        E *= self.std
+        E += self.c
+        F *= self.std
+        W *= self.std
+        return E, F, W
 
     def _virial(self, R, lat_and_inv):
         if R is None:
@@ -393,22 +434,23 @@ class GDMLPredict(object):
             R = R[None, :]
         R = R.reshape(R.shape[0], -1)
         parts = self._sharded(R.shape[0], lambda ctx, lo, hi: ctx.predict_virial(R[lo:hi], lat_and_inv))
-        E, F, W = (parts[0] if len(parts) == 1 else [np.concatenate([p_[i] for p_ in parts]) for i in range(3)])
-        E *= self.std
-        E += self.c
-        F *= self.std
-        W *= self.std
-        return E, F, W
+        return self._scaled(*(parts[0] if len(parts) == 1 else [np.concatenate([p_[i] for p_ in parts]) for i in range(3)]))
 
-    def predict_stress(self, R, lattice=None, voigt=False):
+    def predict_stress(self, R, lattice=None, voigt=False, lattices=None):
         """(E, F, S) with the stress S = W / |det lattice| (B,3,3) of predict_virial: +dE/d eps per volume, ASE's sign, in the
-        model's energy unit per length unit cubed.  voigt=True: S (B,6) in ASE's order xx, yy, zz, yz, xz, xy.  ValueError when
-        neither the model nor the call supplies a lattice (a volume)."""
-        lat_and_inv = self._lat_and_inv(lattice)
-        if lat_and_inv is None:
-            raise ValueError('predict_stress needs a lattice: the model has none and none was given')
-        E, F, W = self._virial(R, lat_and_inv)
-        W /= abs(det3(lat_and_inv[0]))
+        model's energy unit per length unit cubed.  voigt=True: S (B,6) in ASE's order xx, yy, zz, yz, xz, xy.  lattices: one
+        lattice per geometry as in predict(); each W is divided by its own geometry's volume.  ValueError when neither the
+        model nor the call supplies a lattice (a volume)."""
+        if lattices is not None:
+            E, F, W, lats = self._cells(R, lattices, lattice)
+            E, F, W = self._scaled(E, F, W)
+            W /= np.array([abs(det3(lat)) for lat in lats]).reshape(-1, 1, 1)
+        else:
+            lat_and_inv = self._lat_and_inv(lattice)
+            if lat_and_inv is None:
+                raise ValueError('predict_stress needs a lattice: the model has none and none was given')
+            E, F, W = self._virial(R, lat_and_inv)
+            W /= abs(det3(lat_and_inv[0]))
         if voigt:
             W = np.ascontiguousarray(W.reshape(-1, 9)[:, [0, 4, 8, 5, 2, 1]])
         return E, F, W
@@ -505,6 +547,92 @@ class GDMLPredict(object):
         for k in ('E_end', 'E_hist'):
             out[k] *= self.std
             out[k] += self.c
+        out['n_steps'] = status[:, 1].copy()
+        out['converged'] = status[:, 0] == 1
+        out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
+        return out
+
+    # ---- variable-cell relaxation on the device (gdml_cell_relax_run, csrc/cellrelax.hip)
+
+    def relax_cell(self, R0, fmax, lattice=None, lattices=None, pressure=0.0, mask=None, cell_factor=None, max_steps=1000,
+                   dt_start=0.1, dt_max=None, max_step=0.2, n_min=5, f_inc=1.1, f_dec=0.5, alpha_start=0.1, f_alpha=0.99,
+                   state=None, f_unit=1.0, record_every=0):
+        """Relax atoms AND cell of B independent periodic geometries on the device by FIRE, in the form of ASE's
+        FIRE(UnitCellFilter(atoms)): the enthalpy H = f_unit * E + pressure * volume is minimised over the atoms' reference
+        positions s and the deformation gradient Fd of the cell (positions Fd s, lattice Fd L0), one FIRE system of 3N + 9
+        coordinates (s, cell_factor * Fd) per geometry; the FIRE parameters are relax()'s.  R0: (B,3N) or (3N,).  lattice: one
+        3 x 3 start lattice (cell vectors in the columns) for all starts, default the model's; lattices: (B,3,3), one per
+        start.  pressure: in (f_unit * the model's energy unit) / length^3.  mask: symmetric 3 x 3 of 0/1, the strain components
+        that relax (default all; [[1,1,0],[1,1,0],[0,0,0]] relaxes a slab in its plane only).  cell_factor: default N, as in ASE.
+        A geometry is converged when the largest row norm of the generalised force -- the atoms' Fd^T g and the three rows of
+        -(mask o (f_unit W + pressure V I)) Fd^-T / cell_factor -- is below fmax.  state: the 'state' of an earlier call continues
+        that run bit for bit (R0 then only fixes the batch size; the lattice arguments are not used).
+        Returns a dict like relax()'s: 'R_end' (B,3N), 'lattice_end' (B,3,3), 'E_end', 'F_end' scaled like predict(),
+        'stress_end' (B,3,3; W / volume scaled by std, ASE's sign, WITHOUT the external pressure), 'vol_end' (B), 'fmax_end',
+        'n_steps', 'converged', 'E_hist', 'vol_hist', 'fmax_hist' (evaluations made, B), 'state', and with record_every > 0
+        the frames 'R' and 'lattice'.  Runs on the predictor's first device, always on the general prediction route.
+        Not offered: hydrostatic-only and constant-volume modes, the exponential cell parametrisation, L-BFGS, NPT dynamics.
+        ValueError before anything is launched; FloatingPointError naming geometry and evaluation when a value is not finite
+        (a cell that collapses to zero volume included)."""
+        n3 = 3 * self.n_atoms
+        R0 = _as_batch(R0, n3)
+        B = R0.shape[0]
+        if dt_max is None:
+            dt_max = 10.0 * dt_start
+        if cell_factor is None:
+            cell_factor = float(self.n_atoms)
+        _check_finite(('fmax', fmax), ('dt_start', dt_start), ('dt_max', dt_max), ('max_step', max_step), ('f_inc', f_inc),
+                      ('f_dec', f_dec), ('alpha_start', alpha_start), ('f_alpha', f_alpha), ('f_unit', f_unit),
+                      ('pressure', pressure), ('cell_factor', cell_factor))
+        if not cell_factor > 0.0:
+            raise ValueError('cell_factor must be positive')
+        if int(max_steps) != max_steps or int(record_every) != record_every or int(n_min) != n_min:
+            raise ValueError('max_steps, record_every and n_min must be integers')
+        if mask is not None:
+            mask = np.asarray(mask, dtype=np.float64)
+            if mask.shape != (3, 3) or not np.isin(mask, (0.0, 1.0)).all() or not np.array_equal(mask, mask.T):
+                raise ValueError('mask must be a symmetric 3 x 3 array of 0 and 1')
+        if state is None:
+            if lattices is not None:
+                L0 = self._lats_and_invs(lattices, B, lattice)[0]
+            else:
+                lat_and_inv = self._lat_and_inv(lattice)
+                if lat_and_inv is None:
+                    raise ValueError('relax_cell needs a lattice: the model has none and none was given')
+                L0 = np.broadcast_to(lat_and_inv[0], (B, 3, 3))
+            S, Cc = R0, np.broadcast_to(float(cell_factor) * np.eye(3), (B, 3, 3))
+            fire = dict(V=np.zeros((B, n3 + 9)), dt=np.full(B, float(dt_start)), alpha=np.full(B, float(alpha_start)),
+                        n_pos=np.zeros(B, dtype=np.int64), n_taken=np.zeros(B, dtype=np.int64))
+        else:
+            missing = [k for k in ('S', 'C', 'L0', 'V', 'dt', 'alpha', 'n_pos', 'n_taken') if k not in state]
+            if missing:
+                raise ValueError('state lacks {}'.format(missing))
+            for k, shp in (('S', (B, n3)), ('C', (B, 3, 3)), ('L0', (B, 3, 3)), ('V', (B, n3 + 9))):
+                if np.shape(state[k]) != shp:
+                    raise ValueError("state['{}'] must have shape {}, got {}".format(k, shp, np.shape(state[k])))
+            if not all(np.isfinite(np.asarray(state[k], dtype=np.float64)).all() for k in ('V', 'dt', 'alpha')):
+                raise ValueError('state must be finite')
+            S, Cc, L0, fire = state['S'], state['C'], state['L0'], state
+        # a NaN start is not a usage error: the run reports the geometry and the evaluation (FloatingPointError)
+        out = self._ctx.cell_relax_run(S, Cc, L0, fmax, max_steps, fire, dt_max, pressure=pressure, cell_factor=cell_factor,
+                                       mask=mask, max_step=max_step, n_min=n_min, f_inc=f_inc, f_dec=f_dec,
+                                       alpha_start=alpha_start, f_alpha=f_alpha, f_scale=self.std * float(f_unit),
+                                       record_every=record_every)
+        _raise_first_bad(out.pop('first_bad_step'), 'geometry', 'evaluation')
+        status = out.pop('status')
+        out.pop('n_made')
+        out['state'].update(S=out.pop('S'), C=out.pop('C'), L0=np.array(L0, dtype=np.float64))
+        out['lattice_end'] = out.pop('lat_end')
+        out['F_end'] *= self.std
+        W = out.pop('W_end')
+        W *= self.std
+        W /= out['vol_end'].reshape(-1, 1, 1)
+        out['stress_end'] = W
+        for k in ('E_end', 'E_hist'):
+            out[k] *= self.std
+            out[k] += self.c
+        if 'lat' in out:
+            out['lattice'] = out.pop('lat')
         out['n_steps'] = status[:, 1].copy()
         out['converged'] = status[:, 0] == 1
         out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
@@ -1367,11 +1495,16 @@ class GDMLPredict(object):
                 m['e_err'] = {'mae': np.nan, 'rmse': np.nan}
         return m
 
-    def predict(self, R=None, return_E=True, lattice=None):
+    def predict(self, R=None, return_E=True, lattice=None, lattices=None):
         """Energies (B,) and forces (B,3N) for geometries R (B,3N); R=None -> training-set mode.
         lattice: a 3 x 3 matrix with the cell vectors in its columns, used for THIS call instead of the model's (one lattice
-        per call; ValueError unless 3 x 3 and regular).  None: the model's lattice, or none."""
-        if R is not None:
+        per call; ValueError unless 3 x 3 and regular).  None: the model's lattice, or none.
+        lattices: (B,3,3), ONE LATTICE PER GEOMETRY (cell vectors in the columns), for B independent cells or the volumes of an
+        equation-of-state scan in one batch; mutually exclusive with lattice; each member is validated like lattice.  Such a
+        call takes the general prediction route for any B (the single launch holds one lattice)."""
+        if lattices is not None:
+            E, F, _, _ = self._cells(R, lattices, lattice, return_E=return_E, virial=False)
+        elif R is not None:
             R = np.asarray(R, dtype=np.float64)
             if R.ndim == 1:
                 R = R[None, :]
