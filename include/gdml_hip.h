@@ -192,8 +192,8 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *                         32 = always 32.  The results do not depend on it
  *   predict.relax_fused (1)       gdml_relax_run with 1-8 geometries of a molecule with D <= 256: one launch per evaluation (0: the
  *                         general route of two pieces per evaluation)
- *   predict.relax_chunk_steps (32)  evaluations gdml_relax_run (and gdml_neb_run, gdml_ef_run) queues between two
- *                         synchronisations (the host learns at a chunk's end which replicas froze); the results do not depend on it
+ *   predict.relax_chunk_steps (32)  evaluations gdml_relax_run (and gdml_neb_run, gdml_cell_relax_run, gdml_ef_run) queues between
+ *                         two synchronisations (the host learns at a chunk's end which replicas froze); the results do not depend on it
  *   predict.vib_chunk (0)         geometries per chunk of gdml_vib_run (0 = as many as keep its Hessians and work matrices under
  *                         256 MiB); steps b to d of that entry do not depend on it.  Also the geometries per slice of an
  *                         evaluation of gdml_ef_run

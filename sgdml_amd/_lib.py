@@ -259,6 +259,38 @@ def _recorded(rec):
     return {k: v for k, v in rec.items() if v is not None}
 
 
+def _replica_state(state, B, noun, f_keys=('dt', 'alpha'), i_keys=('n_pos', 'n_taken')):
+    """Fresh (B,) arrays of the per-replica entries of `state`, float64 for f_keys and int64 for i_keys, in that order (the
+    run-until-frozen entries overwrite them with the end state).  noun: what a replica is, for the message."""
+    arrays = [np.array(state[k], dtype=np.float64).ravel() for k in f_keys]
+    arrays += [np.array(state[k], dtype=np.int64).ravel() for k in i_keys]
+    for k, a in zip(f_keys + i_keys, arrays):
+        if a.shape != (B,):
+            raise ValueError("state['{}'] must have one entry per {} ({}), got shape {}".format(k, noun, B, a.shape))
+    return arrays
+
+
+def _frozen_arrays(B, max_steps, record_every, n_hist, frame_shapes):
+    """What every run-until-frozen entry fills: status (B,2) and first_bad_step (B) at -1, n_hist uninitialised histories
+    (max_steps + 1, B) and, per shape of frame_shapes, the frames (max_steps // record_every + 1, B) + shape (None without
+    record_every > 0)."""
+    n_eval = max(max_steps, 0) + 1
+    n_rec = max(max_steps, 0) // record_every + 1 if record_every > 0 else 0
+    hists = [np.empty((n_eval, B)) for _ in range(n_hist)]
+    frames = [np.empty((n_rec, B) + shp) if record_every > 0 else None for shp in frame_shapes]
+    return np.full((B, 2), -1, dtype=np.int64), np.full(B, -1, dtype=np.int64), hists, frames
+
+
+def _frozen_out(status, bad, record_every, hists, frames):
+    """The shared part of such an entry's result: 'status', 'first_bad_step', 'n_made' (evaluations made), the histories
+    (dict name -> array) cut to n_made rows and the recorded frames (dict name -> array or None) to those of n_made."""
+    n_made = int(status[:, 1].max()) + 1 if len(status) and (status[:, 1] >= 0).all() else 0
+    out = dict(status=status, first_bad_step=bad, n_made=n_made)
+    out.update((k, h[:n_made]) for k, h in hists.items())
+    out.update((k, f[:(n_made + record_every - 1) // record_every]) for k, f in frames.items() if f is not None)
+    return out
+
+
 def _digest(a):
     """Content fingerprint of a contiguous array (xxhash when present, else md5)."""
     try:
@@ -715,31 +747,18 @@ class Context(object):
         n3 = 3 * self.model_n_atoms
         R, V = _state_copies(R, state['V'], (-1, n3))
         B = R.shape[0]
-        dt, alpha = (np.array(state[k], dtype=np.float64).ravel() for k in ('dt', 'alpha'))
-        n_pos, n_taken = (np.array(state[k], dtype=np.int64).ravel() for k in ('n_pos', 'n_taken'))
-        for k, a in (('dt', dt), ('alpha', alpha), ('n_pos', n_pos), ('n_taken', n_taken)):
-            if a.shape != (B,):
-                raise ValueError("state['{}'] must have one entry per geometry ({}), got shape {}".format(k, B, a.shape))
+        dt, alpha, n_pos, n_taken = _replica_state(state, B, 'geometry')
         lat, lat_inv = _lat_pair(lat_and_inv)
         max_steps, record_every = int(max_steps), int(record_every)
-        n_eval = max(max_steps, 0) + 1
-        R_rec = np.empty((max(max_steps, 0) // record_every + 1, B, n3)) if record_every > 0 else None
-        E_hist, f_hist = np.empty((n_eval, B)), np.empty((n_eval, B))
+        status, bad, (E_hist, f_hist), (R_rec,) = _frozen_arrays(B, max_steps, record_every, 2, [(n3,)])
         E_end, F_end = np.empty(B), np.empty((B, n3))
-        status = np.full((B, 2), -1, dtype=np.int64)
-        bad = np.full(B, -1, dtype=np.int64)
         prm = RelaxParams(B, self.model_n_atoms, float(f_scale), _ptr(lat), _ptr(lat_inv), float(fmax), float(dt_max),
                           float(max_step), float(f_inc), float(f_dec), float(alpha_start), float(f_alpha), int(n_min))
         self._check(self._lib.gdml_relax_run(self._h, C.byref(prm), _ptr(R), _ptr(V), _ptr(dt), _ptr(alpha), _ptr(n_pos),
                                              _ptr(n_taken), max_steps, record_every, _ptr(R_rec), _ptr(E_hist), _ptr(f_hist),
                                              _ptr(E_end), _ptr(F_end), _ptr(status), _ptr(bad)))
-        n_made = int(status[:, 1].max()) + 1 if B and (status[:, 1] >= 0).all() else 0
-        out = dict(R_end=R, E_end=E_end, F_end=F_end, status=status, first_bad_step=bad, n_made=n_made,
-                   E_hist=E_hist[:n_made], fmax_hist=f_hist[:n_made],
-                   state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken))
-        if R_rec is not None:
-            out['R'] = R_rec[:(n_made + record_every - 1) // record_every]
-        return out
+        return dict(R_end=R, E_end=E_end, F_end=F_end, state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken),
+                    **_frozen_out(status, bad, record_every, dict(E_hist=E_hist, fmax_hist=f_hist), dict(R=R_rec)))
 
     def neb_run(self, R, fmax, k_spring, max_steps, state, dt_max, climb=False, max_step=0.2, n_min=5, f_inc=1.1, f_dec=0.5,
                 alpha_start=0.1, f_alpha=0.99, f_scale=1.0, record_every=0, lat_and_inv=None):
@@ -758,21 +777,13 @@ class Context(object):
         if P >= 1:
             V[:, 0] = 0.0
             V[:, -1] = 0.0
-        dt, alpha = (np.array(state[k], dtype=np.float64).ravel() for k in ('dt', 'alpha'))
-        n_pos, n_taken = (np.array(state[k], dtype=np.int64).ravel() for k in ('n_pos', 'n_taken'))
-        for k, a in (('dt', dt), ('alpha', alpha), ('n_pos', n_pos), ('n_taken', n_taken)):
-            if a.shape != (B,):
-                raise ValueError("state['{}'] must have one entry per band ({}), got shape {}".format(k, B, a.shape))
+        dt, alpha, n_pos, n_taken = _replica_state(state, B, 'band')
         lat, lat_inv = _lat_pair(lat_and_inv)
         max_steps, record_every = int(max_steps), int(record_every)
-        n_eval = max(max_steps, 0) + 1
-        R_rec = np.empty((max(max_steps, 0) // record_every + 1, B, P, n3)) if record_every > 0 else None
-        E_hist, f_hist = np.empty((n_eval, B)), np.empty((n_eval, B))
+        status, bad, (E_hist, f_hist), (R_rec,) = _frozen_arrays(B, max_steps, record_every, 2, [(P, n3)])
         E_end, F_end = np.zeros((B, P)), np.zeros((B, P, n3))
         s, f_tan = np.zeros((B, P)), np.zeros((B, P))
         i_climb = np.zeros(B, dtype=np.int64)
-        status = np.full((B, 2), -1, dtype=np.int64)
-        bad = np.full(B, -1, dtype=np.int64)
         prm = NebParams(B, self.model_n_atoms, P, float(f_scale), _ptr(lat), _ptr(lat_inv), float(fmax), float(dt_max),
                         float(max_step), float(f_inc), float(f_dec), float(alpha_start), float(f_alpha), int(n_min),
                         float(k_spring), int(bool(climb)))
@@ -780,13 +791,9 @@ class Context(object):
                                            _ptr(n_taken), max_steps, record_every, _ptr(R_rec), _ptr(E_hist), _ptr(f_hist),
                                            _ptr(E_end), _ptr(F_end), _ptr(i_climb), _ptr(s), _ptr(f_tan), _ptr(status),
                                            _ptr(bad)))
-        n_made = int(status[:, 1].max()) + 1 if B and (status[:, 1] >= 0).all() else 0
-        out = dict(R_end=R, E_end=E_end, F_end=F_end, i_climb=i_climb, s=s, f_tangent=f_tan, status=status, first_bad_step=bad,
-                   n_made=n_made, Emax_hist=E_hist[:n_made], fmax_hist=f_hist[:n_made],
-                   state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken))
-        if R_rec is not None:
-            out['R'] = R_rec[:(n_made + record_every - 1) // record_every]
-        return out
+        return dict(R_end=R, E_end=E_end, F_end=F_end, i_climb=i_climb, s=s, f_tangent=f_tan,
+                    state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken),
+                    **_frozen_out(status, bad, record_every, dict(Emax_hist=E_hist, fmax_hist=f_hist), dict(R=R_rec)))
 
     def predict_virial(self, R, lat_and_inv=None):
         """Unscaled E' (B,), F (B,3N) and strain derivative W = dE'/d eps (B,3,3) of geometries R (B,3N) (gdml_predict_virial);
@@ -853,24 +860,15 @@ class Context(object):
         V = np.array(state['V'], dtype=np.float64, order='C')
         if V.shape != (B, n3a + 9):
             raise ValueError("state['V'] must be ({}, {}), got {}".format(B, n3a + 9, V.shape))
-        dt, alpha = (np.array(state[k], dtype=np.float64).ravel() for k in ('dt', 'alpha'))
-        n_pos, n_taken = (np.array(state[k], dtype=np.int64).ravel() for k in ('n_pos', 'n_taken'))
-        for k, a in (('dt', dt), ('alpha', alpha), ('n_pos', n_pos), ('n_taken', n_taken)):
-            if a.shape != (B,):
-                raise ValueError("state['{}'] must have one entry per geometry ({}), got shape {}".format(k, B, a.shape))
+        dt, alpha, n_pos, n_taken = _replica_state(state, B, 'geometry')
         mask = None if mask is None else f64(mask)
         if mask is not None and mask.shape != (3, 3):
             raise ValueError('mask must be 3 x 3, got shape {}'.format(mask.shape))
         max_steps, record_every = int(max_steps), int(record_every)
-        n_eval = max(max_steps, 0) + 1
-        n_rec = max(max_steps, 0) // record_every + 1 if record_every > 0 else 0
-        R_rec = np.empty((n_rec, B, n3a)) if record_every > 0 else None
-        lat_rec = np.empty((n_rec, B, 3, 3)) if record_every > 0 else None
-        E_hist, v_hist, f_hist = np.empty((n_eval, B)), np.empty((n_eval, B)), np.empty((n_eval, B))
+        status, bad, (E_hist, v_hist, f_hist), (R_rec, lat_rec) = _frozen_arrays(B, max_steps, record_every, 3,
+                                                                                 [(n3a,), (3, 3)])
         R_end, lat_end = np.empty((B, n3a)), np.empty((B, 3, 3))
         E_end, F_end, W_end, vol_end = np.empty(B), np.empty((B, n3a)), np.empty((B, 3, 3)), np.empty(B)
-        status = np.full((B, 2), -1, dtype=np.int64)
-        bad = np.full(B, -1, dtype=np.int64)
         prm = CellRelaxParams(B, self.model_n_atoms, float(f_scale), float(fmax), float(dt_max), float(max_step), float(f_inc),
                               float(f_dec), float(alpha_start), float(f_alpha), int(n_min), float(pressure), float(cell_factor),
                               _ptr(mask))
@@ -878,14 +876,10 @@ class Context(object):
             self._h, C.byref(prm), _ptr(S), _ptr(Cc), _ptr(L0), _ptr(V), _ptr(dt), _ptr(alpha), _ptr(n_pos), _ptr(n_taken),
             max_steps, record_every, _ptr(R_rec), _ptr(lat_rec), _ptr(E_hist), _ptr(v_hist), _ptr(f_hist), _ptr(R_end),
             _ptr(lat_end), _ptr(E_end), _ptr(F_end), _ptr(W_end), _ptr(vol_end), _ptr(status), _ptr(bad)))
-        n_made = int(status[:, 1].max()) + 1 if B and (status[:, 1] >= 0).all() else 0
-        out = dict(S=S, C=Cc, R_end=R_end, lat_end=lat_end, E_end=E_end, F_end=F_end, W_end=W_end, vol_end=vol_end, status=status,
-                   first_bad_step=bad, n_made=n_made, E_hist=E_hist[:n_made], vol_hist=v_hist[:n_made], fmax_hist=f_hist[:n_made],
-                   state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken))
-        if record_every > 0:
-            n = (n_made + record_every - 1) // record_every
-            out['R'], out['lat'] = R_rec[:n], lat_rec[:n]
-        return out
+        return dict(S=S, C=Cc, R_end=R_end, lat_end=lat_end, E_end=E_end, F_end=F_end, W_end=W_end, vol_end=vol_end,
+                    state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken),
+                    **_frozen_out(status, bad, record_every, dict(E_hist=E_hist, vol_hist=v_hist, fmax_hist=f_hist),
+                                  dict(R=R_rec, lat=lat_rec)))
 
     def hessian_batch(self):
         """Geometries per gdml_predict_hessian call: max_query_batch scaled down by the 3N-fold larger output (9N^2 vs 3N)."""
@@ -959,11 +953,7 @@ class Context(object):
         n3 = 3 * self.model_n_atoms
         R = np.array(R, dtype=np.float64).reshape(-1, n3)
         B = R.shape[0]
-        trust, E_prev, dE_pred = (np.array(state[k], dtype=np.float64).ravel() for k in ('trust', 'E_prev', 'dE_pred'))
-        flags = np.array(state['flags'], dtype=np.int64).ravel()
-        for k, a in (('trust', trust), ('E_prev', E_prev), ('dE_pred', dE_pred), ('flags', flags)):
-            if a.shape != (B,):
-                raise ValueError("state['{}'] must have one entry per geometry ({}), got shape {}".format(k, B, a.shape))
+        trust, E_prev, dE_pred, flags = _replica_state(state, B, 'geometry', ('trust', 'E_prev', 'dE_pred'), ('flags',))
         t = state.get('t')
         if t is not None:
             t = np.array(t, dtype=np.float64)
@@ -971,28 +961,20 @@ class Context(object):
                 raise ValueError("state['t'] must have the shape of R {}, got {}".format(R.shape, t.shape))
         lat, lat_inv = _lat_pair(lat_and_inv)
         max_steps, record_every = int(max_steps), int(record_every)
-        n_eval = max(max_steps, 0) + 1
-        R_rec = np.empty((max(max_steps, 0) // record_every + 1, B, n3)) if record_every > 0 else None
-        E_hist, f_hist, w_hist = np.empty((n_eval, B)), np.empty((n_eval, B)), np.empty((n_eval, B))
-        k_hist = np.zeros((n_eval, B), dtype=np.int64)
+        status, bad, (E_hist, f_hist, w_hist), (R_rec,) = _frozen_arrays(B, max_steps, record_every, 3, [(n3,)])
+        k_hist = np.zeros(E_hist.shape, dtype=np.int64)
         E_end, F_end, w_end, mode_end = np.empty(B), np.empty((B, n3)), np.empty((B, n3)), np.empty((B, n3))
         n_rigid, n_neg = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
-        status = np.full((B, 2), -1, dtype=np.int64)
-        bad = np.full(B, -1, dtype=np.int64)
         prm = EfParams(B, self.model_n_atoms, int(order), float(f_scale), _ptr(lat), _ptr(lat_inv), float(fmax), float(trust_min),
                        float(trust_max), int(project))
         self._check(self._lib.gdml_ef_run(self._h, C.byref(prm), _ptr(R), _ptr(trust), _ptr(E_prev), _ptr(dE_pred), _ptr(flags),
                                           _ptr(t), max_steps, record_every, _ptr(R_rec), _ptr(E_hist), _ptr(f_hist), _ptr(w_hist),
                                           _ptr(k_hist), _ptr(E_end), _ptr(F_end), _ptr(w_end), _ptr(n_rigid), _ptr(n_neg),
                                           _ptr(mode_end), _ptr(status), _ptr(bad)))
-        n_made = int(status[:, 1].max()) + 1 if B and (status[:, 1] >= 0).all() else 0
-        out = dict(R_end=R, E_end=E_end, F_end=F_end, w_end=w_end, n_rigid=n_rigid, n_neg=n_neg, mode_end=mode_end, status=status,
-                   first_bad_step=bad, n_made=n_made, E_hist=E_hist[:n_made], fmax_hist=f_hist[:n_made],
-                   w_follow_hist=w_hist[:n_made], k_follow_hist=k_hist[:n_made],
-                   state=dict(trust=trust, E_prev=E_prev, dE_pred=dE_pred, flags=flags, t=t))
-        if R_rec is not None:
-            out['R'] = R_rec[:(n_made + record_every - 1) // record_every]
-        return out
+        return dict(R_end=R, E_end=E_end, F_end=F_end, w_end=w_end, n_rigid=n_rigid, n_neg=n_neg, mode_end=mode_end,
+                    state=dict(trust=trust, E_prev=E_prev, dE_pred=dE_pred, flags=flags, t=t),
+                    **_frozen_out(status, bad, record_every,
+                                  dict(E_hist=E_hist, fmax_hist=f_hist, w_follow_hist=w_hist, k_follow_hist=k_hist), dict(R=R_rec)))
 
     def uncert_prepare(self, sig, lam):
         """Factor A = -K + lam I of the resident training set and keep it for predict_cov (gdml_uncert_prepare).  Raises

@@ -162,12 +162,10 @@ extern "C" int gdml_cell_relax_run(gdml_ctx* ctx, const gdml_cell_relax_params* 
                                    double* W_end, double* vol_end, int64_t* status, int64_t* first_bad_step) {
   const char* fn = "gdml_cell_relax_run";
   if (!p) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: params is NULL", fn);
-  gdml_relax_params rp;
-  memset(&rp, 0, sizeof(rp));
-  rp.B = p->B; rp.N = p->N; rp.f_scale = p->f_scale; rp.fmax = p->fmax; rp.dt_max = p->dt_max; rp.max_step = p->max_step;
-  rp.f_inc = p->f_inc; rp.f_dec = p->f_dec; rp.alpha_start = p->alpha_start; rp.f_alpha = p->f_alpha; rp.n_min = p->n_min;
-  GDML_TRY(relax_check(ctx, fn, &rp, Sr, V, dt, alpha, n_pos, n_taken, max_steps, record_every, R_rec ? R_rec : lat_rec, E_hist,
-                       fmax_hist, E_end, F_end, status));
+  const FireParams fire = fire_params(*p);
+  const FireState h_fire = {dt, alpha, n_pos, n_taken};
+  GDML_TRY(relax_check(ctx, fn, p->B, p->N, p->f_scale, nullptr, nullptr, fire, Sr, V, h_fire, max_steps, record_every,
+                       R_rec ? R_rec : lat_rec, E_hist, fmax_hist, E_end, F_end, status));
   if (!L0) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: L0 is NULL (a cell relaxation needs a lattice per geometry)", fn);
   if (!Cc) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: Cc is NULL", fn);
   if (!vol_hist || !R_end || !lat_end || !W_end || !vol_end)
@@ -194,21 +192,17 @@ extern "C" int gdml_cell_relax_run(gdml_ctx* ctx, const gdml_cell_relax_params* 
   const int64_t B = p->B;
   const int n3a = 3 * p->N, n3 = n3a + 9;
   const int64_t na = B * n3a, nu = B * n3;
-  const int64_t n_eval_max = max_steps + 1;
-  int64_t chunk_steps = (int64_t)ctx_opt(ctx, "predict.relax_chunk_steps", 32.0);
-  if (chunk_steps < 1) chunk_steps = 1;
-  if (chunk_steps > n_eval_max) chunk_steps = n_eval_max;
+  FrozenRun fr = {B, max_steps, record_every, traj_frozen_chunk_steps(ctx, max_steps), 3, {E_hist, fmax_hist, vol_hist}};
   Recorder rec;
   const int f_R = rec.add(R_rec, na);
   const int f_L = rec.add(lat_rec, 9 * B);
-  rec.size(ctx, chunk_steps);
+  rec.size(ctx, fr.chunk_steps);
 
-  // one allocation: U | V | G | G kept | R | F' | F_end | L | L^-1 | L0 | W' | W_end | E' | vol_end | E | dt | alpha | n_pos |
-  // n_taken | status | bad | a chunk of the history (E, f_atom, Vol) and of frames
-  const int64_t n_state = 4 * nu + 3 * na + 5 * 9 * B + 10 * B;
-  const int64_t n_chunk = 3 * chunk_steps * B + rec.len();
+  // one allocation: U | V | G | G kept | R | F' | F_end | L | L^-1 | L0 | W' | W_end | E' | vol_end | E | dt, alpha, n_pos,
+  // n_taken | status, bad, a chunk of the history (E, f_atom, Vol) | a chunk of frames
+  const int64_t n_state = 4 * nu + 3 * na + 5 * 9 * B + 7 * B;
   double* buf = nullptr;
-  GDML_TRY(ctx_alloc(ctx, (void**)&buf, (n_state + n_chunk) * 8));
+  GDML_TRY(ctx_alloc(ctx, (void**)&buf, (n_state + fr.words() + rec.len()) * 8));
   auto drop = [&](int rc) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)ctx_free(ctx, buf);
@@ -229,42 +223,20 @@ extern "C" int gdml_cell_relax_run(gdml_ctx* ctx, const gdml_cell_relax_params* 
   double* d_Et = d_We + 9 * B;
   double* d_ve = d_Et + B;
   double* d_E = d_ve + B;
-  double* d_dt = d_E + B;
-  double* d_alpha = d_dt + B;
-  int64_t* d_npos = (int64_t*)(d_alpha + B);
-  int64_t* d_ntaken = d_npos + B;
-  int64_t* d_status = d_ntaken + B;
-  int64_t* d_bad = d_status + 2 * B;
-  double* c_E = (double*)(d_bad + B);
-  double* c_fat = c_E + chunk_steps * B;
-  double* c_vol = c_fat + chunk_steps * B;
-  rec.carve(c_vol + chunk_steps * B);
+  FireState d_fire;
+  rec.carve(fr.carve(d_fire.carve(d_E + B, B)));
 
   hipStream_t st = ctx->stream;
   DROP_HIP(hipMemcpy2DAsync(d_U, (size_t)n3 * 8, Sr, (size_t)n3a * 8, (size_t)n3a * 8, (size_t)B, hipMemcpyHostToDevice, st));
   DROP_HIP(hipMemcpy2DAsync(d_U + n3a, (size_t)n3 * 8, Cc, 72, 72, (size_t)B, hipMemcpyHostToDevice, st));
   DROP_HIP(hipMemcpyAsync(d_L0, L0, (size_t)B * 72, hipMemcpyHostToDevice, st));
   DROP_HIP(hipMemcpyAsync(d_V, V, (size_t)nu * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_dt, dt, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_alpha, alpha, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_npos, n_pos, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_ntaken, n_taken, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  traj_fill_i64_kernel<<<ceil_div(3 * B, 256), 256, 0, st>>>(d_status, 3 * B, -1);  // status and bad
+  DROP_HIP(d_fire.copy(h_fire, B, false, st));
   // the caller's arrays are pageable: the copies above have to be through before they may change
   DROP_HIP(hipStreamSynchronize(st));
 
-  RelaxConst C;
-  C.n3 = n3;
-  C.f_scale = 1.0;  // G is in the caller's units already
-  C.fmax = p->fmax;
-  C.dt_max = p->dt_max;
-  C.max_step = p->max_step;
-  C.f_inc = p->f_inc;
-  C.f_dec = p->f_dec;
-  C.alpha_start = p->alpha_start;
-  C.f_alpha = p->f_alpha;
-  C.n_min = p->n_min;
-  RelaxState S = {d_V, d_Gk, d_E, d_dt, d_alpha, d_npos, d_ntaken, d_status, d_bad};
+  const RelaxConst C = relax_const(fire, n3, 1.0);  // G is in the caller's units already
+  RelaxState S = {d_V, d_Gk, d_E, d_fire.dt, d_fire.alpha, d_fire.n_pos, d_fire.n_taken, fr.status(), fr.bad()};
   CellConst K;
   K.n3a = n3a;
   K.f_scale = p->f_scale;
@@ -275,31 +247,16 @@ extern "C" int gdml_cell_relax_run(gdml_ctx* ctx, const gdml_cell_relax_params* 
 
   cell_start_kernel<<<(unsigned)B, 256, 0, st>>>(K, A, n3);
 
-  // the volume history is the third one: its chunk is fetched when the chunk loop starts the next chunk (the stream is idle
-  // then: the loop has synchronised) and once more behind the loop
-  int64_t vol_t0 = 0;
-  auto fetch_vol = [&](int64_t t_end) {
-    const hipError_t e = t_end > vol_t0 ? hipMemcpy(vol_hist + vol_t0 * B, c_vol, (size_t)((t_end - vol_t0) * B) * 8, hipMemcpyDeviceToHost)
-                                        : hipSuccess;
-    vol_t0 = t_end;
-    return e;
-  };
-
-  std::vector<int64_t> h_out;
-  int64_t t = 0;
-  DROP_TRY(traj_run_until_frozen(ctx, rec, R_rec != nullptr || lat_rec != nullptr, B, max_steps, record_every, chunk_steps,
-                                 d_status, E_hist, fmax_hist, h_out, &t, [&](int64_t te, int64_t row, int64_t frame, int last) {
-    if (row == 0) HIP_CHECK(ctx, fetch_vol(te));
-    RelaxSlot sl = {c_E + row * B, c_fat + row * B, nullptr};
-    CellSlot cs = {c_vol + row * B, frame >= 0 ? rec.slot(f_R, frame) : nullptr, frame >= 0 ? rec.slot(f_L, frame) : nullptr};
+  DROP_TRY(traj_run_until_frozen(ctx, rec, R_rec != nullptr || lat_rec != nullptr, fr,
+                                 [&](int64_t te, int64_t row, int64_t frame, int last) {
+    RelaxSlot sl = {fr.row(0, row), fr.row(1, row), nullptr};
+    CellSlot cs = {fr.row(2, row), frame >= 0 ? rec.slot(f_R, frame) : nullptr, frame >= 0 ? rec.slot(f_L, frame) : nullptr};
     // the timer of the previous evaluation's prediction is dropped unread: reading it would wait for it on the host
     ctx->phase_pending.clear();
     GDML_TRY(gdml_predict_virial_cells_dev(ctx, d_R, B, d_L, d_Li, d_Et, d_Ft, d_Wt));
     cell_update_kernel<<<(unsigned)B, 256, 0, st>>>(K, C, S, sl, cs, A, te, last);
     return (int)GDML_OK;
   }));
-  DROP_HIP(fetch_vol(t));
-  const int64_t* h_flags = h_out.data();
   DROP_HIP(hipMemcpy2DAsync(Sr, (size_t)n3a * 8, d_U, (size_t)n3 * 8, (size_t)n3a * 8, (size_t)B, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpy2DAsync(Cc, 72, d_U + n3a, (size_t)n3 * 8, 72, (size_t)B, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpyAsync(V, d_V, (size_t)nu * 8, hipMemcpyDeviceToHost, st));
@@ -309,16 +266,10 @@ extern "C" int gdml_cell_relax_run(gdml_ctx* ctx, const gdml_cell_relax_params* 
   DROP_HIP(hipMemcpyAsync(W_end, d_We, (size_t)B * 72, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpyAsync(vol_end, d_ve, (size_t)B * 8, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpyAsync(E_end, d_E, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(dt, d_dt, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(alpha, d_alpha, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(n_pos, d_npos, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(n_taken, d_ntaken, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(d_fire.copy(h_fire, B, true, st));
   DROP_HIP(hipStreamSynchronize(st));
-  memcpy(status, h_flags, (size_t)(2 * B) * 8);
-  if (first_bad_step) memcpy(first_bad_step, h_flags + 2 * B, (size_t)B * 8);
-
   // a frozen geometry repeats its last history values, its end positions and its end lattice up to the last evaluation made
-  traj_repeat_frozen(h_flags, B, t, record_every, E_hist, fmax_hist, R_rec, R_end, n3a);
-  traj_repeat_frozen(h_flags, B, t, record_every, vol_hist, vol_hist, lat_rec, lat_end, 9);
+  const TrajFrames frames[2] = {{R_rec, R_end, n3a}, {lat_rec, lat_end, 9}};
+  fr.finish(status, first_bad_step, frames, 2);
   return drop(GDML_OK);
 }

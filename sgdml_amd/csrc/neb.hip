@@ -180,16 +180,14 @@ extern "C" int gdml_neb_run(gdml_ctx* ctx, const gdml_neb_params* p, double* R, 
                             double* f_tangent, int64_t* status, int64_t* first_bad_step) {
   const char* fn = "gdml_neb_run";
   if (!p) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: params is NULL", fn);
-  gdml_relax_params rp;
-  rp.B = p->B; rp.N = p->N; rp.f_scale = p->f_scale; rp.lat = p->lat; rp.lat_inv = p->lat_inv; rp.fmax = p->fmax;
-  rp.dt_max = p->dt_max; rp.max_step = p->max_step; rp.f_inc = p->f_inc; rp.f_dec = p->f_dec; rp.alpha_start = p->alpha_start;
-  rp.f_alpha = p->f_alpha; rp.n_min = p->n_min;
   if (p->P < 3 || p->P > NEB_MAX_IMAGES) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: P outside 3 ... %d", fn, NEB_MAX_IMAGES);
   if (!(p->k_spring > 0.0) || !isfinite(p->k_spring))
     return gdml_fail(ctx, GDML_ERR_INVALID, "%s: k_spring must be positive and finite", fn);
   if (p->B > 0 && p->B * (int64_t)p->P > 0x7fffffffLL) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: B P out of range", fn);
-  GDML_TRY(relax_check(ctx, fn, &rp, R, V, dt, alpha, n_pos, n_taken, max_steps, record_every, R_rec, Emax_hist, fmax_hist, E_end,
-                       F_end, status));
+  const FireParams fire = fire_params(*p);
+  const FireState h_fire = {dt, alpha, n_pos, n_taken};
+  GDML_TRY(relax_check(ctx, fn, p->B, p->N, p->f_scale, p->lat, p->lat_inv, fire, R, V, h_fire, max_steps, record_every, R_rec,
+                       Emax_hist, fmax_hist, E_end, F_end, status));
   if (!i_climb || !s || !f_tangent)
     return gdml_fail(ctx, GDML_ERR_INVALID, "%s: an output array (i_climb, s, f_tangent) is NULL", fn);
   bool run;
@@ -198,20 +196,16 @@ extern "C" int gdml_neb_run(gdml_ctx* ctx, const gdml_neb_params* p, double* R, 
   const int64_t B = p->B;
   const int P = p->P, n3 = 3 * p->N;
   const int64_t nb = B * P, nc = nb * n3;
-  const int64_t n_eval_max = max_steps + 1;
-  int64_t chunk_steps = (int64_t)ctx_opt(ctx, "predict.relax_chunk_steps", 32.0);
-  if (chunk_steps < 1) chunk_steps = 1;
-  if (chunk_steps > n_eval_max) chunk_steps = n_eval_max;
+  FrozenRun fr = {B, max_steps, record_every, traj_frozen_chunk_steps(ctx, max_steps), 2, {Emax_hist, fmax_hist}};
   Recorder rec;
   const int f_R = rec.add(R_rec, nc);
-  rec.size(ctx, chunk_steps);
+  rec.size(ctx, fr.chunk_steps);
 
   // one allocation: R | V | band force | F', E' of the prediction | the outputs F, E, s, f_tangent, i_climb | scratch f_tangent,
-  // arc-length increments | E'(highest image) | dt | alpha | n_pos | n_taken | status | bad | a chunk of the history and of frames
-  const int64_t n_state = 5 * nc + 6 * nb + 9 * B;
-  const int64_t n_chunk = 2 * chunk_steps * B + rec.len();
+  // arc-length increments | E'(highest image) | dt, alpha, n_pos, n_taken | status, bad, a chunk of the history | a chunk of frames
+  const int64_t n_state = 5 * nc + 6 * nb + 6 * B;
   double* buf = nullptr;
-  GDML_TRY(ctx_alloc(ctx, (void**)&buf, (n_state + n_chunk) * 8));
+  GDML_TRY(ctx_alloc(ctx, (void**)&buf, (n_state + fr.words() + rec.len()) * 8));
   auto drop = [&](int rc) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)ctx_free(ctx, buf);
@@ -230,50 +224,27 @@ extern "C" int gdml_neb_run(gdml_ctx* ctx, const gdml_neb_params* p, double* R, 
   double* w_inc = w_ftan + nb;
   int64_t* d_iclimb = (int64_t*)(w_inc + nb);
   double* d_Emax = (double*)(d_iclimb + B);
-  double* d_dt = d_Emax + B;
-  double* d_alpha = d_dt + B;
-  int64_t* d_npos = (int64_t*)(d_alpha + B);
-  int64_t* d_ntaken = d_npos + B;
-  int64_t* d_status = d_ntaken + B;
-  int64_t* d_bad = d_status + 2 * B;
-  double* c_E = (double*)(d_bad + B);
-  double* c_fat = c_E + chunk_steps * B;
-  rec.carve(c_fat + chunk_steps * B);
+  FireState d_fire;
+  rec.carve(fr.carve(d_fire.carve(d_Emax + B, B)));
 
   hipStream_t st = ctx->stream;
   DROP_HIP(hipMemcpyAsync(d_R, R, (size_t)nc * 8, hipMemcpyHostToDevice, st));
   DROP_HIP(hipMemcpyAsync(d_V, V, (size_t)nc * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_dt, dt, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_alpha, alpha, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_npos, n_pos, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_ntaken, n_taken, (size_t)B * 8, hipMemcpyHostToDevice, st));
+  DROP_HIP(d_fire.copy(h_fire, B, false, st));
   // band force (its end rows are never written), outputs and scratch: zero
   DROP_HIP(hipMemsetAsync(d_Fb, 0, (size_t)(3 * nc + 6 * nb + B) * 8, st));
-  traj_fill_i64_kernel<<<ceil_div(3 * B, 256), 256, 0, st>>>(d_status, 3 * B, -1);  // status and bad
   // the caller's arrays are pageable: the copies above have to be through before they may change
   DROP_HIP(hipStreamSynchronize(st));
 
-  RelaxConst C;
-  C.n3 = (P - 2) * n3;  // the band vector
-  C.f_scale = 1.0;      // the NEB force is built from g = f_scale F' already
-  C.fmax = p->fmax;
-  C.dt_max = p->dt_max;
-  C.max_step = p->max_step;
-  C.f_inc = p->f_inc;
-  C.f_dec = p->f_dec;
-  C.alpha_start = p->alpha_start;
-  C.f_alpha = p->f_alpha;
-  C.n_min = p->n_min;
+  // the band vector; the NEB force is built from g = f_scale F' already
+  const RelaxConst C = relax_const(fire, (P - 2) * n3, 1.0);
   // relax_finish keeps "F'" of the vector in S.F: here the band force buffer itself (every thread rewrites what it read)
-  RelaxState S = {d_V, d_Fb, d_Emax, d_dt, d_alpha, d_npos, d_ntaken, d_status, d_bad};
-  NebBand A = {P, n3, d_R, d_Ft, d_Et, d_Fb, w_ftan, w_inc, d_status};
+  RelaxState S = {d_V, d_Fb, d_Emax, d_fire.dt, d_fire.alpha, d_fire.n_pos, d_fire.n_taken, fr.status(), fr.bad()};
+  NebBand A = {P, n3, d_R, d_Ft, d_Et, d_Fb, w_ftan, w_inc, fr.status()};
   NebEnd Z = {d_F, d_E, d_s, d_ftan, d_iclimb};
 
-  std::vector<int64_t> h_out;
-  int64_t t = 0;
-  DROP_TRY(traj_run_until_frozen(ctx, rec, R_rec != nullptr, B, max_steps, record_every, chunk_steps, d_status, Emax_hist,
-                                 fmax_hist, h_out, &t, [&](int64_t te, int64_t row, int64_t frame, int last) {
-    RelaxSlot sl = {c_E + row * B, c_fat + row * B, frame >= 0 ? rec.slot(f_R, frame) : nullptr};
+  DROP_TRY(traj_run_until_frozen(ctx, rec, R_rec != nullptr, fr, [&](int64_t te, int64_t row, int64_t frame, int last) {
+    RelaxSlot sl = {fr.row(0, row), fr.row(1, row), frame >= 0 ? rec.slot(f_R, frame) : nullptr};
     // the timer of the previous evaluation's prediction is dropped unread: reading it would wait for it on the host
     ctx->phase_pending.clear();
     GDML_TRY(gdml_predict_dev(ctx, d_R, nb, p->lat, p->lat_inv, d_Et, d_Ft));
@@ -281,7 +252,6 @@ extern "C" int gdml_neb_run(gdml_ctx* ctx, const gdml_neb_params* p, double* R, 
     neb_step_kernel<<<(unsigned)B, 256, 0, st>>>(C, S, sl, A, Z, d_R, te, last);
     return (int)GDML_OK;
   }));
-  const int64_t* h_flags = h_out.data();
   DROP_HIP(hipMemcpyAsync(R, d_R, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpyAsync(V, d_V, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpyAsync(F_end, d_F, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
@@ -289,13 +259,9 @@ extern "C" int gdml_neb_run(gdml_ctx* ctx, const gdml_neb_params* p, double* R, 
   DROP_HIP(hipMemcpyAsync(s, d_s, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpyAsync(f_tangent, d_ftan, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpyAsync(i_climb, d_iclimb, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(dt, d_dt, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(alpha, d_alpha, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(n_pos, d_npos, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(n_taken, d_ntaken, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(d_fire.copy(h_fire, B, true, st));
   DROP_HIP(hipStreamSynchronize(st));
-  memcpy(status, h_flags, (size_t)(2 * B) * 8);
-  if (first_bad_step) memcpy(first_bad_step, h_flags + 2 * B, (size_t)B * 8);
-  traj_repeat_frozen(h_flags, B, t, record_every, Emax_hist, fmax_hist, R_rec, R, (int64_t)P * n3);
+  const TrajFrames frames = {R_rec, R, (int64_t)P * n3};
+  fr.finish(status, first_bad_step, &frames, 1);
   return drop(GDML_OK);
 }

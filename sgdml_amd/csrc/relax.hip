@@ -85,35 +85,35 @@ extern "C" int gdml_relax_run(gdml_ctx* ctx, const gdml_relax_params* p, double*
                               int64_t* n_pos, int64_t* n_taken, int64_t max_steps, int64_t record_every, double* R_rec,
                               double* E_hist, double* fmax_hist, double* E_end, double* F_end, int64_t* status,
                               int64_t* first_bad_step) {
-  GDML_TRY(relax_check(ctx, "gdml_relax_run", p, R, V, dt, alpha, n_pos, n_taken, max_steps, record_every, R_rec, E_hist,
-                       fmax_hist, E_end, F_end, status));
+  const char* fn = "gdml_relax_run";
+  if (!p) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: params is NULL", fn);
+  const FireParams fire = fire_params(*p);
+  const FireState h_fire = {dt, alpha, n_pos, n_taken};
+  GDML_TRY(relax_check(ctx, fn, p->B, p->N, p->f_scale, p->lat, p->lat_inv, fire, R, V, h_fire, max_steps, record_every, R_rec,
+                       E_hist, fmax_hist, E_end, F_end, status));
   bool run;
-  GDML_TRY(traj_prelude(ctx, "gdml_relax_run", p->N, p->B, first_bad_step, &run));
+  GDML_TRY(traj_prelude(ctx, fn, p->N, p->B, first_bad_step, &run));
   if (!run) return GDML_OK;
   Model& md = ctx->model;
   const int64_t B = p->B;
   const int n3 = 3 * p->N;
   const int64_t nc = B * n3;
-  const int64_t n_eval_max = max_steps + 1;
   // evaluations per chunk, and frames of R per chunk where they are recorded
-  int64_t chunk_steps = (int64_t)ctx_opt(ctx, "predict.relax_chunk_steps", 32.0);
-  if (chunk_steps < 1) chunk_steps = 1;
-  if (chunk_steps > n_eval_max) chunk_steps = n_eval_max;
+  FrozenRun fr = {B, max_steps, record_every, traj_frozen_chunk_steps(ctx, max_steps), 2, {E_hist, fmax_hist}};
   Recorder rec;
   const int f_R = rec.add(R_rec, nc);
-  rec.size(ctx, chunk_steps);
+  rec.size(ctx, fr.chunk_steps);
 
   const bool fused =
       fused_serves(md, B) && n3 <= FUSED_MAX_N3 && !ctx->profiling && ctx_opt_i(ctx, "predict.relax_fused", 1) != 0;
   const FusedPlan plan = fused_plan(ctx, md);
 
   // one allocation: two halves of R (the general route works in the first) | V | F | F', E' of the general route's prediction
-  // | E | dt | alpha | n_pos | n_taken | status | bad | a chunk of the history (E, f_atom) and of frames | partials, tickets
-  const int64_t n_state = 4 * nc + (fused ? 0 : nc + B) + 8 * B;
-  const int64_t n_chunk = 2 * chunk_steps * B + rec.len();
+  // | E | dt, alpha, n_pos, n_taken | status, bad, a chunk of the history (E, f_atom) | a chunk of frames | partials, tickets
+  const int64_t n_state = 4 * nc + (fused ? 0 : nc + B) + 5 * B;
   const int64_t n_part = fused ? fused_part_len(md, plan, B) + FUSED_MAX_Q : 0;
   double* buf = nullptr;
-  GDML_TRY(ctx_alloc(ctx, (void**)&buf, (n_state + n_chunk + n_part) * 8));
+  GDML_TRY(ctx_alloc(ctx, (void**)&buf, (n_state + fr.words() + rec.len() + n_part) * 8));
   auto drop = [&](int rc) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)ctx_free(ctx, buf);
@@ -126,41 +126,20 @@ extern "C" int gdml_relax_run(gdml_ctx* ctx, const gdml_relax_params* p, double*
   double* d_Ft = d_F + nc;
   double* d_Et = d_Ft + (fused ? 0 : nc);
   double* d_E = d_Et + (fused ? 0 : B);
-  double* d_dt = d_E + B;
-  double* d_alpha = d_dt + B;
-  int64_t* d_npos = (int64_t*)(d_alpha + B);
-  int64_t* d_ntaken = d_npos + B;
-  int64_t* d_status = d_ntaken + B;
-  int64_t* d_bad = d_status + 2 * B;
-  double* c_E = (double*)(d_bad + B);
-  double* c_fat = c_E + chunk_steps * B;
-  double* d_part = rec.carve(c_fat + chunk_steps * B);
+  FireState d_fire;
+  double* d_part = rec.carve(fr.carve(d_fire.carve(d_E + B, B)));
   unsigned* d_counter = (unsigned*)(d_part + fused_part_len(md, plan, B));
 
   hipStream_t st = ctx->stream;
   DROP_HIP(hipMemcpyAsync(half[0], R, (size_t)nc * 8, hipMemcpyHostToDevice, st));
   DROP_HIP(hipMemcpyAsync(d_V, V, (size_t)nc * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_dt, dt, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_alpha, alpha, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_npos, n_pos, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  DROP_HIP(hipMemcpyAsync(d_ntaken, n_taken, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  traj_fill_i64_kernel<<<ceil_div(3 * B, 256), 256, 0, st>>>(d_status, 3 * B, -1);  // status and bad
+  DROP_HIP(d_fire.copy(h_fire, B, false, st));
   if (fused) DROP_HIP(hipMemsetAsync(d_counter, 0, FUSED_MAX_Q * 8, st));
   // the caller's arrays are pageable: the copies above have to be through before they may change
   DROP_HIP(hipStreamSynchronize(st));
 
-  RelaxConst C;
-  C.n3 = n3;
-  C.f_scale = p->f_scale;
-  C.fmax = p->fmax;
-  C.dt_max = p->dt_max;
-  C.max_step = p->max_step;
-  C.f_inc = p->f_inc;
-  C.f_dec = p->f_dec;
-  C.alpha_start = p->alpha_start;
-  C.f_alpha = p->f_alpha;
-  C.n_min = p->n_min;
-  RelaxState S = {d_V, d_F, d_E, d_dt, d_alpha, d_npos, d_ntaken, d_status, d_bad};
+  const RelaxConst C = relax_const(fire, n3, p->f_scale);
+  RelaxState S = {d_V, d_F, d_E, d_fire.dt, d_fire.alpha, d_fire.n_pos, d_fire.n_taken, fr.status(), fr.bad()};
 
   RelaxStepArgs A;
   memset(&A, 0, sizeof(A));
@@ -169,12 +148,8 @@ extern "C" int gdml_relax_run(gdml_ctx* ctx, const gdml_relax_params* p, double*
     A.C = C; A.S = S;
   }
 
-  // status (B,2), bad (B) and the chunk's history lie side by side: ONE copy per chunk brings them to the host
-  std::vector<int64_t> h_out;
-  int64_t t = 0;
-  DROP_TRY(traj_run_until_frozen(ctx, rec, R_rec != nullptr, B, max_steps, record_every, chunk_steps, d_status, E_hist, fmax_hist,
-                                 h_out, &t, [&](int64_t te, int64_t row, int64_t frame, int last) {
-    RelaxSlot sl = {c_E + row * B, c_fat + row * B, frame >= 0 ? rec.slot(f_R, frame) : nullptr};
+  DROP_TRY(traj_run_until_frozen(ctx, rec, R_rec != nullptr, fr, [&](int64_t te, int64_t row, int64_t frame, int last) {
+    RelaxSlot sl = {fr.row(0, row), fr.row(1, row), frame >= 0 ? rec.slot(f_R, frame) : nullptr};
     if (fused) {
       A.sl = sl; A.t = te; A.last = last;
       A.inR = half[cur]; A.outR = half[cur ^ 1];
@@ -188,20 +163,14 @@ extern "C" int gdml_relax_run(gdml_ctx* ctx, const gdml_relax_params* p, double*
     }
     return (int)GDML_OK;
   }));
-  const int64_t* h_flags = h_out.data();
   DROP_HIP(hipMemcpyAsync(R, half[cur], (size_t)nc * 8, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpyAsync(V, d_V, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpyAsync(F_end, d_F, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
   DROP_HIP(hipMemcpyAsync(E_end, d_E, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(dt, d_dt, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(alpha, d_alpha, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(n_pos, d_npos, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  DROP_HIP(hipMemcpyAsync(n_taken, d_ntaken, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+  DROP_HIP(d_fire.copy(h_fire, B, true, st));
   DROP_HIP(hipStreamSynchronize(st));
-  memcpy(status, h_flags, (size_t)(2 * B) * 8);
-  if (first_bad_step) memcpy(first_bad_step, h_flags + 2 * B, (size_t)B * 8);
-
   // a frozen replica repeats its last history values and its end positions up to the last evaluation made
-  traj_repeat_frozen(h_flags, B, t, record_every, E_hist, fmax_hist, R_rec, R, n3);
+  const TrajFrames frames = {R_rec, R, n3};
+  fr.finish(status, first_bad_step, &frames, 1);
   return drop(GDML_OK);
 }

@@ -128,38 +128,71 @@ __device__ __forceinline__ bool relax_finish(const RelaxConst& C, const RelaxSta
   return false;
 }
 
-// argument checks of gdml_relax_run, and the part of gdml_neb_run's they cover (fn: the entry's name, the prefix of every
-// message); ctx may be NULL (the message then goes where gdml_ctx_create's goes)
-static inline int relax_check(gdml_ctx* ctx, const char* fn, const gdml_relax_params* p, const double* R, const double* V,
-                              const double* dt, const double* alpha, const int64_t* n_pos, const int64_t* n_taken,
+// ---- host side: what gdml_relax_run, gdml_neb_run and gdml_cell_relax_run share around the kernels -------------------------------
+struct FireParams {  // the FIRE constants of gdml_relax_params, gdml_neb_params and gdml_cell_relax_params
+  double fmax, dt_max, max_step, f_inc, f_dec, alpha_start, f_alpha;
+  int64_t n_min;
+};
+template <class P>
+static inline FireParams fire_params(const P& p) {
+  return {p.fmax, p.dt_max, p.max_step, p.f_inc, p.f_dec, p.alpha_start, p.f_alpha, p.n_min};
+}
+static inline RelaxConst relax_const(const FireParams& f, int n3, double f_scale) {
+  return {n3, f_scale, f.fmax, f.dt_max, f.max_step, f.f_inc, f.f_dec, f.alpha_start, f.f_alpha, f.n_min};
+}
+
+// the per-replica FIRE state dt | alpha | n_pos | n_taken, B words each: in device memory (carve), or the caller's arrays
+struct FireState {
+  double *dt, *alpha;
+  int64_t *n_pos, *n_taken;
+  double* carve(double* p, int64_t B) {  // takes 4 B words from p; returns the end
+    *this = {p, p + B, (int64_t*)(p + 2 * B), (int64_t*)(p + 3 * B)};
+    return p + 4 * B;
+  }
+  // device <- host (to_host = false) or host <- device, queued on st
+  hipError_t copy(const FireState& host, int64_t B, bool to_host, hipStream_t st) const {
+    void* d[4] = {dt, alpha, n_pos, n_taken};
+    void* h[4] = {host.dt, host.alpha, host.n_pos, host.n_taken};
+    for (int i = 0; i < 4; ++i) {
+      const hipError_t e = to_host ? hipMemcpyAsync(h[i], d[i], (size_t)B * 8, hipMemcpyDeviceToHost, st)
+                                   : hipMemcpyAsync(d[i], h[i], (size_t)B * 8, hipMemcpyHostToDevice, st);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+};
+
+// argument checks of the three entries behind their own test of params (fn: the entry's name, the prefix of every message);
+// ctx may be NULL (the message then goes where gdml_ctx_create's goes)
+static inline int relax_check(gdml_ctx* ctx, const char* fn, int64_t B, int N, double f_scale, const double* lat,
+                              const double* lat_inv, const FireParams& p, const double* R, const double* V, const FireState& s,
                               int64_t max_steps, int64_t record_every, const double* R_rec, const double* E_hist,
                               const double* fmax_hist, const double* E_end, const double* F_end, const int64_t* status) {
-  if (!p) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: params is NULL", fn);
   if (max_steps < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: max_steps < 0", fn);
   if (record_every < 0 || (R_rec && record_every < 1))
     return gdml_fail(ctx, GDML_ERR_INVALID, "%s: record_every < 0, or < 1 with R_rec", fn);
-  GDML_TRY(traj_check_shape(ctx, fn, p->B, p->N));
-  GDML_TRY(traj_check_f_scale(ctx, fn, p->f_scale));
-  if (!(p->fmax > 0.0) || !isfinite(p->fmax)) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: fmax must be positive and finite", fn);
-  if (!(p->max_step > 0.0) || !isfinite(p->max_step))
+  GDML_TRY(traj_check_shape(ctx, fn, B, N));
+  GDML_TRY(traj_check_f_scale(ctx, fn, f_scale));
+  if (!(p.fmax > 0.0) || !isfinite(p.fmax)) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: fmax must be positive and finite", fn);
+  if (!(p.max_step > 0.0) || !isfinite(p.max_step))
     return gdml_fail(ctx, GDML_ERR_INVALID, "%s: max_step must be positive and finite", fn);
-  if (!(p->f_inc >= 1.0) || !isfinite(p->f_inc)) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: f_inc < 1", fn);
-  if (!(p->f_dec > 0.0 && p->f_dec < 1.0)) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: f_dec outside (0, 1)", fn);
-  if (!(p->alpha_start > 0.0 && p->alpha_start <= 1.0))
+  if (!(p.f_inc >= 1.0) || !isfinite(p.f_inc)) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: f_inc < 1", fn);
+  if (!(p.f_dec > 0.0 && p.f_dec < 1.0)) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: f_dec outside (0, 1)", fn);
+  if (!(p.alpha_start > 0.0 && p.alpha_start <= 1.0))
     return gdml_fail(ctx, GDML_ERR_INVALID, "%s: alpha_start outside (0, 1]", fn);
-  if (!(p->f_alpha > 0.0 && p->f_alpha <= 1.0)) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: f_alpha outside (0, 1]", fn);
-  if (p->n_min < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: n_min < 0", fn);
-  GDML_TRY(traj_check_lattice(ctx, fn, p->lat, p->lat_inv));
-  if (!R || !V || !dt || !alpha || !n_pos || !n_taken)
+  if (!(p.f_alpha > 0.0 && p.f_alpha <= 1.0)) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: f_alpha outside (0, 1]", fn);
+  if (p.n_min < 0) return gdml_fail(ctx, GDML_ERR_INVALID, "%s: n_min < 0", fn);
+  GDML_TRY(traj_check_lattice(ctx, fn, lat, lat_inv));
+  if (!R || !V || !s.dt || !s.alpha || !s.n_pos || !s.n_taken)
     return gdml_fail(ctx, GDML_ERR_INVALID, "%s: a state array (R, V, dt, alpha, n_pos, n_taken) is NULL", fn);
   if (!E_hist || !fmax_hist || !E_end || !F_end || !status)
     return gdml_fail(ctx, GDML_ERR_INVALID, "%s: an output array (E_hist, fmax_hist, E_end, F_end, status) is NULL", fn);
-  if (!(p->dt_max > 0.0) || !isfinite(p->dt_max))
+  if (!(p.dt_max > 0.0) || !isfinite(p.dt_max))
     return gdml_fail(ctx, GDML_ERR_INVALID, "%s: dt_max must be positive and finite", fn);
-  for (int64_t b = 0; b < p->B; ++b) {
-    if (!(dt[b] > 0.0) || !isfinite(dt[b]))
+  for (int64_t b = 0; b < B; ++b) {
+    if (!(s.dt[b] > 0.0) || !isfinite(s.dt[b]))
       return gdml_fail(ctx, GDML_ERR_INVALID, "%s: dt of replica %lld must be positive and finite", fn, (long long)b);
-    if (p->dt_max < dt[b])
+    if (p.dt_max < s.dt[b])
       return gdml_fail(ctx, GDML_ERR_INVALID, "%s: dt_max is below dt of replica %lld", fn, (long long)b);
   }
   return GDML_OK;

@@ -1,14 +1,15 @@
 // What the on-device trajectory entries (gdml_md_run in md.hip, gdml_pimd_run in pimd.hip, gdml_relax_run in relax.hip,
-// gdml_neb_run in neb.hip) share:
+// gdml_neb_run in neb.hip, gdml_cell_relax_run in cellrelax.hip, gdml_ef_run in vib.hip) share:
 // the counter-based noise, the fixed reduction tree, the argument checks and prelude, the recorder of a chunk of frames and
-// the chunk loop of the two MD entries, and the chunk loop of the entries whose replicas freeze on their own (gdml_relax_run,
-// gdml_neb_run in neb.hip).
+// the chunk loop of the two MD entries, and the chunk loop of the four entries whose replicas freeze on their own
+// (gdml_relax_run, gdml_neb_run, gdml_cell_relax_run, gdml_ef_run), whose host-only part is traj_host.h's.
 #pragma once
 #include <math.h>
 
 #include <vector>
 
 #include "common.h"
+#include "traj_host.h"
 
 // ---- Philox4x32-10 (Salmon et al., SC'11), key = (seed lo, seed hi), counter = (step lo, step hi, replica, block) -------------
 struct Philox4 {
@@ -222,66 +223,58 @@ static int traj_run_chunks(gdml_ctx* ctx, Recorder& rec, int64_t n_steps, int64_
   return GDML_OK;
 }
 
-// The chunk loop of gdml_relax_run and gdml_neb_run, whose replicas (geometries, bands) freeze on their own: enqueue(t, row,
-// frame, last) queues evaluation t = 0 .. max_steps on ctx->stream; row = its row in the chunk's two history buffers, frame =
-// the chunk slot of its recorded positions or -1, last = (t == max_steps).  d_flags: status (B,2) | bad (B) | history a
-// (chunk_steps,B) | history b (chunk_steps,B), side by side in device memory, so ONE copy per chunk brings them into h_out
-// (3 B + 2 chunk_steps B words); the rows go on into hist_a, hist_b (max_steps + 1, B).  Ends when no status word says active
-// (-1), a bad flag is set or the budget is used up; *t_queued = evaluations queued.
-template <class Enqueue>
-static int traj_run_until_frozen(gdml_ctx* ctx, Recorder& rec, bool record, int64_t B, int64_t max_steps, int64_t record_every,
-                                 int64_t chunk_steps, const int64_t* d_flags, double* hist_a, double* hist_b,
-                                 std::vector<int64_t>& h_out, int64_t* t_queued, Enqueue&& enqueue) {
-  hipStream_t st = ctx->stream;
-  const int64_t n_out = 3 * B + 2 * chunk_steps * B;
-  h_out.assign((size_t)n_out, -1);
-  const int64_t* h_flags = h_out.data();
-  const double* h_a = (const double*)(h_out.data() + 3 * B);
-  const double* h_b = h_a + chunk_steps * B;
-  int64_t t = 0;
-  bool active = true, any_bad = false;
-  while (t <= max_steps && active && !any_bad) {
-    const int64_t t0 = t;
-    int64_t in_chunk = 0;
-    for (; t <= max_steps && t - t0 < chunk_steps; ++t) {
-      const bool on = record && t % record_every == 0;
-      if (on && in_chunk == rec.frames) break;
-      GDML_TRY(enqueue(t, t - t0, on ? in_chunk : (int64_t)-1, (int)(t == max_steps)));
-      if (on) ++in_chunk;
-    }
-    HIP_CHECK(ctx, hipGetLastError());
-    if (in_chunk > 0) HIP_CHECK(ctx, rec.flush(st, in_chunk));
-    HIP_CHECK(ctx, hipMemcpyAsync(h_out.data(), d_flags, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(ctx, hipStreamSynchronize(st));
-    memcpy(hist_a + t0 * B, h_a, (size_t)((t - t0) * B) * 8);
-    memcpy(hist_b + t0 * B, h_b, (size_t)((t - t0) * B) * 8);
-    active = false;
-    for (int64_t b = 0; b < B; ++b) {
-      active |= h_flags[(size_t)(2 * b)] < 0;
-      any_bad |= h_flags[(size_t)(2 * B + b)] >= 0;
-    }
+// A run of one of the four entries whose replicas (geometries, bands) freeze on their own.  Device layout, side by side so that
+// ONE copy per chunk brings all of it to the host: status (B,2) | bad (B) | history 0 .. n_hist - 1, (chunk_steps,B) each.  A
+// history is 8-byte words (doubles, or int64 as gdml_ef_run's k_follow_hist); its rows go on into hist[h] (max_steps + 1, B).
+struct FrozenRun {
+  int64_t B, max_steps, record_every, chunk_steps;
+  int n_hist;
+  void* hist[4];             // the caller's arrays; null: not wanted
+  int64_t* d_flags;          // device base (carve)
+  std::vector<int64_t> h_out;  // the last chunk as read back: h_out.data() = status, + 2 B = bad
+  int64_t t;                 // evaluations queued
+
+  int64_t words() const { return 3 * B + n_hist * chunk_steps * B; }
+  double* carve(double* p) {  // takes words() from p; returns the end
+    d_flags = (int64_t*)p;
+    return p + words();
   }
-  *t_queued = t;
-  return GDML_OK;
+  int64_t* status() const { return d_flags; }
+  int64_t* bad() const { return d_flags + 2 * B; }
+  double* row(int h, int64_t r) const { return (double*)(d_flags + 3 * B + (h * chunk_steps + r) * B); }
+  // behind the run: status and first_bad_step (may be null) for the caller, then what frozen replicas repeat
+  void finish(int64_t* status_out, int64_t* first_bad_step, const TrajFrames* fr, int n_fr) {
+    memcpy(status_out, h_out.data(), (size_t)(2 * B) * 8);
+    if (first_bad_step) memcpy(first_bad_step, h_out.data() + 2 * B, (size_t)B * 8);
+    traj_repeat_frozen(h_out.data(), B, t, record_every, hist, n_hist, fr, n_fr);
+  }
+};
+
+// evaluations per chunk of such a run: option predict.relax_chunk_steps, at least one, at most all max_steps + 1
+static inline int64_t traj_frozen_chunk_steps(const gdml_ctx* ctx, int64_t max_steps) {
+  const int64_t c = (int64_t)ctx_opt(ctx, "predict.relax_chunk_steps", 32.0);
+  return std::min(std::max(c, (int64_t)1), max_steps + 1);
 }
 
-// After such a run: a frozen replica repeats its last history values and its end positions (R, len doubles per replica) up to
-// the last evaluation any replica made (the launches behind its freeze wrote nothing for it).  h_flags: status (B,2) as read
-// back; t: evaluations queued.
-static inline void traj_repeat_frozen(const int64_t* h_flags, int64_t B, int64_t t, int64_t record_every, double* hist_a,
-                                      double* hist_b, double* R_rec, const double* R, int64_t len) {
-  int64_t n_made = 0;
-  for (int64_t b = 0; b < B; ++b) {
-    const int64_t e = h_flags[(size_t)(2 * b + 1)];
-    n_made = std::max(n_made, e < 0 ? t : e + 1);
+// The chunk loop of such a run: status and bad start at -1; enqueue(t, row, frame, last) queues evaluation t = 0 .. max_steps on
+// ctx->stream; row = its row in the chunk's histories (run.row(h, row)), frame = the chunk slot of its recorded frame or -1,
+// last = (t == max_steps).  Per chunk (traj_next_chunk): flush, the ONE copy, ONE synchronisation.  Ends when no status word
+// says active (-1), a bad flag is set or the budget is used up.
+template <class Enqueue>
+static int traj_run_until_frozen(gdml_ctx* ctx, Recorder& rec, bool record, FrozenRun& run, Enqueue&& enqueue) {
+  hipStream_t st = ctx->stream;
+  traj_fill_i64_kernel<<<ceil_div(3 * run.B, 256), 256, 0, st>>>(run.d_flags, 3 * run.B, -1);
+  run.h_out.assign((size_t)run.words(), -1);
+  run.t = 0;
+  for (bool go = true; go && run.t <= run.max_steps;) {
+    const TrajChunk c = traj_next_chunk(run.t, run.max_steps, run.chunk_steps, record, run.record_every, rec.frames);
+    for (int64_t t = c.t0; t < c.t1; ++t) GDML_TRY(enqueue(t, c.row(t), c.frame(t), (int)(t == run.max_steps)));
+    run.t = c.t1;
+    HIP_CHECK(ctx, hipGetLastError());
+    if (c.frames > 0) HIP_CHECK(ctx, rec.flush(st, c.frames));
+    HIP_CHECK(ctx, hipMemcpyAsync(run.h_out.data(), run.d_flags, (size_t)run.words() * 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(ctx, hipStreamSynchronize(st));
+    go = traj_take_chunk(c, run.h_out.data(), run.B, run.chunk_steps, run.hist, run.n_hist);
   }
-  for (int64_t b = 0; b < B; ++b) {
-    const int64_t e = h_flags[(size_t)(2 * b + 1)];
-    if (e < 0) continue;
-    for (int64_t u = e + 1; u < n_made; ++u) {
-      hist_a[u * B + b] = hist_a[e * B + b];
-      hist_b[u * B + b] = hist_b[e * B + b];
-      if (R_rec && u % record_every == 0) memcpy(R_rec + (u / record_every) * B * len + b * len, R + b * len, (size_t)len * 8);
-    }
-  }
+  return GDML_OK;
 }

@@ -293,16 +293,13 @@ struct EfConst {
   int n3, order, has_t;
   double f_scale, fmax, trust_min, trust_max;
 };
-struct EfState {  // per geometry, in device memory: the optimiser's state, the end-of-run outputs, status and histories
+struct EfState {  // per geometry, in device memory: the optimiser's state, the end-of-run outputs and status
   double *R, *tvec, *trust, *E_prev, *dE_pred;
   int64_t* flags;   // bit 0: a previous step exists, bit 1: that step was clipped
   double *F, *E, *w, *mode;
   int64_t *n_rigid, *n_neg;
   int64_t* status;  // (B,2) as gdml_relax_run's
   int64_t* bad;
-  double* wf;       // (max_steps + 1, B): eigenvalue of the followed mode
-  int64_t* kf;      // (max_steps + 1, B): its index
-  int64_t B;
 };
 struct EfEval {  // this evaluation's results for one slice of geometries
   const double *V, *w, *Ft, *Et;  // eigenvectors as rows (bc,n3,n3), spectrum after vib_finish_kernel (bc,n3), F', E'
@@ -310,6 +307,8 @@ struct EfEval {  // this evaluation's results for one slice of geometries
 };
 struct EfSlot {  // where this evaluation goes in the chunk buffers
   double *E, *fat;  // (B) rows of the history
+  double* wf;       // (B) row: eigenvalue of the followed mode
+  int64_t* kf;      // (B) row: its index
   double* R;        // (B,3N) frame; null when this is no recording evaluation
 };
 
@@ -399,8 +398,8 @@ __global__ void __launch_bounds__(256) ef_step_kernel(EfConst C, EfState S, EfEv
     S.E[q] = e;
     S.n_rigid[q] = n_rigid;
     S.n_neg[q] = Ev.n_neg[ql];
-    S.wf[t * S.B + q] = nv > 0 ? wq[kfol] : 0.0;
-    S.kf[t * S.B + q] = kfol;
+    sl.wf[q] = nv > 0 ? wq[kfol] : 0.0;
+    sl.kf[q] = kfol;
     sl.E[q] = e;
     sl.fat[q] = f_atom;
     if (bad_now && S.bad[q] < 0) S.bad[q] = t;
@@ -731,24 +730,22 @@ extern "C" int gdml_ef_run(gdml_ctx* ctx, const gdml_ef_params* p, double* R, do
   const int64_t B = p->B;
   const int N = p->N, n3 = 3 * N;
   const int64_t nn = (int64_t)n3 * n3, nc = B * n3;
-  const int64_t n_eval_max = max_steps + 1;
   // evaluations per chunk, and frames of R per chunk where they are recorded: gdml_relax_run's
-  int64_t chunk_steps = (int64_t)ctx_opt(ctx, "predict.relax_chunk_steps", 32.0);
-  if (chunk_steps < 1) chunk_steps = 1;
-  if (chunk_steps > n_eval_max) chunk_steps = n_eval_max;
+  FrozenRun fr = {B, max_steps, record_every, traj_frozen_chunk_steps(ctx, max_steps), 4,
+                  {E_hist, fmax_hist, w_follow_hist, k_follow_hist}};
   Recorder rec;
   const int f_R = rec.add(R_rec, nc);
-  rec.size(ctx, chunk_steps);
+  rec.size(ctx, fr.chunk_steps);
   // geometries per slice of an evaluation: gdml_vib_run's chunk
   const int64_t slice = vib_chunk_len(ctx, B, n3);
   const SymEigPlan plan = full_plan(ctx, slice, n3);
   const int64_t n_work = full_work_doubles(plan, n3);
 
   // one carve.  Per slice: work matrices | H (D_s, eigenvectors) | F' | w | info | E' | unit masses | sweeps, n_rigid, n_neg.
-  // Per run: R | t | F_end | w_end | mode_end | E_end | trust | E_prev | dE_pred | flags, n_rigid, n_neg | w_follow, k_follow
-  // histories | status, bad, a chunk of the history (E, f_atom) | a chunk of frames
+  // Per run: R | t | F_end | w_end | mode_end | E_end | trust | E_prev | dE_pred | flags, n_rigid, n_neg | status, bad, a chunk of
+  // the history (E, f_atom, w_follow, k_follow) | a chunk of frames
   const int64_t n_slice = n_work + slice * (nn + 2 * n3 + 4 + 1 + 3) + N;
-  const int64_t n_run = 5 * nc + 7 * B + 2 * n_eval_max * B + 3 * B + 2 * chunk_steps * B + rec.len();
+  const int64_t n_run = 5 * nc + 7 * B + fr.words() + rec.len();
   double* buf;
   GDML_TRY(ctx_slot(ctx, SLOT_EF_WS, (n_slice + n_run) * 8, &buf));
   double* work = buf;
@@ -774,14 +771,9 @@ extern "C" int gdml_ef_run(gdml_ctx* ctx, const gdml_ef_params* p, double* R, do
   S.flags = (int64_t*)(S.dE_pred + B);
   S.n_rigid = S.flags + B;
   S.n_neg = S.n_rigid + B;
-  S.wf = (double*)(S.n_neg + B);
-  S.kf = (int64_t*)(S.wf + n_eval_max * B);
-  S.status = S.kf + n_eval_max * B;
-  S.bad = S.status + 2 * B;
-  S.B = B;
-  double* c_E = (double*)(S.bad + B);
-  double* c_fat = c_E + chunk_steps * B;
-  rec.carve(c_fat + chunk_steps * B);
+  rec.carve(fr.carve((double*)(S.n_neg + B)));
+  S.status = fr.status();
+  S.bad = fr.bad();
 
   hipStream_t st = ctx->stream;
   const std::vector<double> ones((size_t)N, 1.0);
@@ -792,7 +784,6 @@ extern "C" int gdml_ef_run(gdml_ctx* ctx, const gdml_ef_params* p, double* R, do
   HIP_CHECK(ctx, hipMemcpyAsync(S.E_prev, E_prev, (size_t)B * 8, hipMemcpyHostToDevice, st));
   HIP_CHECK(ctx, hipMemcpyAsync(S.dE_pred, dE_pred, (size_t)B * 8, hipMemcpyHostToDevice, st));
   HIP_CHECK(ctx, hipMemcpyAsync(S.flags, flags, (size_t)B * 8, hipMemcpyHostToDevice, st));
-  traj_fill_i64_kernel<<<ceil_div(3 * B, 256), 256, 0, st>>>(S.status, 3 * B, -1);  // status and bad
   // the caller's arrays are pageable: the copies above have to be through before they may change
   HIP_CHECK(ctx, hipStreamSynchronize(st));
 
@@ -804,11 +795,9 @@ extern "C" int gdml_ef_run(gdml_ctx* ctx, const gdml_ef_params* p, double* R, do
     HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(vib_project_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)proj_lds));
 
-  std::vector<int64_t> h_out;
-  int64_t t = 0;
-  GDML_TRY(traj_run_until_frozen(ctx, rec, R_rec != nullptr, B, max_steps, record_every, chunk_steps, S.status, E_hist, fmax_hist,
-                                 h_out, &t, [&](int64_t te, int64_t row, int64_t frame, int last) {
-    const EfSlot sl = {c_E + row * B, c_fat + row * B, frame >= 0 ? rec.slot(f_R, frame) : nullptr};
+  GDML_TRY(traj_run_until_frozen(ctx, rec, R_rec != nullptr, fr, [&](int64_t te, int64_t row, int64_t frame, int last) {
+    const EfSlot sl = {fr.row(0, row), fr.row(1, row), fr.row(2, row), (int64_t*)fr.row(3, row),
+                       frame >= 0 ? rec.slot(f_R, frame) : nullptr};
     // the timer of the previous Hessian is dropped unread: reading it would wait for it on the host
     ctx->phase_pending.clear();
     for (int64_t b0 = 0; b0 < B; b0 += slice) {
@@ -830,8 +819,6 @@ extern "C" int gdml_ef_run(gdml_ctx* ctx, const gdml_ef_params* p, double* R, do
     }
     return (int)GDML_OK;
   }));
-  const int64_t* h_flags = h_out.data();
-  std::vector<int64_t> h_k((size_t)(t * B));
   HIP_CHECK(ctx, hipMemcpyAsync(R, S.R, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
   if (t_follow) HIP_CHECK(ctx, hipMemcpyAsync(t_follow, S.tvec, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(ctx, hipMemcpyAsync(trust, S.trust, (size_t)B * 8, hipMemcpyDeviceToHost, st));
@@ -844,22 +831,10 @@ extern "C" int gdml_ef_run(gdml_ctx* ctx, const gdml_ef_params* p, double* R, do
   HIP_CHECK(ctx, hipMemcpyAsync(mode_end, S.mode, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(ctx, hipMemcpyAsync(n_rigid, S.n_rigid, (size_t)B * 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(ctx, hipMemcpyAsync(n_neg, S.n_neg, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(ctx, hipMemcpyAsync(w_follow_hist, S.wf, (size_t)(t * B) * 8, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(ctx, hipMemcpyAsync(h_k.data(), S.kf, (size_t)(t * B) * 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(ctx, hipStreamSynchronize(st));
-  memcpy(status, h_flags, (size_t)(2 * B) * 8);
-  if (first_bad_step) memcpy(first_bad_step, h_flags + 2 * B, (size_t)B * 8);
-
   // a frozen geometry repeats its last history values and its end positions up to the last evaluation made (the launches
   // behind its freeze wrote nothing for it)
-  traj_repeat_frozen(h_flags, B, t, record_every, E_hist, fmax_hist, R_rec, R, n3);
-  for (int64_t b = 0; b < B; ++b) {
-    const int64_t e = h_flags[(size_t)(2 * b + 1)];
-    for (int64_t u = 0; u < t; ++u) {
-      const int64_t src = (e >= 0 && u > e) ? e : u;
-      if (src != u) w_follow_hist[u * B + b] = w_follow_hist[src * B + b];
-      if (k_follow_hist) k_follow_hist[u * B + b] = h_k[(size_t)(src * B + b)];
-    }
-  }
+  const TrajFrames frames = {R_rec, R, n3};
+  fr.finish(status, first_bad_step, &frames, 1);
   return GDML_OK;
 }

@@ -142,6 +142,38 @@ def _raise_first_bad(bad, noun, unit):
         raise FloatingPointError('{} {} stopped being finite at {} {}'.format(noun, b, unit, int(bad[b])))
 
 
+def _fire_checks(fmax, dt_start, dt_max, max_step, f_inc, f_dec, alpha_start, f_alpha, f_unit, n_min, max_steps, record_every,
+                 after_fmax=(), more=(), positive=None):
+    """The checks relax(), relax_cell() and neb() share, in their order.  after_fmax, more: the entry's own (name, value)
+    pairs for the finite check; positive: a (name, value) that must be > 0.  Returns dt_max (None: 10 dt_start)."""
+    if dt_max is None:
+        dt_max = 10.0 * dt_start
+    _check_finite(('fmax', fmax), *after_fmax, ('dt_start', dt_start), ('dt_max', dt_max), ('max_step', max_step),
+                  ('f_inc', f_inc), ('f_dec', f_dec), ('alpha_start', alpha_start), ('f_alpha', f_alpha), ('f_unit', f_unit), *more)
+    if positive is not None and not positive[1] > 0.0:
+        raise ValueError('{} must be positive'.format(positive[0]))
+    if int(max_steps) != max_steps or int(record_every) != record_every or int(n_min) != n_min:
+        raise ValueError('max_steps, record_every and n_min must be integers')
+    return dt_max
+
+
+def _fire_state(state, B, v_shape, dt_start, alpha_start, shapes, more_keys=()):
+    """A fresh FIRE state (state None; V zeros of v_shape), or the caller's, checked: no key missing, then the shapes
+    ((key, shape, message with {} for the shape wanted and the shape found), ...), then finite V, dt, alpha."""
+    if state is None:
+        return dict(V=np.zeros(v_shape), dt=np.full(B, float(dt_start)), alpha=np.full(B, float(alpha_start)),
+                    n_pos=np.zeros(B, dtype=np.int64), n_taken=np.zeros(B, dtype=np.int64))
+    missing = [k for k in more_keys + ('V', 'dt', 'alpha', 'n_pos', 'n_taken') if k not in state]
+    if missing:
+        raise ValueError('state lacks {}'.format(missing))
+    for k, shp, msg in shapes:
+        if np.shape(state[k]) != shp:
+            raise ValueError(msg.format(shp, np.shape(state[k])))
+    if not all(np.isfinite(np.asarray(state[k], dtype=np.float64)).all() for k in ('V', 'dt', 'alpha')):
+        raise ValueError('state must be finite')
+    return state
+
+
 class GDMLPredict(object):
     def __init__(
         self,
@@ -519,37 +551,30 @@ class GDMLPredict(object):
         n3 = 3 * self.n_atoms
         R0 = _as_batch(R0, n3)
         B = R0.shape[0]
-        if dt_max is None:
-            dt_max = 10.0 * dt_start
-        _check_finite(('fmax', fmax), ('dt_start', dt_start), ('dt_max', dt_max), ('max_step', max_step), ('f_inc', f_inc),
-                      ('f_dec', f_dec), ('alpha_start', alpha_start), ('f_alpha', f_alpha), ('f_unit', f_unit))
-        if int(max_steps) != max_steps or int(record_every) != record_every or int(n_min) != n_min:
-            raise ValueError('max_steps, record_every and n_min must be integers')
-        if state is None:
-            state = dict(V=np.zeros((B, n3)), dt=np.full(B, float(dt_start)), alpha=np.full(B, float(alpha_start)),
-                         n_pos=np.zeros(B, dtype=np.int64), n_taken=np.zeros(B, dtype=np.int64))
-        else:
-            missing = [k for k in ('V', 'dt', 'alpha', 'n_pos', 'n_taken') if k not in state]
-            if missing:
-                raise ValueError('state lacks {}'.format(missing))
-            if np.shape(state['V']) != R0.shape:
-                raise ValueError("state['V'] must have the shape of R0 {}, got {}".format(R0.shape, np.shape(state['V'])))
-            if not all(np.isfinite(np.asarray(state[k], dtype=np.float64)).all() for k in ('V', 'dt', 'alpha')):
-                raise ValueError('state must be finite')
+        dt_max = _fire_checks(fmax, dt_start, dt_max, max_step, f_inc, f_dec, alpha_start, f_alpha, f_unit, n_min, max_steps,
+                              record_every)
+        state = _fire_state(state, B, R0.shape, dt_start, alpha_start,
+                            (('V', R0.shape, "state['V'] must have the shape of R0 {}, got {}"),))
         # a NaN start is not a usage error: the run reports the geometry and the evaluation (FloatingPointError)
         out = self._ctx.relax_run(R0, fmax, max_steps, state, dt_max, max_step=max_step, n_min=n_min, f_inc=f_inc, f_dec=f_dec,
                                   alpha_start=alpha_start, f_alpha=f_alpha, f_scale=self.std * float(f_unit),
                                   record_every=record_every, lat_and_inv=self._lat_and_inv(lattice))
-        _raise_first_bad(out.pop('first_bad_step'), 'geometry', 'evaluation')
+        return self._frozen_result(out, 'geometry', ('E_end', 'E_hist'))
+
+    def _frozen_result(self, out, noun, energy_keys):
+        """What relax(), relax_cell(), neb() and stationary_point() make of their entry's result: the first non-finite value
+        is an error naming the `noun`; 'status' becomes 'n_steps', 'converged' and 'fmax_end'; 'F_end' and the energy_keys
+        are scaled like predict()."""
+        _raise_first_bad(out.pop('first_bad_step'), noun, 'evaluation')
         status = out.pop('status')
         out.pop('n_made')
         out['F_end'] *= self.std
-        for k in ('E_end', 'E_hist'):
+        for k in energy_keys:
             out[k] *= self.std
             out[k] += self.c
         out['n_steps'] = status[:, 1].copy()
         out['converged'] = status[:, 0] == 1
-        out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
+        out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(len(status))] if len(status) else np.empty(0)
         return out
 
     # ---- variable-cell relaxation on the device (gdml_cell_relax_run, csrc/cellrelax.hip)
@@ -577,21 +602,19 @@ class GDMLPredict(object):
         n3 = 3 * self.n_atoms
         R0 = _as_batch(R0, n3)
         B = R0.shape[0]
-        if dt_max is None:
-            dt_max = 10.0 * dt_start
         if cell_factor is None:
             cell_factor = float(self.n_atoms)
-        _check_finite(('fmax', fmax), ('dt_start', dt_start), ('dt_max', dt_max), ('max_step', max_step), ('f_inc', f_inc),
-                      ('f_dec', f_dec), ('alpha_start', alpha_start), ('f_alpha', f_alpha), ('f_unit', f_unit),
-                      ('pressure', pressure), ('cell_factor', cell_factor))
-        if not cell_factor > 0.0:
-            raise ValueError('cell_factor must be positive')
-        if int(max_steps) != max_steps or int(record_every) != record_every or int(n_min) != n_min:
-            raise ValueError('max_steps, record_every and n_min must be integers')
+        dt_max = _fire_checks(fmax, dt_start, dt_max, max_step, f_inc, f_dec, alpha_start, f_alpha, f_unit, n_min, max_steps,
+                              record_every, more=(('pressure', pressure), ('cell_factor', cell_factor)),
+                              positive=('cell_factor', cell_factor))
         if mask is not None:
             mask = np.asarray(mask, dtype=np.float64)
             if mask.shape != (3, 3) or not np.isin(mask, (0.0, 1.0)).all() or not np.array_equal(mask, mask.T):
                 raise ValueError('mask must be a symmetric 3 x 3 array of 0 and 1')
+        fire = _fire_state(state, B, (B, n3 + 9), dt_start, alpha_start,
+                           tuple((k, shp, "state['" + k + "'] must have shape {}, got {}")
+                                 for k, shp in (('S', (B, n3)), ('C', (B, 3, 3)), ('L0', (B, 3, 3)), ('V', (B, n3 + 9)))),
+                           more_keys=('S', 'C', 'L0'))
         if state is None:
             if lattices is not None:
                 L0 = self._lats_and_invs(lattices, B, lattice)[0]
@@ -601,41 +624,22 @@ class GDMLPredict(object):
                     raise ValueError('relax_cell needs a lattice: the model has none and none was given')
                 L0 = np.broadcast_to(lat_and_inv[0], (B, 3, 3))
             S, Cc = R0, np.broadcast_to(float(cell_factor) * np.eye(3), (B, 3, 3))
-            fire = dict(V=np.zeros((B, n3 + 9)), dt=np.full(B, float(dt_start)), alpha=np.full(B, float(alpha_start)),
-                        n_pos=np.zeros(B, dtype=np.int64), n_taken=np.zeros(B, dtype=np.int64))
         else:
-            missing = [k for k in ('S', 'C', 'L0', 'V', 'dt', 'alpha', 'n_pos', 'n_taken') if k not in state]
-            if missing:
-                raise ValueError('state lacks {}'.format(missing))
-            for k, shp in (('S', (B, n3)), ('C', (B, 3, 3)), ('L0', (B, 3, 3)), ('V', (B, n3 + 9))):
-                if np.shape(state[k]) != shp:
-                    raise ValueError("state['{}'] must have shape {}, got {}".format(k, shp, np.shape(state[k])))
-            if not all(np.isfinite(np.asarray(state[k], dtype=np.float64)).all() for k in ('V', 'dt', 'alpha')):
-                raise ValueError('state must be finite')
-            S, Cc, L0, fire = state['S'], state['C'], state['L0'], state
+            S, Cc, L0 = state['S'], state['C'], state['L0']
         # a NaN start is not a usage error: the run reports the geometry and the evaluation (FloatingPointError)
         out = self._ctx.cell_relax_run(S, Cc, L0, fmax, max_steps, fire, dt_max, pressure=pressure, cell_factor=cell_factor,
                                        mask=mask, max_step=max_step, n_min=n_min, f_inc=f_inc, f_dec=f_dec,
                                        alpha_start=alpha_start, f_alpha=f_alpha, f_scale=self.std * float(f_unit),
                                        record_every=record_every)
-        _raise_first_bad(out.pop('first_bad_step'), 'geometry', 'evaluation')
-        status = out.pop('status')
-        out.pop('n_made')
+        out = self._frozen_result(out, 'geometry', ('E_end', 'E_hist'))
         out['state'].update(S=out.pop('S'), C=out.pop('C'), L0=np.array(L0, dtype=np.float64))
         out['lattice_end'] = out.pop('lat_end')
-        out['F_end'] *= self.std
         W = out.pop('W_end')
         W *= self.std
         W /= out['vol_end'].reshape(-1, 1, 1)
         out['stress_end'] = W
-        for k in ('E_end', 'E_hist'):
-            out[k] *= self.std
-            out[k] += self.c
         if 'lat' in out:
             out['lattice'] = out.pop('lat')
-        out['n_steps'] = status[:, 1].copy()
-        out['converged'] = status[:, 0] == 1
-        out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
         return out
 
     # ---- harmonic vibrational analysis on the device (gdml_vib_run, csrc/vib.hip)
@@ -765,17 +769,7 @@ class GDMLPredict(object):
         out = self._ctx.ef_run(R0, fmax, max_steps, state, order=order, trust_min=trust_min, trust_max=trust_max,
                                project=self._VIB_PROJECT[project], f_scale=self.std * float(f_unit),
                                record_every=record_every, lat_and_inv=lat_and_inv)
-        _raise_first_bad(out.pop('first_bad_step'), 'geometry', 'evaluation')
-        status = out.pop('status')
-        out.pop('n_made')
-        out['F_end'] *= self.std
-        for k in ('E_end', 'E_hist'):
-            out[k] *= self.std
-            out[k] += self.c
-        out['n_steps'] = status[:, 1].copy()
-        out['converged'] = status[:, 0] == 1
-        out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
-        return out
+        return self._frozen_result(out, 'geometry', ('E_end', 'E_hist'))
 
     @staticmethod
     def harmonic_thermo(w2_vib, kT, hbar):
@@ -859,40 +853,16 @@ class GDMLPredict(object):
         B, P = R_path.shape[:2]
         if not 3 <= P <= 128:
             raise ValueError('a band needs 3 to 128 images, got {}'.format(P))
-        if dt_max is None:
-            dt_max = 10.0 * dt_start
-        _check_finite(('fmax', fmax), ('k_spring', k_spring), ('dt_start', dt_start), ('dt_max', dt_max), ('max_step', max_step),
-                      ('f_inc', f_inc), ('f_dec', f_dec), ('alpha_start', alpha_start), ('f_alpha', f_alpha), ('f_unit', f_unit))
-        if not k_spring > 0.0:
-            raise ValueError('k_spring must be positive')
-        if int(max_steps) != max_steps or int(record_every) != record_every or int(n_min) != n_min:
-            raise ValueError('max_steps, record_every and n_min must be integers')
-        if state is None:
-            state = dict(V=np.zeros((B, P, n3)), dt=np.full(B, float(dt_start)), alpha=np.full(B, float(alpha_start)),
-                         n_pos=np.zeros(B, dtype=np.int64), n_taken=np.zeros(B, dtype=np.int64))
-        else:
-            missing = [k for k in ('V', 'dt', 'alpha', 'n_pos', 'n_taken') if k not in state]
-            if missing:
-                raise ValueError('state lacks {}'.format(missing))
-            if np.shape(state['V']) != R_path.shape:
-                raise ValueError("state['V'] must have the shape of R_path {}, got {}".format(R_path.shape, np.shape(state['V'])))
-            if not all(np.isfinite(np.asarray(state[k], dtype=np.float64)).all() for k in ('V', 'dt', 'alpha')):
-                raise ValueError('state must be finite')
+        dt_max = _fire_checks(fmax, dt_start, dt_max, max_step, f_inc, f_dec, alpha_start, f_alpha, f_unit, n_min, max_steps,
+                              record_every, after_fmax=(('k_spring', k_spring),), positive=('k_spring', k_spring))
+        state = _fire_state(state, B, R_path.shape, dt_start, alpha_start,
+                            (('V', R_path.shape, "state['V'] must have the shape of R_path {}, got {}"),))
         # a NaN image is not a usage error: the run reports the band and the evaluation (FloatingPointError)
         out = self._ctx.neb_run(R_path, fmax, k_spring, max_steps, state, dt_max, climb=climb, max_step=max_step, n_min=n_min,
                                 f_inc=f_inc, f_dec=f_dec, alpha_start=alpha_start, f_alpha=f_alpha,
                                 f_scale=self.std * float(f_unit), record_every=record_every,
                                 lat_and_inv=self._lat_and_inv(lattice))
-        _raise_first_bad(out.pop('first_bad_step'), 'band', 'evaluation')
-        status = out.pop('status')
-        out.pop('n_made')
-        out['F_end'] *= self.std
-        for k in ('E_end', 'Emax_hist'):
-            out[k] *= self.std
-            out[k] += self.c
-        out['n_steps'] = status[:, 1].copy()
-        out['converged'] = status[:, 0] == 1
-        out['fmax_end'] = out['fmax_hist'][status[:, 1], np.arange(B)] if B else np.empty(0)
+        out = self._frozen_result(out, 'band', ('E_end', 'Emax_hist'))
         E_top = out['E_end'][np.arange(B), out['i_climb']] if B else np.empty(0)
         out['barrier'] = np.stack([E_top - out['E_end'][:, 0], E_top - out['E_end'][:, -1]], axis=1)
         return out

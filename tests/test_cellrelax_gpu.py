@@ -4,6 +4,7 @@ convergence; end state against the per-geometry-lattice predictor; determinism, 
 bit; geometries that finish at different steps; frames; edges and error paths."""
 import ctypes as C
 import functools
+import itertools
 import os
 import sys
 
@@ -385,3 +386,31 @@ def test_wrong_atom_count_and_missing_model():
             empty.cell_relax_run(st['S'], st['C'], st['L0'], fmax, 5, st, 1.0, cell_factor=6.0)
     finally:
         empty.close()
+
+
+# ---- budgets on the edges of a chunk
+
+@functools.lru_cache(maxsize=None)
+def _whole_toy_run():
+    return _toy_predictor().relax_cell(**_toy_kw(record_every=1))
+
+
+def test_budgets_on_chunk_edges_are_the_whole_runs_first_rows():
+    """Chunks of 4 evaluations; budgets of 1, 4, 5, 8 and 9 evaluations (one evaluation, the last row of a chunk, the first
+    row of the next) with no frames, every evaluation a frame and every third: every history and both frame arrays are, bit
+    for bit, the first rows of the run to convergence at default options."""
+    whole = _whole_toy_run()
+    pred = _toy_predictor()
+    try:
+        pred._ctx.set_option('predict.relax_chunk_steps', 4)
+        for max_steps, every in itertools.product((0, 3, 4, 7, 8), (0, 1, 3)):
+            o = pred.relax_cell(**_toy_kw(max_steps=max_steps, record_every=every))
+            n = min(max_steps + 1, whole['E_hist'].shape[0])
+            for k in ('E_hist', 'vol_hist', 'fmax_hist'):
+                assert o[k].shape[0] == n and np.array_equal(o[k], whole[k][:n]), (k, max_steps, every)
+            for k in ('R', 'lattice'):
+                assert (k in o) == (every > 0)
+                if every:
+                    assert np.array_equal(o[k], whole[k][:n][::every]), (k, max_steps, every)
+    finally:
+        pred._ctx.set_option('predict.relax_chunk_steps', 32)

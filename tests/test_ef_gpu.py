@@ -8,6 +8,7 @@ Hessian noise of 1e-10 max and energy noise of 1e-10 max|E'| -- the predictor's 
 tests/test_ef_cpu.py makes a fair demand: no decision of these runs lies within 1e-6 of its threshold."""
 import ctypes as C
 import functools
+import itertools
 import os
 import sys
 
@@ -259,3 +260,32 @@ def test_error_paths_on_the_device():
     one = pred.stationary_point(R0, 1e-12, max_steps=0)
     assert np.array_equal(one['R_end'], R0) and (one['n_steps'] == 0).all() and not one['converged'].any()
     assert np.array_equal(one['state']['flags'], np.zeros(3, dtype=np.int64))
+
+
+# ---- budgets on the edges of a chunk
+
+@functools.lru_cache(maxsize=None)
+def _whole_batch_run():
+    R0, follow, fmax = _batch()
+    return _toy_pred('band').stationary_point(R0, fmax, follow=follow, max_steps=er.TOY_MAX_STEPS, record_every=1)
+
+
+def test_budgets_on_chunk_edges_are_the_whole_runs_first_rows():
+    """Chunks of 4 evaluations; budgets of 1, 4, 5, 8 and 9 evaluations (one evaluation, the last row of a chunk, the first
+    row of the next) with no frames, every evaluation a frame and every third: the four histories and the frames are, bit for
+    bit, the first rows of the run to convergence at default options."""
+    whole = _whole_batch_run()
+    pred = _toy_pred('band')
+    R0, follow, fmax = _batch()
+    try:
+        pred._ctx.set_option('predict.relax_chunk_steps', 4)
+        for max_steps, every in itertools.product((0, 3, 4, 7, 8), (0, 1, 3)):
+            o = pred.stationary_point(R0, fmax, follow=follow, max_steps=max_steps, record_every=every)
+            n = min(max_steps + 1, whole['E_hist'].shape[0])
+            for k in ('E_hist', 'fmax_hist', 'w_follow_hist', 'k_follow_hist'):
+                assert o[k].shape[0] == n and np.array_equal(o[k], whole[k][:n]), (k, max_steps, every)
+            assert ('R' in o) == (every > 0)
+            if every:
+                assert np.array_equal(o['R'], whole['R'][:n][::every]), (max_steps, every)
+    finally:
+        pred._ctx.set_option('predict.relax_chunk_steps', 32)

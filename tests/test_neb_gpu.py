@@ -2,6 +2,7 @@
 (tests/_neb_ref.py), to convergence on a toy with a barrier, end state against predict(), determinism, continuation, chunking
 and record_every bit for bit, bands that freeze at different evaluations, relax() untouched, edges and error paths."""
 import functools
+import itertools
 import os
 import sys
 
@@ -351,3 +352,30 @@ def test_error_paths_launch_nothing_and_leave_the_predictor_working():
     assert np.array_equal(E, E_ok) and np.array_equal(F, F_ok)
     out = pred.neb(**ok)  # and the band itself still works
     assert (out['n_steps'] == 5).all() and np.isfinite(out['E_end']).all()
+
+
+# ---- budgets on the edges of a chunk
+
+@functools.lru_cache(maxsize=None)
+def _whole_toy_run():
+    return _toy_run('p8_x3', record_every=1)[1]
+
+
+def test_budgets_on_chunk_edges_are_the_whole_runs_first_rows():
+    """Chunks of 4 evaluations; budgets of 1, 4, 5, 8 and 9 evaluations (one evaluation, the last row of a chunk, the first
+    row of the next) with no frames, every evaluation a frame and every third: every history and the frames are, bit for bit,
+    the first rows of the run to convergence at default options."""
+    whole = _whole_toy_run()
+    pred = _toy_predictor()
+    try:
+        pred._ctx.set_option('predict.relax_chunk_steps', 4)
+        for max_steps, every in itertools.product((0, 3, 4, 7, 8), (0, 1, 3)):
+            o = _toy_run('p8_x3', max_steps=max_steps, record_every=every)[1]
+            n = min(max_steps + 1, whole['Emax_hist'].shape[0])
+            for k in ('Emax_hist', 'fmax_hist'):
+                assert o[k].shape[0] == n and np.array_equal(o[k], whole[k][:n]), (k, max_steps, every)
+            assert ('R' in o) == (every > 0)
+            if every:
+                assert np.array_equal(o['R'], whole['R'][:n][::every]), (max_steps, every)
+    finally:
+        pred._ctx.set_option('predict.relax_chunk_steps', 32)

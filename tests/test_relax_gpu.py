@@ -2,6 +2,7 @@
 restatement (tests/_relax_ref.py), to convergence on a bound toy model, end state against predict(), determinism, continuation, chunking
 and record_every bit for bit, replicas that finish at different steps, edges and error paths."""
 import functools
+import itertools
 import os
 import sys
 
@@ -383,3 +384,33 @@ def test_wrong_atom_count_and_missing_model():
             empty.relax_run(starts, fmax, 5, rr.fresh_state(7, 18), 1.0)
     finally:
         empty.close()
+
+
+# ---- budgets on the edges of a chunk
+
+@functools.lru_cache(maxsize=None)
+def _whole_toy_run(route):
+    model, starts, _, fmax = rr.toy()
+    return _toy_predictor(route).relax(starts, fmax, max_steps=200, record_every=1, **rr.TOY_PARAMS['clip'])
+
+
+@pytest.mark.parametrize('route', ['step', 'general'])
+def test_budgets_on_chunk_edges_are_the_whole_runs_first_rows(route):
+    """Chunks of 4 evaluations; budgets of 1, 4, 5, 8 and 9 evaluations (one evaluation, the last row of a chunk, the first
+    row of the next) with no frames, every evaluation a frame and every third: every history and the frames are, bit for bit,
+    the first rows of the run to convergence at default options."""
+    model, starts, _, fmax = rr.toy()
+    whole = _whole_toy_run(route)
+    pred = _toy_predictor(route)
+    try:
+        pred._ctx.set_option('predict.relax_chunk_steps', 4)
+        for max_steps, every in itertools.product((0, 3, 4, 7, 8), (0, 1, 3)):
+            o = pred.relax(starts, fmax, max_steps=max_steps, record_every=every, **rr.TOY_PARAMS['clip'])
+            n = min(max_steps + 1, whole['E_hist'].shape[0])
+            for k in ('E_hist', 'fmax_hist'):
+                assert o[k].shape[0] == n and np.array_equal(o[k], whole[k][:n]), (k, max_steps, every)
+            assert ('R' in o) == (every > 0)
+            if every:
+                assert np.array_equal(o['R'], whole['R'][:n][::every]), (max_steps, every)
+    finally:
+        pred._ctx.set_option('predict.relax_chunk_steps', 32)
