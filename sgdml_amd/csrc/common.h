@@ -282,6 +282,22 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// load(0) + ... + load(n - 1), added in index order; loaded eight at a time, the index clamped to n - 1, so that a batch is
+// eight independent loads behind one wait instead of a chain of load + wait per value
+template <typename Int, typename Load>
+__device__ __forceinline__ double sum_in_order8(Int n, Load load) {
+  double s = 0.0;
+  for (Int i0 = 0; i0 < n; i0 += 8) {
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = load(i0 + u < n ? i0 + u : n - 1);
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (i0 + u < n) s += v[u];
+  }
+  return s;
+}
+
 // internal cross-TU entry points
 int desc_device(gdml_ctx* ctx, const double* d_R, int64_t M, int N, const double* lat,
                 const double* lat_inv, double* d_x, double* d_g);

@@ -737,52 +737,26 @@ __global__ void __launch_bounds__(256, 1) predict_mfma_kernel(PredArgs A, const 
   if (lk == 0 && myq < A.B) A.part_E[(int64_t)split * A.B + myq] = es;
 }
 
-// One workgroup per query: sum the split partials in order, then F = J_x^T F_x.
-// LDSFX = false (D beyond the LDS row, JS = 1): F_x is read where the GEMM pipeline left it.
-template <bool LDSFX>
-__global__ void __launch_bounds__(256) predict_epilogue_kernel(const double* __restrict__ part_F,
-                                                               const double* __restrict__ part_E,
-                                                               const double* __restrict__ gq,
-                                                               int64_t B, int N, int D, int JS,
-                                                               double* __restrict__ E_out,
-                                                               double* __restrict__ F_out) {
-  extern __shared__ __attribute__((aligned(16))) double fxs[];
+// E and F of one query, the half that both epilogue kernels share: the split partials of F_x summed in order into the LDS
+// row fxs (LDSFX = false, D beyond the LDS row and JS = 1: F_x is read where the GEMM pipeline left it), E by thread 0, then
+// F = J_x^T F_x (FGUARD: only where F_out is given).  Returns the F_x row, valid for the whole workgroup.
+// Loads in batches of 8 with clamped indices, sums in the original order: as plain loops every partial (JS of them: 62 for
+// a single query against 1000 training points) and every G entry of the back-projection (N - 1 per output) was one load
+// + s_waitcnt vmcnt(0) -- ~100 dependent memory round trips in the single-geometry latency path.
+template <bool LDSFX, bool FGUARD>
+__device__ __forceinline__ const double* predict_epilogue_ef(const double* __restrict__ part_F, const double* __restrict__ part_E,
+                                                             const double* __restrict__ gq, int64_t B, int N, int D, int JS,
+                                                             double* __restrict__ E_out, double* __restrict__ F_out,
+                                                             double* fxs) {
   const int64_t q = blockIdx.x;
   const int tid = threadIdx.x, T = blockDim.x;
   const double* fx = LDSFX ? fxs : part_F + q * D;
-  // Loads in batches of 8 with clamped indices, sums in the original order: as plain loops every partial (JS of them: 62 for
-  // a single query against 1000 training points) and every G entry of the back-projection (N - 1 per output) was one load
-  // + s_waitcnt vmcnt(0) -- ~100 dependent memory round trips in the single-geometry latency path.
   if (LDSFX) {
-    for (int k = tid; k < D; k += T) {
-      double s = 0.0;
-      for (int sp0 = 0; sp0 < JS; sp0 += 8) {
-        double v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int sp = sp0 + u < JS ? sp0 + u : JS - 1;
-          v[u] = part_F[((int64_t)sp * B + q) * D + k];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (sp0 + u < JS) s += v[u];
-      }
-      fxs[k] = s;
-    }
+    for (int k = tid; k < D; k += T) fxs[k] = sum_in_order8(JS, [&](int sp) { return part_F[((int64_t)sp * B + q) * D + k]; });
   }
-  if (tid == 0 && E_out) {
-    double s = 0.0;
-    for (int sp0 = 0; sp0 < JS; sp0 += 8) {
-      double v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part_E[(int64_t)(sp0 + u < JS ? sp0 + u : JS - 1) * B + q];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (sp0 + u < JS) s += v[u];
-    }
-    E_out[q] = s;
-  }
+  if (tid == 0 && E_out) E_out[q] = sum_in_order8(JS, [&](int sp) { return part_E[(int64_t)sp * B + q]; });
   __syncthreads();
+  if (FGUARD && !F_out) return fx;
   const double* g = gq + q * 3 * D;
   for (int t = tid; t < 3 * N; t += T) {
     const int a = t / 3, al = t - 3 * a;
@@ -808,6 +782,19 @@ __global__ void __launch_bounds__(256) predict_epilogue_kernel(const double* __r
     }
     F_out[q * 3 * N + t] = s;
   }
+  return fx;
+}
+
+// One workgroup per query: sum the split partials in order, then F = J_x^T F_x.
+template <bool LDSFX>
+__global__ void __launch_bounds__(256) predict_epilogue_kernel(const double* __restrict__ part_F,
+                                                               const double* __restrict__ part_E,
+                                                               const double* __restrict__ gq,
+                                                               int64_t B, int N, int D, int JS,
+                                                               double* __restrict__ E_out,
+                                                               double* __restrict__ F_out) {
+  extern __shared__ __attribute__((aligned(16))) double fxs[];
+  predict_epilogue_ef<LDSFX, false>(part_F, part_E, gq, B, N, D, JS, E_out, F_out, fxs);
 }
 
 // predict_epilogue_kernel plus the strain derivative W = dE'/d eps = sum_k F_x[k] g_k (x) d_k of gdml_predict_virial (atoms and
@@ -829,64 +816,8 @@ __global__ void __launch_bounds__(256) predict_epilogue_virial_kernel(const doub
   __shared__ double s_w[4][6];
   const int64_t q = blockIdx.x;
   const int tid = threadIdx.x, T = blockDim.x;
-  const double* fx = LDSFX ? fxs : part_F + q * D;
-  if (LDSFX) {
-    for (int k = tid; k < D; k += T) {
-      double s = 0.0;
-      for (int sp0 = 0; sp0 < JS; sp0 += 8) {
-        double v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int sp = sp0 + u < JS ? sp0 + u : JS - 1;
-          v[u] = part_F[((int64_t)sp * B + q) * D + k];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (sp0 + u < JS) s += v[u];
-      }
-      fxs[k] = s;
-    }
-  }
-  if (tid == 0 && E_out) {
-    double s = 0.0;
-    for (int sp0 = 0; sp0 < JS; sp0 += 8) {
-      double v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part_E[(int64_t)(sp0 + u < JS ? sp0 + u : JS - 1) * B + q];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (sp0 + u < JS) s += v[u];
-    }
-    E_out[q] = s;
-  }
-  __syncthreads();
+  const double* fx = predict_epilogue_ef<LDSFX, true>(part_F, part_E, gq, B, N, D, JS, E_out, F_out, fxs);
   const double* g = gq + q * 3 * D;
-  if (F_out) {
-    for (int t = tid; t < 3 * N; t += T) {
-      const int a = t / 3, al = t - 3 * a;
-      const int other = a == 0 ? 1 : 0;
-      double s = 0.0;
-      for (int m0 = 0; m0 < N && N >= 2; m0 += 8) {
-        double gv[8], fv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int mc = m0 + u < N ? m0 + u : N - 1;
-          const int k = pair_idx(a, mc == a ? other : mc);
-          gv[u] = g[k * 3 + al];
-          fv[u] = fx[k];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int m = m0 + u;
-          if (m < N && m != a) {
-            const double v = gv[u] * fv[u];
-            s += (a < m) ? v : -v;
-          }
-        }
-      }
-      F_out[q * 3 * N + t] = s;
-    }
-  }
   const double* x = xq + q * D;
   double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // xx, yy, zz, yz, xz, xy
   for (int k = tid; k < D; k += T) {

@@ -25,24 +25,11 @@
 //   hess_fx_kernel        per query: the group partials of F_x, E', tau summed in order; F = J_x^T F_x.
 //   hess_epilogue_kernel  per (16-row block of H, query): split partials summed in order, + tau J_x^T J_x - sum F_x grad^2 x
 //                         (both block-sparse), the lower triangle mirrored; H written (B, 3N, 3N) row-major, both triangles.
-// Dispatch: D <= 512 (N <= 32): hess_proj_wave_kernel<KPL> (one wavefront per row group, KPL = D / 64 rounded up to 1, 2,
-// 4, 8); otherwise hess_proj_kernel<KT>, KT = ceil(D / 256) >= 3 rounded up to 4, 8, 16, 32, 48 (N <= 157); above that, or
-// with option predict.hess_generic = 1 (which also skips the wavefront variant), the KT = 0 variant.  d must fit the LDS
-// (D <= 19456, N <= 197): larger molecules are GDML_ERR_UNSUPPORTED.
-// Departure from one fused fp64-MFMA kernel with J_x in LDS: projection and rank-2 update are separate passes through
-// bounded panels, which keeps every N, P, lattice and energy-constraint case on one deterministic path; the rank-2 update
-// is VALU.  The projection pass is the measured bottleneck and the first thing to move onto the MFMA pipe.
-// Workspace (one ctx_slot): batches go through in slices of at most 64 queries and the table rows in chunks sized to
-// ~256 MiB of panels (option predict.hess_chunk_rows caps the chunk, tests).
+// Which projection variant serves a call, the slices, chunks, groups and splits, and the workspace: hess_plan.h.
 #include "common.h"
+#include "hess_plan.h"
 
 namespace {
-
-constexpr int HT = 64;           // H tile edge (rank2 / epilogue)
-constexpr int HK = 16;           // table rows per LDS stage of the rank-2 kernel
-constexpr int HE = 16;           // H rows per workgroup of the epilogue
-constexpr int64_t HESS_PANEL_BYTES = 256ll << 20;
-constexpr int64_t HESS_LDS_MAX = 152 * 1024;
 
 struct HessProjArgs {
   const double* xq;   // (bs, D)
@@ -384,18 +371,7 @@ __global__ void __launch_bounds__(256) hess_fx_kernel(const double* __restrict__
                                                       double* __restrict__ F_out) {
   const int q = blockIdx.x, tid = threadIdx.x;
   double* f = fx + (int64_t)q * D;
-  for (int k = tid; k < D; k += 256) {
-    double s = 0.0;
-    for (int64_t g0 = 0; g0 < G; g0 += 8) {
-      double v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part_F[((g0 + u < G ? g0 + u : G - 1) * bs + q) * D + k];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (g0 + u < G) s += v[u];
-    }
-    f[k] = s;
-  }
+  for (int k = tid; k < D; k += 256) f[k] = sum_in_order8(G, [&](int64_t g) { return part_F[(g * bs + q) * D + k]; });
   if (tid == 0) {
     double e = 0.0, t = 0.0;
     for (int64_t g = 0; g < G; ++g) {
@@ -436,16 +412,7 @@ __global__ void __launch_bounds__(256) hess_epilogue_kernel(const double* __rest
   for (int e = tid; e < rows * n3; e += 256) {
     const int il = e / n3, j = e - il * n3, i = I0 + il;
     if (j > i) continue;
-    double s = 0.0;
-    for (int j0 = 0; j0 < JS; j0 += 8) {
-      double v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        v[u] = Hp[(((int64_t)(j0 + u < JS ? j0 + u : JS - 1) * bs + q) * ld + i) * ld + j];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (j0 + u < JS) s += v[u];
-    }
+    const double s = sum_in_order8(JS, [&](int js) { return Hp[(((int64_t)js * bs + q) * ld + i) * ld + j]; });
     const int a = i / 3, c = i - 3 * a, bb = j / 3, c2 = j - 3 * bb;
     double extra = 0.0;
     if (a == bb) {
@@ -470,110 +437,79 @@ __global__ void __launch_bounds__(256) hess_epilogue_kernel(const double* __rest
 
 }  // namespace
 
+// the projection kernel of a plan: one pointer for hipFuncSetAttribute and for the launches; null for a selector no kernel has
+typedef void (*HessProjFn)(HessProjArgs);
+static HessProjFn hess_proj_fn(const HessPlan& p) {
+  if (p.variant == HESS_WAVE) {  // D <= 512: KPL <= 8
+    switch (p.sel) {
+      case 1: return hess_proj_wave_kernel<1>;
+      case 2: return hess_proj_wave_kernel<2>;
+      case 4: return hess_proj_wave_kernel<4>;
+      case 8: return hess_proj_wave_kernel<8>;
+    }
+  } else {  // D > 512 (KT >= 4), or forced KT = 0
+    switch (p.sel) {
+      case 0: return hess_proj_kernel<0>;
+      case 4: return hess_proj_kernel<4>;
+      case 8: return hess_proj_kernel<8>;
+      case 16: return hess_proj_kernel<16>;
+      case 32: return hess_proj_kernel<32>;
+      case 48: return hess_proj_kernel<48>;
+    }
+  }
+  return nullptr;
+}
+
+// Plan (hess_plan.h) -> workspace -> per batch slice: per row chunk projection and rank-2 update, then F_x and the epilogue.
 int hess_device(gdml_ctx* ctx, const double* d_xq, const double* d_gq, int64_t B, double* d_E, double* d_F, double* d_H) {
   Model& md = ctx->model;
   if (!md.xp) return gdml_fail(ctx, GDML_ERR_STATE, "hessian: no model resident");
   if (B == 0) return GDML_OK;
   const int N = md.N, D = md.D, n3 = 3 * N;
   const int64_t MP = md.M * md.P;
-  if ((int64_t)D * 8 > HESS_LDS_MAX)
+  HessPlanIn in;
+  in.N = N; in.MP = MP; in.B = B;
+  in.generic = ctx_opt_i(ctx, "predict.hess_generic", 0);
+  in.chunk_rows = ctx_opt_i(ctx, "predict.hess_chunk_rows", 0);
+  const HessPlan p = hess_plan(in);
+  if (!p.supported)
     return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "hessian: N = %d beyond the LDS row of the projection (N <= 197)", N);
-  const int nb = (n3 + HT - 1) / HT, ld = nb * HT, n_tp = nb * (nb + 1) / 2;
-  int kt = (D + 255) / 256;
-  int KT = 1;
-  while (KT < kt) KT <<= 1;
-  if (KT == 64 && kt <= 48) KT = 48;
-  if (kt > 48 || ctx_opt_i(ctx, "predict.hess_generic", 0)) KT = 0;
-  // wavefront-per-row-group projection for small descriptors (D <= 512; at D = 861 it ran at half the block variant's rate)
-  int KPL = 1;
-  while (KPL * 64 < D) KPL <<= 1;
-  const bool wave = D <= 512 && !ctx_opt_i(ctx, "predict.hess_generic", 0);
-  const int v_lds = wave || (int64_t)2 * D * 8 <= HESS_LDS_MAX;
-  const size_t lds_bytes = wave ? (size_t)8 * D * 8 : (size_t)(v_lds ? 2 : 1) * D * 8;
 
-  // batch slice (bounded partial-H workspace), rows per projection group, row chunk, rank-2 splits
-  int64_t Bs = B < 64 ? B : 64;
-  while (Bs > 1 && Bs * (int64_t)ld * ld * 8 > HESS_PANEL_BYTES) Bs >>= 1;
-  int64_t nr_cap = HESS_PANEL_BYTES / (Bs * ((int64_t)ld * 16 + 16));
-  const int64_t cap_opt = ctx_opt_i(ctx, "predict.hess_chunk_rows", 0);
-  if (cap_opt > 0 && cap_opt < nr_cap) nr_cap = cap_opt;
-  if (nr_cap > MP) nr_cap = MP;
-  int RG = 256;  // rows per group (a workgroup, or a wavefront of the wave variant): enough groups per chunk to fill the chip
-  while (RG > (wave ? 4 : 8) && ((nr_cap + RG - 1) / RG) * Bs < 4096) RG >>= 1;
-  nr_cap = (nr_cap + RG - 1) / RG * RG;  // a multiple of RG: every chunk but the last has full groups
-  // groups of the first (largest) chunk; later chunks add their group partials of F_x, E', tau onto these
-  const int64_t G = ((MP < nr_cap ? MP : nr_cap) + RG - 1) / RG;
-  int64_t JS = (1024 + n_tp * Bs - 1) / (n_tp * Bs);
-  const int64_t js_max = nr_cap / 64 > 1 ? nr_cap / 64 : 1;
-  if (JS > js_max) JS = js_max;
-  if (JS < 1) JS = 1;
-
-  const int64_t nU = Bs * nr_cap * ld, nCS = Bs * nr_cap * 2, nPF = G * Bs * D, nPE = G * Bs * 2,
-                nHp = JS * Bs * (int64_t)ld * ld, nFX = Bs * (int64_t)D;
   double* ws;
-  GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, (2 * nU + nCS + nPF + nPE + nHp + nFX + Bs) * 8, &ws));
-  double* U = ws;
-  double* W = U + nU;
-  double* cs = W + nU;
-  double* part_F = cs + nCS;
-  double* part_ET = part_F + nPF;
-  double* Hp = part_ET + nPE;
-  double* fx = Hp + nHp;
-  double* tau = fx + nFX;
+  GDML_TRY(ctx_slot(ctx, SLOT_PREDICT_WS, p.ws_bytes, &ws));
+  const struct { double *U, *W, *cs, *part_F, *part_ET, *Hp, *fx, *tau; } w = {
+      ws, ws + p.oW, ws + p.oCS, ws + p.oPF, ws + p.oPE, ws + p.oHp, ws + p.oFX, ws + p.oTau};
 
-  const void* proj_fn = nullptr;
-  if (wave) {  // D <= 512: KPL <= 8
-    switch (KPL) {
-#define HW(v) case v: proj_fn = (const void*)hess_proj_wave_kernel<v>; break;
-      HW(1) HW(2) HW(4) HW(8)
-#undef HW
-      default: return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "hessian: bad lane tile %d", KPL);
-    }
-  } else {  // D > 512 (KT >= 4), or forced KT = 0
-    switch (KT) {
-#define HP(v) case v: proj_fn = (const void*)hess_proj_kernel<v>; break;
-      HP(0) HP(4) HP(8) HP(16) HP(32) HP(48)
-#undef HP
-      default: return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, "hessian: bad register tile %d", KT);
-    }
-  }
-  if (lds_bytes > 64 * 1024) HIP_CHECK(ctx, hipFuncSetAttribute(proj_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  const HessProjFn proj = hess_proj_fn(p);
+  if (!proj)
+    return gdml_fail(ctx, GDML_ERR_UNSUPPORTED, p.variant == HESS_WAVE ? "hessian: bad lane tile %d" : "hessian: bad register tile %d",
+                     p.sel);
+  if (p.lds_bytes > 64 * 1024)
+    HIP_CHECK(ctx, hipFuncSetAttribute((const void*)proj, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
 
-  for (int64_t b0 = 0; b0 < B; b0 += Bs) {
-    const int bs = (int)(B - b0 < Bs ? B - b0 : Bs);
+  for (int64_t b0 = 0; b0 < B; b0 += p.Bs) {
+    const int bs = p.slice(b0);
     const double* xq = d_xq + b0 * D;
     const double* gq = d_gq + b0 * 3 * D;
     const int slot = ktime_begin(ctx);
-    for (int64_t r0 = 0; r0 < MP; r0 += nr_cap) {
-      const int64_t nr = MP - r0 < nr_cap ? MP - r0 : nr_cap;
+    for (int64_t r0 = 0; r0 < MP; r0 += p.nr_cap) {
+      const HessChunk c = p.chunk(r0);
       HessProjArgs P;
       P.xq = xq; P.gq = gq; P.xp = md.xp; P.jap = md.jap; P.aE = md.has_aE ? md.aE : nullptr;
-      P.D = D; P.N = N; P.n3 = n3; P.ld = ld; P.RG = RG; P.bs = bs; P.v_lds = v_lds; P.sig = md.sig;
-      P.r0 = r0; P.nr = nr; P.nr_cap = nr_cap;
-      P.U = U; P.W = W; P.cs = cs; P.part_F = part_F; P.part_ET = part_ET;
-      const int64_t ng = (nr + RG - 1) / RG;
-      dim3 pg((unsigned)(wave ? (ng + 3) / 4 : ng), (unsigned)bs);
-      if (wave) {
-        switch (KPL) {
-#define HL(v) case v: hipLaunchKernelGGL(hess_proj_wave_kernel<v>, pg, dim3(256), lds_bytes, ctx->stream, P); break;
-          HL(1) HL(2) HL(4) HL(8)
-#undef HL
-        }
-      } else switch (KT) {
-#define HL(v) case v: hipLaunchKernelGGL(hess_proj_kernel<v>, pg, dim3(256), lds_bytes, ctx->stream, P); break;
-        HL(0) HL(4) HL(8) HL(16) HL(32) HL(48)
-#undef HL
-      }
+      P.D = D; P.N = N; P.n3 = n3; P.ld = p.ld; P.RG = p.RG; P.bs = bs; P.v_lds = p.v_lds; P.sig = md.sig;
+      P.r0 = r0; P.nr = c.nr; P.nr_cap = p.nr_cap;
+      P.U = w.U; P.W = w.W; P.cs = w.cs; P.part_F = w.part_F; P.part_ET = w.part_ET;
+      hipLaunchKernelGGL(proj, dim3(c.grid_x, (unsigned)bs), dim3(256), p.lds_bytes, ctx->stream, P);
       HessRank2Args R2;
-      R2.U = U; R2.W = W; R2.cs = cs; R2.nr = nr; R2.nr_cap = nr_cap; R2.rps = (nr + JS - 1) / JS;
-      R2.ld = ld; R2.bs = bs; R2.accumulate = r0 > 0; R2.Hp = Hp;
-      hipLaunchKernelGGL(hess_rank2_kernel, dim3((unsigned)n_tp, (unsigned)bs, (unsigned)JS), dim3(256), 0, ctx->stream, R2);
+      R2.U = w.U; R2.W = w.W; R2.cs = w.cs; R2.nr = c.nr; R2.nr_cap = p.nr_cap; R2.rps = c.rps;
+      R2.ld = p.ld; R2.bs = bs; R2.accumulate = c.accumulate; R2.Hp = w.Hp;
+      hipLaunchKernelGGL(hess_rank2_kernel, dim3((unsigned)p.n_tp, (unsigned)bs, (unsigned)p.JS), dim3(256), 0, ctx->stream, R2);
       ctx->launch_counter += 2;
     }
-    hipLaunchKernelGGL(hess_fx_kernel, dim3((unsigned)bs), dim3(256), 0, ctx->stream, part_F, part_ET, G, bs, N, D, gq, fx,
-                       tau, d_E ? d_E + b0 : nullptr, d_F ? d_F + b0 * n3 : nullptr);
-    hipLaunchKernelGGL(hess_epilogue_kernel, dim3((unsigned)((n3 + HE - 1) / HE), (unsigned)bs), dim3(256), 0, ctx->stream, Hp, (int)JS, bs, ld,
-                       N, D, xq, gq, fx, tau, d_H + b0 * n3 * (int64_t)n3);
+    hipLaunchKernelGGL(hess_fx_kernel, dim3((unsigned)bs), dim3(256), 0, ctx->stream, w.part_F, w.part_ET, p.G, bs, N, D, gq, w.fx,
+                       w.tau, d_E ? d_E + b0 : nullptr, d_F ? d_F + b0 * n3 : nullptr);
+    hipLaunchKernelGGL(hess_epilogue_kernel, dim3((unsigned)((n3 + HE - 1) / HE), (unsigned)bs), dim3(256), 0, ctx->stream, w.Hp,
+                       (int)p.JS, bs, p.ld, N, D, xq, gq, w.fx, w.tau, d_H + b0 * n3 * (int64_t)n3);
     ctx->launch_counter += 2;
     // algorithmic work per Hessian and table row: rank-2 update 36 N^2, projections 24 D, coefficients and F_x 9 D
     ktime_end(ctx, slot, "hessian", (double)bs * (double)MP * (36.0 * N * (double)N + 33.0 * D));

@@ -256,14 +256,16 @@ HESS_LDS_MAX = 152 * 1024
 
 
 def hess_plan(N, MP, B, generic=0, chunk_rows=0):
-    """What hess_device (csrc/predict_hess.hip:477-509 and the loops at :542-570) does for N atoms, MP table rows and B
-    queries under the options predict.hess_generic and predict.hess_chunk_rows.  None when the library refuses the size."""
+    """What hess_device (csrc/predict_hess.hip) does for N atoms, MP table rows and B queries under the options
+    predict.hess_generic and predict.hess_chunk_rows: an independent restatement of the arithmetic that csrc/hess_plan.h
+    compiles, written from the host code as it stood before that header existed.  tests/test_hess_plan_cpu.py pins the two to
+    each other field by field.  None when the library refuses the size."""
     D, n3 = N * (N - 1) // 2, 3 * N
-    if D * 8 > HESS_LDS_MAX:  # :479
+    if D * 8 > HESS_LDS_MAX:
         return None
-    nb = (n3 + HT - 1) // HT  # :481
+    nb = (n3 + HT - 1) // HT
     ld, n_tp = nb * HT, nb * (nb + 1) // 2
-    kt = (D + 255) // 256  # :482-486
+    kt = (D + 255) // 256
     KT = 1
     while KT < kt:
         KT <<= 1
@@ -271,35 +273,39 @@ def hess_plan(N, MP, B, generic=0, chunk_rows=0):
         KT = 48
     if kt > 48 or generic:
         KT = 0
-    KPL = 1  # :488-492
+    KPL = 1
     while KPL * 64 < D:
         KPL <<= 1
     wave = D <= 512 and not generic
     v_lds = int(wave or 2 * D * 8 <= HESS_LDS_MAX)
-    Bs = min(B, 64)  # :495-500
+    lds_bytes = 8 * D * 8 if wave else (2 if v_lds else 1) * D * 8
+    Bs = min(B, 64)
     while Bs > 1 and Bs * ld * ld * 8 > HESS_PANEL_BYTES:
         Bs >>= 1
     nr_cap = HESS_PANEL_BYTES // (Bs * (ld * 16 + 16))
     if 0 < chunk_rows < nr_cap:
         nr_cap = chunk_rows
     nr_cap = min(nr_cap, MP)
-    RG = 256  # :501-503
+    RG = 256
     while RG > (4 if wave else 8) and ((nr_cap + RG - 1) // RG) * Bs < 4096:
         RG >>= 1
     nr_cap = (nr_cap + RG - 1) // RG * RG
-    G = (min(MP, nr_cap) + RG - 1) // RG  # :505
-    JS = (1024 + n_tp * Bs - 1) // (n_tp * Bs)  # :506-509
+    G = (min(MP, nr_cap) + RG - 1) // RG
+    JS = (1024 + n_tp * Bs - 1) // (n_tp * Bs)
     JS = max(1, min(JS, max(nr_cap // 64, 1)))
-    slices = [min(Bs, B - b0) for b0 in range(0, B, Bs)]  # :542-543
-    chunks = [min(nr_cap, MP - r0) for r0 in range(0, MP, nr_cap)]  # :547-548
-    rps = [(nr + JS - 1) // JS for nr in chunks]  # :568
-    groups = [(nr + RG - 1) // RG for nr in chunks]  # :554
+    nU = Bs * nr_cap * ld
+    ws = [nU, nU, Bs * nr_cap * 2, G * Bs * D, G * Bs * 2, JS * Bs * ld * ld, Bs * D, Bs]  # U W cs part_F part_ET Hp fx tau
+    slices = [min(Bs, B - b0) for b0 in range(0, B, Bs)]
+    chunks = [min(nr_cap, MP - r0) for r0 in range(0, MP, nr_cap)]
+    rps = [(nr + JS - 1) // JS for nr in chunks]
+    groups = [(nr + RG - 1) // RG for nr in chunks]
     return dict(
         N=N, D=D, n3=n3, MP=MP, B=B, variant=('wave', KPL) if wave else ('block', KT), forced=bool(generic), v_lds=v_lds,
-        nb=nb, Bs=Bs, slices=slices, RG=RG, nr_cap=nr_cap, G=G, JS=JS, chunks=chunks, rps=rps,
+        lds_bytes=lds_bytes, nb=nb, ld=ld, n_tp=n_tp, Bs=Bs, slices=slices, RG=RG, nr_cap=nr_cap, G=G, JS=JS, ws=ws,
+        ws_bytes=8 * sum(ws), chunks=chunks, rps=rps, groups=groups,
         last_group_rows=[nr - (ng - 1) * RG for nr, ng in zip(chunks, groups)],
-        idle_waves=[(-ng) % 4 if wave else 0 for ng in groups],  # wavefronts of the last workgroup past the last group (:555)
-        empty_splits=[JS - (nr + r - 1) // r for nr, r in zip(chunks, rps)],  # splits with k0 >= nr (:321-322)
+        idle_waves=[(-ng) % 4 if wave else 0 for ng in groups],  # wavefronts of the last workgroup past the last group
+        empty_splits=[JS - (nr + r - 1) // r for nr, r in zip(chunks, rps)],  # splits that begin at or past the chunk's end
         rps_mod16=[r % HK for r in rps])
 
 
@@ -317,6 +323,12 @@ ROW_CASES = [(1, 1, 0), (4, 1, 0), (5, 3, 0), (63, 1, 0), (64, 1, 0), (65, 1, 0)
              (600, 1, 0), (600, 64, 0), (600, 65, 0), (600, 129, 0), (600, 1, 200), (265, 1, 256), (70, 65, 16),
              (600, 65, 100), (265, 1, 128), (1024, 64, 0)]
 ROW_N = (12, 33)
+
+
+def grid_plan_inputs():
+    """(N, M P, B, predict.hess_generic, predict.hess_chunk_rows) of every call of the grid."""
+    inputs = [(N, size_case(N)['M'] * size_case(N)['P'], 2, 0, 0) for N in SIZE_N]
+    return inputs + [(N, MP, B, generic, chunk) for N in ROW_N for generic in (0, 1) for MP, B, chunk in ROW_CASES]
 
 
 def size_case(N):

@@ -113,9 +113,7 @@ def test_long_double_reference_sees_the_zero_distance_row():
 
 
 def _grid_plans():
-    plans = [hr.hess_plan(N, hr.size_case(N)['M'] * hr.size_case(N)['P'], 2) for N in hr.SIZE_N]
-    plans += [hr.hess_plan(N, MP, B, generic, chunk) for N in hr.ROW_N for generic in (0, 1) for MP, B, chunk in hr.ROW_CASES]
-    return plans
+    return [hr.hess_plan(*a) for a in hr.grid_plan_inputs()]
 
 
 def test_plan_restates_the_documented_cases():

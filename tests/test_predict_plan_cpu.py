@@ -35,7 +35,7 @@ FIELDS = ('route', 'sel', 'QB', 'grid_x', 'grid_y', 'block', 'JS', 'rps', 'lds',
 
 def _parent_plan(N, MP, B, ncu, virial, wave_only, mfma, mfma_wide, fill):
     """predict_device_w of 136c553 (see the module docstring); integer division is C's on non-negative values."""
-    MQ, MR, PQ, PR = 64, 16, 32, 32  # predict.hip:275-276, 490-491
+    MQ, MR, PQ, PR = 64, 16, 32, 32  # the tile constants of predict_plan.h
     D = N * (N - 1) // 2
     KPL = 1
     while KPL * 64 < D:
