@@ -669,7 +669,8 @@ int gdml_predict_virial_cells_dev(gdml_ctx* ctx, const double* R_dev, int64_t B,
  *   cell relaxation needs a lattice per geometry), Cc or output array; an L0 or C that is not finite or singular (|det| at
  *   most 1e-12 of the cube of its largest entry); mask entries other than 0 and 1 or an asymmetric mask; cell_factor <= 0 or
  *   not finite; a non-finite pressure.  GDML_ERR_STATE without a model.
- * Not offered: hydrostatic-only and constant-volume modes, the exponential (Frechet) cell parametrisation, L-BFGS, NPT. */
+ * Not offered: hydrostatic-only and constant-volume modes, the exponential (Frechet) cell parametrisation, L-BFGS.  (Dynamics at
+ *   a pressure: gdml_npt_run.) */
 typedef struct gdml_cell_relax_params {
   int64_t B;
   int N;
@@ -687,6 +688,80 @@ int gdml_cell_relax_run(gdml_ctx* ctx, const gdml_cell_relax_params* params, dou
                         double* R_rec, double* lat_rec, double* E_hist, double* vol_hist, double* fmax_hist, double* R_end,
                         double* lat_end, double* E_end, double* F_end, double* W_end, double* vol_end, int64_t* status,
                         int64_t* first_bad_step);
+
+/* Constant-pressure molecular dynamics on the device: B independent replicas of a PERIODIC model under the isotropic
+ * Martyna-Tobias-Klein (MTK) equations -- density, thermal expansion, compressibility.  Positions, velocities, forces, virial,
+ * the log-scale eps of the cell and the piston momentum p_eps stay resident in device memory; the host sees recorded frames
+ * only.  Two modes: NPH (thermostat 0; no thermostat, piston undamped; it has a conserved quantity) and NPT (thermostat 1;
+ * Langevin on the particles and on the piston, a Langevin piston; samples the isothermal-isobaric ensemble).  The model users
+ * know is ASE's NPT around a calculator, one host round trip and one stress prediction per replica and step.
+ * Per replica:
+ *   - the masses are m, N_f = 3N and kappa = 1 + 3/N_f;
+ *   - f = f_scale F' and Wv = f_scale W', the library's unscaled force and strain derivative (gdml_predict_virial), with
+ *     f_scale = std times the caller's unit factor;  K = sum m v^2 / 2;
+ *   - the reference lattice is L0 with inverse L0^-1 and V0 = |det L0|;  the state is (r, v, eps, p_eps);
+ *   - the cell is lambda = exp(eps), L = lambda L0, L^-1 = L0^-1 / lambda (entry by entry) and Vol = lambda^3 V0; eps = 0 gives
+ *     L0's bits exactly;
+ *   - the piston has mass Wp and rate alpha = p_eps / Wp.  Wp = +inf is allowed and makes alpha exactly 0;
+ *   - G_eps = kappa 2K - tr(Wv) - 3 P_ext Vol.
+ * Step t, with step = step0 + t:
+ *   1. p_eps += dt/2 G_eps, from the K, tr Wv and Vol of the current state.
+ *   2. alpha = p_eps / Wp and s = exp(-kappa alpha dt/4).  Then v <- s v, v <- v + dt/2 f/m, v <- s v.
+ *   3. The drift depends on the thermostat.
+ *      No thermostat: q = exp(alpha dt/2).  Then r <- q r, r <- r + dt v, r <- q r, and eps += alpha dt.
+ *      Langevin:      q = exp(alpha dt/4).  Then r <- q r, r <- r + dt/2 v, r <- q r, and eps += alpha dt/2.
+ *                     v <- c1 v + c2 sqrt(kT/m) xi_k and p_eps <- b1 p_eps + b2 sqrt(Wp kT) xi_3N, with alpha = p_eps / Wp
+ *                     afterwards.  The same half drift again with the new alpha.
+ *                     c1 = exp(-gamma dt), c2 = sqrt(1 - c1^2);  b1 = exp(-gamma_baro dt), b2 = sqrt(1 - b1^2).
+ *                     xi_k is gdml_md_run's stream at (seed, step, replica, coordinate k), k < 3N.  The piston takes
+ *                     coordinate index 3N of the same replica.  The particle noise is therefore gdml_md_run's, and
+ *                     gdml_md_noise(seed, step, B, 3N + 1) returns everything a step consumes.
+ *                     With Wp = inf, b2 sqrt(Wp kT) is not evaluated: the piston is not thermostatted, p_eps stays finite.
+ *   4. E', F', W' = gdml_predict_virial_cells_dev(r, L, L^-1) for all B replicas.
+ *   5. s = exp(-kappa alpha dt/4) with the current alpha.  Then v <- s v, v <- v + dt/2 f/m, v <- s v.
+ *   6. K is summed by gdml_md_run's tree.  Then p_eps += dt/2 G_eps.
+ * A frame holds the state after step 6.  Every scaling and kick is the exact flow of one term.  Within each half step every
+ * scaling uses the same alpha, so the phase-space volume (r, p, Vol, p_eps) is preserved.  The scheme is symmetric and second
+ * order.  In NPH the conserved quantity is H = K + f_unit E + P_ext Vol + p_eps^2 / (2 Wp)  (f_unit E = f_scale E' + const).
+ * Launches per step: npt_pre_kernel (one workgroup of 256 per replica; steps 1-3; writes r, v, eps, p_eps and the replica's L
+ *   and L^-1 for the predictor), the prediction exactly as gdml_predict_virial_cells_dev runs it, npt_post_kernel (one workgroup
+ *   per replica; steps 5-6, the non-finite check and the frame write).  Forces and virial of the start state come from the
+ *   same predictor call before step 0, K of the start from the same tree: a continued run starts from the bits its
+ *   predecessor ended with.  There is NO single-launch route (the single-launch predictor holds one lattice by value).  Chunks
+ *   as in gdml_md_run (64 MiB of frames, 4096 steps, predict.md_chunk_frames).  fp64 throughout, fixed summation orders, no
+ *   floating-point atomics; kicks, drifts and the Ornstein-Uhlenbeck step are written with the fused multiply-adds of
+ *   gdml_md_run's kernels and nothing else is contracted.
+ * Arguments.  R, V (B,3N), eps, p_eps (B): the start state on entry, the end state on return.  L0, L0_inv (B,3,3): reference
+ *   lattices (cell vectors in the columns) and their inverses, both required, read only.  Frame k is the state after step
+ *   (k + 1) record_every, n_rec = n_steps / record_every: R_rec, V_rec, F_rec (n_rec,B,3N; F' unscaled), lat_rec (n_rec,B,3,3),
+ *   each may be NULL; E_rec (n_rec,B) = E' UNSCALED like gdml_md_run's, Ekin_rec = K, vol_rec = Vol, press_rec = P_int =
+ *   (2K - tr Wv) / (3 Vol), peps_rec = p_eps.  first_bad_step (B): as in gdml_md_run; it additionally trips on a non-finite
+ *   eps, p_eps or Vol.  n_steps = 0 returns the start state untouched.
+ * Bit-identical: the same call repeated; n steps followed by n steps from the end state with step0 + n against 2n steps; any
+ *   record_every; any chunk size; E_rec and F_rec of a frame are gdml_predict_virial_cells_dev's for that frame's R_rec and
+ *   lat_rec at the same B.  With Wp = inf and eps = 0 (any pressure): R, V, F, E', K of gdml_md_run's general route
+ *   (predict.md_fused = 0) with lat = L0.
+ * GDML_ERR_INVALID before any launch (ctx may be NULL for these checks): everything gdml_md_run rejects; a NULL eps, p_eps, L0
+ *   or L0_inv; piston_mass <= 0 or NaN; gamma_baro < 0; a non-finite pressure.  GDML_ERR_STATE without a model.
+ * Not offered: anisotropic or fully flexible cells, per-replica pressures, a single-launch route, removal of the centre-of-mass
+ *   momentum (N_f = 3N is deliberate), a barostat for gdml_pimd_run. */
+typedef struct gdml_npt_params {
+  int64_t B;
+  int N;
+  double dt;
+  const double* mass;    /* (N) */
+  double f_scale;        /* f = f_scale * F', Wv = f_scale * W' */
+  int thermostat;        /* 0 none (NPH), 1 Langevin particles and piston (NPT) */
+  double gamma, gamma_baro, kT;
+  uint64_t seed;
+  int64_t step0;
+  double pressure;       /* P_ext, in units of (f_scale E') per length^3 */
+  double piston_mass;    /* Wp > 0; +inf freezes the cell */
+} gdml_npt_params; /* 104 bytes */
+int gdml_npt_run(gdml_ctx* ctx, const gdml_npt_params* params, double* R, double* V, double* eps, double* p_eps,
+                 const double* L0, const double* L0_inv, int64_t n_steps, int64_t record_every, double* R_rec, double* V_rec,
+                 double* F_rec, double* lat_rec, double* E_rec, double* Ekin_rec, double* vol_rec, double* press_rec,
+                 double* peps_rec, int64_t* first_bad_step);
 
 /* Analytic Hessians (force constants) H' = d^2 E' / dR^2 of B geometries, unscaled like gdml_predict (the caller
  * multiplies by std).  The reference has no counterpart: its users take finite differences of predict().

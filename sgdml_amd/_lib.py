@@ -26,6 +26,13 @@ class MDParams(C.Structure):
                 ('step0', C.c_int64)]
 
 
+class NPTParams(C.Structure):
+    """gdml_npt_params (include/gdml_hip.h)."""
+    _fields_ = [('B', C.c_int64), ('N', C.c_int), ('dt', C.c_double), ('mass', _vp), ('f_scale', C.c_double),
+                ('thermostat', C.c_int), ('gamma', C.c_double), ('gamma_baro', C.c_double), ('kT', C.c_double),
+                ('seed', C.c_uint64), ('step0', C.c_int64), ('pressure', C.c_double), ('piston_mass', C.c_double)]
+
+
 class PIMDParams(C.Structure):
     """gdml_pimd_params (include/gdml_hip.h)."""
     _fields_ = [('B', C.c_int64), ('N', C.c_int), ('beads', C.c_int), ('dt', C.c_double), ('mass', _vp), ('f_scale', C.c_double),
@@ -111,6 +118,8 @@ SIGNATURES = {
     'gdml_predict_virial_cells_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_cell_relax_run': (C.c_int, [_vp, C.POINTER(CellRelaxParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64,
                                       C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gdml_npt_run': (C.c_int, [_vp, C.POINTER(NPTParams), _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_predict_hessian_dev': (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     'gdml_sym_eig': (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
@@ -880,6 +889,36 @@ class Context(object):
                     state=dict(V=V, dt=dt, alpha=alpha, n_pos=n_pos, n_taken=n_taken),
                     **_frozen_out(status, bad, record_every, dict(E_hist=E_hist, vol_hist=v_hist, fmax_hist=f_hist),
                                   dict(R=R_rec, lat=lat_rec)))
+
+    def npt_run(self, R, V, eps, p_eps, L0, L0_inv, mass, dt, n_steps, pressure, piston_mass, record_every=1, f_scale=1.0,
+                thermostat=0, gamma=0.0, gamma_baro=0.0, kT=0.0, seed=0, step0=0, record=('R',)):
+        """gdml_npt_run: B periodic replicas (R, V: (B,3N); eps, p_eps: (B); L0, L0_inv: (B,3,3)) advance n_steps at the
+        pressure on the device.  Returns a dict with the end state 'R_end', 'V_end', 'eps_end', 'p_eps_end', the frames 'E' (n_rec,B;
+        unscaled E'), 'Ekin', 'vol', 'press' (P_int), 'peps' (n_rec,B), those of 'R', 'V', 'F' (n_rec,B,3N) and 'lat'
+        (n_rec,B,3,3) named in `record`, and 'first_bad_step' (B; -1 = every value stayed finite)."""
+        n3 = 3 * self.model_n_atoms
+        R, V = _state_copies(R, V, (-1, n3))
+        B = R.shape[0]
+        mass = self._masses(mass)
+        eps, p_eps = np.array(eps, dtype=np.float64).ravel(), np.array(p_eps, dtype=np.float64).ravel()
+        L0, L0_inv = f64(L0), f64(L0_inv)
+        if eps.shape != (B,) or p_eps.shape != (B,):
+            raise ValueError('eps and p_eps must have one entry per replica ({}), got {} and {}'.format(B, eps.shape, p_eps.shape))
+        if L0.shape != (B, 3, 3) or L0_inv.shape != (B, 3, 3):
+            raise ValueError('L0 and L0_inv must be ({}, 3, 3), got {} and {}'.format(B, L0.shape, L0_inv.shape))
+        n_steps, record_every = int(n_steps), int(record_every)
+        n_rec = n_steps // record_every if (n_steps > 0 and record_every > 0) else 0
+        rec = _record_arrays(record, dict({k: (n_rec, B, n3) for k in ('R', 'V', 'F')}, lat=(n_rec, B, 3, 3)))
+        E, Ek, vol, press, peps = (np.empty((n_rec, B)) for _ in range(5))
+        bad = np.full(B, -1, dtype=np.int64)
+        prm = NPTParams(B, self.model_n_atoms, float(dt), _ptr(mass), float(f_scale), int(thermostat), float(gamma),
+                        float(gamma_baro), float(kT), int(seed), int(step0), float(pressure), float(piston_mass))
+        self._check(self._lib.gdml_npt_run(self._h, C.byref(prm), _ptr(R), _ptr(V), _ptr(eps), _ptr(p_eps), _ptr(L0), _ptr(L0_inv),
+                                           n_steps, record_every, _ptr(rec['R']), _ptr(rec['V']), _ptr(rec['F']), _ptr(rec['lat']),
+                                           _ptr(E), _ptr(Ek), _ptr(vol), _ptr(press), _ptr(peps), _ptr(bad)))
+        out = _recorded(rec)
+        out.update(R_end=R, V_end=V, eps_end=eps, p_eps_end=p_eps, E=E, Ekin=Ek, vol=vol, press=press, peps=peps, first_bad_step=bad)
+        return out
 
     def hessian_batch(self):
         """Geometries per gdml_predict_hessian call: max_query_batch scaled down by the 3N-fold larger output (9N^2 vs 3N)."""

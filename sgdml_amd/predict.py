@@ -532,6 +532,107 @@ class GDMLPredict(object):
         out['step_end'] = step0 + int(n_steps)
         return out
 
+    # ---- constant-pressure molecular dynamics on the device (gdml_npt_run, csrc/npt.hip)
+
+    @staticmethod
+    def piston_mass(n_atoms, kT, tau):
+        """The piston mass (3N + 3) kT tau^2 that gives the cell of N atoms at temperature kT the period scale tau."""
+        return (3 * int(n_atoms) + 3) * float(kT) * float(tau) ** 2
+
+    def run_npt(self, R0, V0, masses, dt, n_steps, pressure, piston_mass, record_every=1, thermostat=None, gamma=0.0,
+                gamma_baro=0.0, kT=0.0, seed=0, step0=0, lattice=None, lattices=None, state=None, f_unit=1.0,
+                record=('R', 'E')):
+        """Advance B independent replicas of a PERIODIC model for n_steps at the external pressure on the device: isotropic
+        Martyna-Tobias-Klein dynamics of atoms and cell, the cell of replica b being exp(eps_b) L0_b.  thermostat=None is NPH
+        (it conserves 'enthalpy'); thermostat='langevin' is NPT with a Langevin piston: friction gamma on the particles and
+        gamma_baro on the piston at temperature kT, which samples the isothermal-isobaric ensemble.  R0, V0, masses, dt, seed,
+        step0, f_unit, record_every: as in run_md().  pressure: in (f_unit * the model's energy unit) / length^3.
+        piston_mass: in energy * time^2 (piston_mass(N, kT, tau) gives the usual choice; inf freezes the cell and the run is
+        run_md()'s general route bit for bit).  lattice: one 3 x 3 reference lattice L0 (cell vectors in the columns) for all
+        replicas, default the model's; lattices: (B,3,3), one per replica.  state: the 'state' of an earlier call ({'eps',
+        'p_eps', 'L0'}) passed with its R_end, V_end and step0 = step_end continues that run bit for bit (the lattice arguments
+        are then not used); None starts at eps = 0, p_eps = 0.
+        record: which of 'R', 'V', 'F', 'lattice', 'E' to return per recorded step.  Returns a dict: those of 'R', 'V', 'F'
+        (n_rec,B,3N; F scaled by std) and 'lattice' (n_rec,B,3,3); always 'E_pot' (n_rec,B; scaled like predict()), 'E_kin',
+        'vol', 'pressure' (the internal pressure (2 E_kin - f_unit tr W) / (3 vol)), 'p_eps' and 'enthalpy' = E_kin + f_unit
+        E_pot + pressure vol + p_eps^2 / (2 piston_mass); the end state 'R_end', 'V_end', 'lattice_end', 'vol_end',
+        'step_end' and 'state'.  Runs on the predictor's first device, always on the general prediction route.
+        Not offered: anisotropic or fully flexible cells, per-replica pressures, removal of the centre-of-mass momentum.
+        ValueError before anything is launched; FloatingPointError naming replica and step when a trajectory stops being
+        finite (a cell that collapses or blows up included)."""
+        n3 = 3 * self.n_atoms
+        R0, V0 = _as_batch(R0, n3), _as_batch(V0)
+        B = R0.shape[0]
+        if V0.shape != R0.shape:
+            raise ValueError('V0 must have the shape of R0 {}, got {}'.format(R0.shape, V0.shape))
+        masses = np.asarray(masses, dtype=np.float64)
+        if masses.shape != (self.n_atoms,):
+            raise ValueError('masses must be ({},), got shape {}'.format(self.n_atoms, masses.shape))
+        if not (np.isfinite(R0).all() and np.isfinite(V0).all() and np.isfinite(masses).all()):
+            raise ValueError('R0, V0 and masses must be finite')
+        _check_finite(('dt', dt), ('gamma', gamma), ('gamma_baro', gamma_baro), ('kT', kT), ('f_unit', f_unit),
+                      ('pressure', pressure))
+        if not float(piston_mass) > 0.0:  # (a NaN fails the comparison; inf passes)
+            raise ValueError('piston_mass must be positive (inf freezes the cell)')
+        if thermostat not in (None, 'langevin'):
+            raise ValueError("thermostat must be None or 'langevin', got {!r}".format(thermostat))
+        record = _record_fields(record, ('R', 'V', 'F', 'lattice', 'E'))
+        seed, step0 = int(seed), int(step0)
+        if not 0 <= seed < 2**64:
+            raise ValueError('seed must fit into 64 unsigned bits')
+        if state is None:
+            if lattices is not None:
+                L0, L0_inv = self._lats_and_invs(lattices, B, lattice)
+            else:
+                lat_and_inv = self._lat_and_inv(lattice)
+                if lat_and_inv is None:
+                    raise ValueError('run_npt needs a lattice: the model has none and none was given')
+                L0, L0_inv = (np.broadcast_to(a, (B, 3, 3)) for a in lat_and_inv)
+            eps, p_eps = np.zeros(B), np.zeros(B)
+        else:
+            for k in ('eps', 'p_eps', 'L0'):
+                if k not in state:
+                    raise ValueError("state lacks '{}'".format(k))
+            eps, p_eps = (np.array(state[k], dtype=np.float64) for k in ('eps', 'p_eps'))
+            L0 = np.array(state['L0'], dtype=np.float64)
+            if eps.shape != (B,) or p_eps.shape != (B,) or L0.shape != (B, 3, 3):
+                raise ValueError("state must hold 'eps' and 'p_eps' of shape ({0},) and 'L0' of shape ({0}, 3, 3)".format(B))
+            if not (np.isfinite(eps).all() and np.isfinite(p_eps).all()):
+                raise ValueError("state['eps'] and state['p_eps'] must be finite")
+            # the inverse that the run which made this state used: the model's stored one for the model's own cell
+            L0_inv = np.empty_like(L0)
+            for b in range(B):
+                try:
+                    L0_inv[b] = self._lat_and_inv(L0[b])[1]
+                except ValueError as e:
+                    raise ValueError("state['L0'][{}]: {}".format(b, e))
+        rec = tuple({'lattice': 'lat', 'E': None}.get(k, k) for k in record)
+        out = self._ctx.npt_run(R0, V0, eps, p_eps, L0, L0_inv, masses, dt, n_steps, pressure, piston_mass,
+                                record_every=record_every, f_scale=self.std * float(f_unit),
+                                thermostat=0 if thermostat is None else 1, gamma=gamma, gamma_baro=gamma_baro, kT=kT, seed=seed,
+                                step0=step0, record=rec)
+        _raise_first_bad(out.pop('first_bad_step'), 'replica', 'step')
+        if 'F' in out:
+            out['F'] *= self.std
+        if 'lat' in out:
+            out['lattice'] = out.pop('lat')
+        E = out.pop('E')
+        E *= self.std
+        E += self.c
+        out['E_pot'] = E
+        out['E_kin'] = out.pop('Ekin')
+        out['pressure'] = out.pop('press')
+        p = out['p_eps'] = out.pop('peps')
+        out['enthalpy'] = out['E_kin'] + float(f_unit) * E + float(pressure) * out['vol'] + p * p / (2.0 * float(piston_mass))
+        eps_end = out.pop('eps_end')
+        L0 = np.array(L0, dtype=np.float64)
+        lam = np.exp(eps_end)
+        out['lattice_end'] = lam[:, None, None] * L0
+        out['vol_end'] = lam * lam * lam * np.abs(np.array([det3(L) for L in L0]))
+        out['state'] = dict(eps=eps_end, p_eps=out.pop('p_eps_end'), L0=L0)
+        out['step_end'] = step0 + int(n_steps)
+        return out
+
     # ---- geometry relaxation on the device (gdml_relax_run, csrc/relax.hip)
 
     def relax(self, R0, fmax, max_steps=1000, dt_start=0.1, dt_max=None, max_step=0.2, n_min=5, f_inc=1.1, f_dec=0.5,
@@ -596,7 +697,8 @@ class GDMLPredict(object):
         'stress_end' (B,3,3; W / volume scaled by std, ASE's sign, WITHOUT the external pressure), 'vol_end' (B), 'fmax_end',
         'n_steps', 'converged', 'E_hist', 'vol_hist', 'fmax_hist' (evaluations made, B), 'state', and with record_every > 0
         the frames 'R' and 'lattice'.  Runs on the predictor's first device, always on the general prediction route.
-        Not offered: hydrostatic-only and constant-volume modes, the exponential cell parametrisation, L-BFGS, NPT dynamics.
+        Not offered: hydrostatic-only and constant-volume modes, the exponential cell parametrisation, L-BFGS (dynamics at a pressure:
+        run_npt()).
         ValueError before anything is launched; FloatingPointError naming geometry and evaluation when a value is not finite
         (a cell that collapses to zero volume included)."""
         n3 = 3 * self.n_atoms
