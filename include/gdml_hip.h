@@ -168,7 +168,7 @@ int gdml_kernel_stat(gdml_ctx* ctx, const char* kernel, double* ms_out, int64_t*
  *   pcg.precon_form (2)   application of the Nystroem preconditioner: 0 = stored n x m fp64 factor streamed twice per application
  *                         (the reference's form, iterative.py:120-140); 3 = the factor stored in fp32 plus an m x m Gram
  *                         correction (half the bytes per application; the exact Woodbury inverse on the rounded factor's column
- *                         space: csrc/cg.hip); 2 = automatic: 3 once the factor reaches 1 GiB per rank, else 0; 1 = matrix-free
+ *                         space: csrc/nystroem.hip); 2 = automatic: 3 once the factor reaches 1 GiB per rank, else 0; 1 = matrix-free
  *                         (two kernel mat-vecs + an m x m matrix; experimental: does not converge at lam = 1e-10, never automatic)
  *   pcg.f32_rows_per (1024), pcg.f32_rw (4)  shape of the fp32 form's two GEMVs: rows per partial sum of X32^T v, rows per
  *                         wavefront of X32 t (A/B)

@@ -78,7 +78,7 @@ struct Model {
 // share a slot exactly when none of them runs, or is called, while another's pointer is still in use:
 //   SLOT_PREDICT_WS   predict_fused, the three paths of predict_device and hess_device are alternatives of one call each;
 //                     none calls another (matvec_device -> predict_device holds SLOT_MATVEC_OUT / _VREF, not this one)
-//   SLOT_PRECON_GEMV  the fp32 form (precon_form 3) and the fp64 form are two branches of precon_apply_device
+//   SLOT_PRECON_GEMV  precon_apply_device alone, laid out by precon_apply_plan (precon_plan.h) for the form that is resident
 //   SLOT_PRECON_MF    build_f32_form reads its flag back and synchronises before it goes on, and applies no preconditioner;
 //                     precon_apply_mf calls matvec_device, which requests other slots only
 //   SLOT_GRAM_WS/ROWS every caller of gram_workspace (gdml_uncert_cross, cov_run for the four gdml_predict_cov* entries, gdml_loo,
@@ -163,7 +163,7 @@ struct gdml_ctx {
   int64_t precon_m = 0, precon_n = 0;
   // form of the resident preconditioner (option pcg.precon_form): 0 = the stored n x m factor X = K_nm Z is streamed twice
   // per application; 1 = matrix-free, P v = (K_nm Z Z^T K_mn v - v)/lam through two kernel mat-vecs and the m x m matrix
-  // Z = L_mm^-T L^-T (cg.hip).  precon_stage: triangular solves applied to X so far (1: only L_mm^-T -- the matrix-free
+  // Z = L_mm^-T L^-T (nystroem.hip).  precon_stage: triangular solves applied to X so far (1: only L_mm^-T -- the matrix-free
   // form does not need the second one until somebody asks for leverage scores).
   int precon_form = 0, precon_stage = 2, precon_use_E = 0;
   double precon_sig = 0;
@@ -172,7 +172,7 @@ struct gdml_ctx {
   int64_t* precon_idx = nullptr;  // device copy of the inducing column indices (m)
   int64_t precon_idx_bytes = 0;
   // form 3: the factor rounded to fp32 (n_loc x K_ld floats) + the m x m correction T0 that makes
-  // (X32 T0 X32^T - I)/lam the exact Woodbury inverse on range(X32) (cg.hip)
+  // (X32 T0 X32^T - I)/lam the exact Woodbury inverse on range(X32) (nystroem.hip)
   float* precon_X32 = nullptr;
   int64_t precon_X32_bytes = 0;
   bool precon_X32_inplace = false;        // X32 overlays the fp64 factor in the matrix buffer (row pitch 2 K_ld floats): not ours to free
@@ -258,7 +258,7 @@ int ctx_scratch(gdml_ctx* ctx, int64_t bytes, double** out);
 void phase_begin(gdml_ctx* ctx);
 // kernel timing (no-ops unless ctx->profiling)
 int phase_resolve(gdml_ctx* ctx);  // reads a pending phase timer (waits for its end event)
-void precon_release_f32(gdml_ctx* ctx);  // cg.hip
+void precon_release_f32(gdml_ctx* ctx);  // nystroem.hip
 void precon_release_aux(gdml_ctx* ctx);
 int ktime_begin(gdml_ctx* ctx);  // returns slot or -1
 void ktime_end(gdml_ctx* ctx, int slot, const char* name, double work);
@@ -333,7 +333,7 @@ int launch_panel_trsm(gdml_ctx* ctx, hipStream_t st, const double* L, double* X,
                       int64_t ldl = 0);
 int panel_factor_steps(gdml_ctx* ctx, hipStream_t st, double* A, int64_t n, int64_t ld, int64_t k0, int64_t nb);
 int chol_bwd_device(gdml_ctx* ctx, const double* L, int64_t n, int64_t ld, double* d_z, double* d_x);
-// X[:, 0:m] <- X L^-T for the n rows of X (cg.hip).  look: 1 left-looking, 0 right-looking, -1 = option nys.trsm_left
+// X[:, 0:m] <- X L^-T for the n rows of X (chol_solve.hip).  look: 1 left-looking, 0 right-looking, -1 = option nys.trsm_left
 int tall_trsm(gdml_ctx* ctx, const double* L, double* X, int64_t n, int64_t m, int64_t ld, int look = -1);
 void tile_sched_cache_free(gdml_ctx* ctx);
 int ctx_slot(gdml_ctx* ctx, int slot, int64_t bytes, double** out);
@@ -435,6 +435,18 @@ struct VecLayout {
   }
 };
 VecLayout vec_layout(const gdml_ctx* ctx, int use_E_cstr);
+// ---- Nystroem preconditioner and PCG: gram_tn.hip, nystroem.hip, precon_apply.hip, cg.hip
+// C (m x m, lower tiles) = X^T X over the n rows of X, cut along the rows where that pays (gram_tn.hip); the one-pass kernel
+// alone, launched and not checked
+int gram_tn(gdml_ctx* ctx, const double* X, int64_t ldx, int64_t n, int64_t m, double* Cout, int64_t ldc);
+void launch_gram_one_pass(gdml_ctx* ctx, const double* X, int64_t ldx, int64_t rows, int64_t m, double* C, int64_t ldc);
+// row-shard geometry of the resident Nystroem matrix (nystroem.hip)
+typedef VecLayout ShardGeo;
+ShardGeo shard_geo(const gdml_ctx* ctx);
+// d_out = P d_v on replicated (padded) device vectors, in the resident form (precon_apply.hip)
+int precon_apply_device(gdml_ctx* ctx, double lam, const double* d_v, double* d_out);
+// y += a x over n entries (cg.hip), launched and not checked
+void launch_vec_axpy(gdml_ctx* ctx, double* y, const double* x, double a, int64_t n);
 // host vector (reference order, L.n entries) -> zero-padded device vector of L.n_pad entries, and back (synchronous)
 int vec_upload(gdml_ctx* ctx, const VecLayout& L, const double* host_ref, double* dev);
 int vec_download(gdml_ctx* ctx, const VecLayout& L, const double* dev, double* host_ref, hipStream_t st = nullptr);

@@ -4,7 +4,7 @@
 // Conventions: A = -K + lam I = L L^T resident in ctx->K (lower triangle, row-major, pitch K_ld = n rounded up
 // to 16), n = 3N M.  Appending b points (m = 3N b rows) borders the matrix and its factor:
 //   A' = | A  C^T |     L' = | L  0   |     C   = -Kx of the new points against the old ones  (cross_rows_kernel of uncert.hip)
-//        | C  D   |          | W  L_S |     W   = C L^-T                                       (tall_trsm of cg.hip, right-looking)
+//        | C  D   |          | W  L_S |     W   = C L^-T                                       (tall_trsm of chol_solve.hip, right-looking)
 //                                           S   = D - W W^T = L_S L_S^T                        (block_gram.hip + schur_reduce_kernel,
 //                                                                                               chol_factor_device)
 // The points go through in chunks (option chol.extend_chunk); a chunk's rows are rows of L' once it is through, and the next chunk

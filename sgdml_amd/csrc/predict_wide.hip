@@ -55,7 +55,7 @@ __device__ __forceinline__ void w_store(double* __restrict__ S, int tid, const d
 // P_z[m x n] = A^T B over this split's share of the nk rows;  A: nk x m (lda), B: nk x n (ldb), row-major.  128 x 128 tiles,
 // 16 rows of A / B per k-tile, fp64 MFMA.  Both operand tiles are 16 x 128 blocks with contiguous rows: interior tiles move
 // them in 16-byte pieces (check-free global_load_dwordx4 from a wave-uniform base, ds_write_b128 into an unpadded [k][128]
-// image, one ds_read_b128 per PAIR of operand blocks -- the column-pair relabelling of syrk_tn_kernel, cg.hip).
+// image, one ds_read_b128 per PAIR of operand blocks -- the column-pair relabelling of syrk_tn_kernel, gram_tn.hip).
 //
 // SPLIT-K: the back contraction of the prediction has a short output (queries x D: 16 x 7 tiles at configs[3]) and a very
 // long contraction (the M P table rows: 54 000), so one workgroup per tile leaves most of the chip idle (112 workgroups

@@ -3,7 +3,7 @@
 //
 // Conventions: A = -K + lam I = L L^T resident in ctx->K (lower triangle, row-major, pitch K_ld), n = 3N M,
 // n3 = 3N, the pool holds B candidates (m_pool = n3 B rows).  For candidate q
-//   W_q    = (-Kx_q) L^-T                                  (cross_rows_kernel of uncert.hip, tall_trsm of cg.hip)
+//   W_q    = (-Kx_q) L^-T                                  (cross_rows_kernel of uncert.hip, tall_trsm of chol_solve.hip)
 //   Sig_q  = (-k_qq) - W_q W_q^T                           (block_gram.hip + cov_reduce_kernel: the bits of gdml_predict_cov)
 //   gain_q = log det(Sig_q / lam + I) = 2 sum_i log G_ii - n3 log lam,   G G^T = Sig_q + lam I     (select_score_kernel)
 // Step t picks q* = argmax gain (ties: the lowest pool index; on the host) and conditions the pool on it:

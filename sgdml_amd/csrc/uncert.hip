@@ -5,7 +5,7 @@
 // matrix resident in ctx->K (lower triangle, row-major, pitch K_ld), n = 3N M.  For a query geometry q
 //   Kx_q  (3N x n)   cross-kernel rows: block j = the 3N x 3N block of train.py:97-232 for row point q (un-permuted) and
 //                    column point j (permuted);  k_qq (3N x 3N) the same with i = j = q
-//   Z_q   = (-Kx_q) L^-T                                   (tall_trsm of cg.hip, right-looking: few rows, long factor)
+//   Z_q   = (-Kx_q) L^-T                                   (tall_trsm of chol_solve.hip, right-looking: few rows, long factor)
 //   Sig_q = (-k_qq) - Z_q Z_q^T                            (block_gram.hip + cov_reduce_kernel)
 // in the units of the normalised labels; the host multiplies by std^2 (and its calibration factor).
 //

@@ -2,8 +2,9 @@
 tools/nys_edges_parity.py): plain NumPy / SciPy, no GPU import at module level.  Test helper only: the package never
 imports it.  It builds on tests/_chol_ref.py (reachable, _dummy_set, gamma, U, spd).
 
-The code under test is csrc/cg.hip: gdml_nystroem_factor (K_mm = -K_nm[idx] + eps I = L_mm L_mm^T; X1 = K_nm L_mm^-T;
-X1^T X1 + lam I = L L^T; X2 = X1 L^-T), gdml_nystroem_lev_scores (row sums of X2^2) and gdml_precon_apply
+The code under test is csrc/nystroem.hip (on gram_tn.hip and tall_trsm of chol_solve.hip): gdml_nystroem_factor
+(K_mm = -K_nm[idx] + eps I = L_mm L_mm^T; X1 = K_nm L_mm^-T; X1^T X1 + lam I = L L^T; X2 = X1 L^-T) and
+gdml_nystroem_lev_scores (row sums of X2^2), and csrc/precon_apply.hip: gdml_precon_apply
 (P v = (X2 X2^T v - v) / lam in three forms).  The tests want THEIR matrix at THEIR shape: load_nystroem uploads a dummy
 training set of n rows, lets the library allocate the (n + m) x m buffer and overwrites it.
 
@@ -21,7 +22,7 @@ reads its inputs back from the device, so no conditioning enters; residuals are 
   S5  rounding                 bit comparisons of the in-place fp32 overlay with the separate fp32 copy
 Measured checks (no simple derived bound): M1 form-0 application, M2 form 3, M3 the CholeskyQR branch, M4 the first solve,
 M5 the matrix-free form, each against the long-double reference, error relative to max |reference|.  The allowance of a
-case is 10 x the largest error that the float64 restatement of cg.hip (nys_f64, f32_form_f64, ...) makes against the same
+case is 10 x the largest error that the float64 restatement of these files (nys_f64, f32_form_f64, ...) makes against the same
 reference over three seeds of the matrix and of v: restatement and kernel perform the same roundings in another order,
 the seeds sample the spread between orders, 10 sits an order of magnitude above that spread.  No allowance is ever sized
 from the device's output.
@@ -38,7 +39,7 @@ import _chol_ref as cr
 
 LD = np.longdouble
 EPS = 2.220446049250313e-16  # the pre-regularisation of K_mm (cho_factor_stable_dev, pre_reg = true)
-TT, TBK = 128, 16            # Gram tile and k-tile of csrc/cg.hip
+TT, TBK = 128, 16            # Gram tile and k-tile of csrc/gram_tn.hip (precon_plan.h)
 SEEDS = (0, 1, 2)
 _POOL = ThreadPoolExecutor(8)
 
@@ -180,7 +181,7 @@ def precon_ld(X2, lam, v):
 
 
 def f32_form_ld(X2, L, lam):
-    """The definition above build_f32_form (csrc/cg.hip): X32 = float32(X2); G0 = I - lam L^-1 L^-T; M0 = L0^T L0 with
+    """The definition above build_f32_form (csrc/nystroem.hip): X32 = float32(X2); G0 = I - lam L^-1 L^-T; M0 = L0^T L0 with
     L0 L0^T = G0; G = X32^T X32 = L_G L_G^T; T0 = L_G^-T M0 L_G^-1.  Returns (X32 as long double, T0)."""
     m = L.shape[0]
     I = np.eye(m, dtype=LD)
@@ -201,6 +202,7 @@ def precon_f32_ld(X32, T0, lam, v):
 
 
 # ------------------------------------------------------------------ the host's branch arithmetic, restated
+# (written from the inline code before csrc/precon_plan.h existed; tests/test_precon_plan_cpu.py holds the header to it)
 
 def gram_plan(n, m, split=1, ldc=None):
     """gram_tn + syrk_tn_kernel: the lower tiles with FULL / ragged per tile (buffers are 16-byte aligned and the pitch is
@@ -264,7 +266,7 @@ def apply_plan(n, m, form, f32_rows_per=1024, f32_rw=4):
     return d
 
 
-# ------------------------------------------------------------------ float64 restatements of cg.hip (defects on request)
+# ------------------------------------------------------------------ float64 restatements of nystroem.hip / precon_apply.hip (defects on request)
 
 def _trsm_f64(X, L, defect=None):
     """tall_trsm.  defect 'trsm_last_block': the last, ragged 64-block receives its updates but is never solved."""

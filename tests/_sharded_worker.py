@@ -1,6 +1,6 @@
 """Worker of tests/test_hip_scale.py::test_sharded_iterative_two_processes_one_gpu (launched with
 torch.distributed.run, world_size ranks sharing GPU 0): trains the pcg_n9_m400 fixture through
-GDMLTrain with the iterative solver SHARDED over the ranks (or, solver 'analytic', the distributed Cholesky) -- csrc/cg.hip, predict.hip and comm.hip
+GDMLTrain with the iterative solver SHARDED over the ranks (or, solver 'analytic', the distributed Cholesky) -- csrc/nystroem.hip, precon_apply.hip, cg.hip, predict.hip and comm.hip
 with host-staged (gloo) collectives -- and writes rank 0's result next to the output path."""
 import os
 import sys

@@ -309,7 +309,7 @@ def test_inducing_point_memory_model_is_per_shard():
     """Iterative.max_n_inducing_pts_device: the largest k whose footprint (this rank's rows of K_nm + the m x m block + its
     backup) fits the budget; the row term shrinks with the number of ranks, the replicated m x m terms do not.  From 1 GiB
     of factor per rank the library builds the fp32 form (rounded in place over the fp64 factor) and needs T0 + four m x m work
-    matrices for it (csrc/cg.hip::build_f32_form): the model counts them (round 6)."""
+    matrices for it (csrc/nystroem.hip::build_f32_form): the model counts them (round 6)."""
     from sgdml_amd.solvers.iterative import Iterative
 
     M, N = 5000, 21

@@ -1,7 +1,7 @@
 """Multi-process (world_size 2 and 3, gloo, CPU) tests of the sharded iterative solver's structure.
 
 The GPU library issues RCCL collectives itself; what can be validated without GPUs is the
-ALGORITHM it implements (csrc/cg.hip, csrc/comm.hip): contiguous point shards, row-sharded
+ALGORITHM it implements (csrc/nystroem.hip, csrc/precon_apply.hip, csrc/cg.hip, csrc/comm.hip): contiguous point shards, row-sharded
 Nystroem factor with an all-reduced K_mm and K_nm^T K_nm, row-sharded preconditioner
 (all-reduce of an m-vector + all-gather), query-sharded mat-vec (all-gather) and replicated CG
 scalars.  Here that algorithm runs with real multi-process collectives, the NumPy oracle standing
@@ -157,7 +157,7 @@ def test_sharded_pcg_matches_single_process(tmp_path, case, world):
 
 
 def _sharded_solve_E(rank, world, case, rtol, out_dir):
-    """The row-sharded Nystroem / PCG algorithm WITH energy constraints (csrc/cg.hip since round 6): a rank holds the force rows
+    """The row-sharded Nystroem / PCG algorithm WITH energy constraints (csrc/nystroem.hip, csrc/precon_apply.hip since round 6): a rank holds the force rows
     of its points followed by their energy rows, the replicated vectors are rank-major (sharded_vector_positions = VecLayout::pos),
     every result is one all-gather of `chunk` entries, the CG runs over the padded vectors."""
     import scipy.linalg as sla

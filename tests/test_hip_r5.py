@@ -79,7 +79,7 @@ def test_preconditioner_forms_agree(golden, ctx):
         # (n4_p6_pbc: smallest squared singular value 0.77) -- such a direction weighs lam / (sigma_i + lam) ~ 0.2 in the
         # operator, and there it is the REFERENCE's stored factor whose Gram matrix is off the exact I - lam L^-1 L^-T by the
         # rounding error of K_nm^T K_nm relative to lam (1e-13 / 1e-10).  Round 6: on n10_p2_pbc (lam = 1e-4, weakest direction
-        # 0.06) this assertion found that round 5's T0 used L0 L0^T where the operator needs L0^T L0 (3 % off; csrc/cg.hip).
+        # 0.06) this assertion found that round 5's T0 used L0 L0^T where the operator needs L0^T L0 (3 % off; csrc/nystroem.hip).
         piv = ctx.get_option('pcg.f32_last_min_pivot')
         if out[3][2] & 4:
             tol3 = 1e-5 if (piv >= 0.99 or lam >= 1e-6) else 1e-2

@@ -214,7 +214,7 @@ def test_rccl_probe_child_process_one_rank():
 
 @pytest.mark.parametrize('world', [2, 3])
 def test_sharded_iterative_processes_share_one_gpu(tmp_path, world):
-    """The sharded iterative solver END TO END through GDMLTrain / Iterative / cg.hip / comm.hip: `world`
+    """The sharded iterative solver END TO END through GDMLTrain / Iterative / nystroem.hip, precon_apply.hip, cg.hip / comm.hip: `world`
     processes (torch.distributed.run, gloo) share GPU 0, each holds a row shard of the Nystroem factor and a
     query shard of the mat-vec, the collectives are host-staged.  Must reproduce the reference's PCG run on the
     same inducing columns (iteration count, residual) and make the same number of collectives per iteration."""

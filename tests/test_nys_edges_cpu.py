@@ -1,5 +1,5 @@
 """The inputs, bounds, allowances and case tables of the Nystroem edge tests (tests/_nys_ref.py) are sound before a kernel
-is blamed: the float64 restatements of csrc/cg.hip stay inside every stage bound on every grid case, each seeded defect of
+is blamed: the float64 restatements of csrc/nystroem.hip and csrc/precon_apply.hip stay inside every stage bound on every grid case, each seeded defect of
 a kernel branch breaks the check that is meant to see it (stage checks: ratio > 1; measured checks: more than 100 x the
 allowance), the grid reaches every branch its table names -- and does not reach what is declared out of scope -- and the
 inputs meet the conditions the device code needs to stay on the path under test.  No GPU."""

@@ -1,5 +1,5 @@
-"""The Nystroem build and its application on the GPU (csrc/cg.hip: gdml_nystroem_factor, gdml_nystroem_lev_scores,
-gdml_precon_apply) at the edges of every kernel branch, against long-double references on the host (tests/_nys_ref.py;
+"""The Nystroem build and its application on the GPU (csrc/nystroem.hip: gdml_nystroem_factor, gdml_nystroem_lev_scores on
+gram_tn.hip and tall_trsm of chol_solve.hip; csrc/precon_apply.hip: gdml_precon_apply) at the edges of every kernel branch, against long-double references on the host (tests/_nys_ref.py;
 its bounds, allowances and case tables are checked without a GPU by tests/test_nys_edges_cpu.py).
 
 Every case loads ITS matrix into the resident buffer with the pitch padding and the m-row work block set to NaN, runs the
