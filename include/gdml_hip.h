@@ -780,7 +780,7 @@ int gdml_predict_hessian_dev(gdml_ctx* ctx, const double* R_dev, int64_t B, cons
                              const double* lat_inv, double* E_dev, double* F_dev, double* H_dev);
 
 /* Eigenvalues and eigenvectors of M symmetric n x n matrices on the device: one workgroup per matrix (grid-stride over M),
- * cyclic two-sided Jacobi with the round-robin ordering -- the sweep loop of gdml_sym_eig_absv (csrc/sym_eig.h holds the one
+ * cyclic two-sided Jacobi with the round-robin ordering -- the sweep loop of gdml_sym_eig_absv (csrc/sym_eig.hip; csrc/sym_eig.h holds the one
  * copy both kernels call).  Only the mean of the two triangles of A enters.
  *   w (M,n): eigenvalues ascending; equal ones in the order of their Jacobi columns.
  *   V (M,n,n) or NULL: V[m][k][:] is the unit eigenvector of w[m][k], a ROW; its component of largest magnitude is positive

@@ -86,10 +86,12 @@ struct Model {
 //                     (gdml_predict_cov_few hands a batch beyond its limit to gdml_predict_cov BEFORE it carves anything; its
 //                     inverted diagonal blocks are the fixed part of SLOT_GRAM_WS and live for one call); tall_trsm in between
 //                     requests SLOT_PANEL_TRSM only.  gdml_factor_extend / gdml_factor_remove release both: they were sized for n
-//   SLOT_VIB_WS       gdml_sym_eig, gdml_sym_eig_dev and gdml_vib_run carve it anew and call none of the others; the Hessian call
-//                     inside gdml_vib_run holds the scratch buffer and SLOT_PREDICT_WS only
-//   SLOT_EF_WS        gdml_ef_run alone: its state lives there for the whole call, across the Hessian calls of every evaluation
-//                     (which hold the scratch buffer and SLOT_PREDICT_WS only)
+//   SLOT_VIB_WS       gdml_sym_eig, gdml_sym_eig_dev (sym_eig.hip) and gdml_vib_run (vib.hip: a chunk laid out by SpectrumWs,
+//                     sym_eig_plan.h) carve it anew and call none of the others; the Hessian call inside spectrum_slice
+//                     holds the scratch buffer and SLOT_PREDICT_WS only
+//   SLOT_EF_WS        gdml_ef_run alone (ef.hip): a slice laid out by SpectrumWs without R, then its state, which lives there
+//                     for the whole call, across the Hessian calls of every evaluation (which hold the scratch buffer and
+//                     SLOT_PREDICT_WS only)
 enum CtxSlot {
   SLOT_PREDICT_WS = 0,      // row-split partials of F_x and E (predict_device, predict_fused); workspace of hess_device
   SLOT_MATVEC_OUT = 1,      // forces and energies of this rank's query points (matvec_device)
@@ -260,6 +262,8 @@ void phase_begin(gdml_ctx* ctx);
 int phase_resolve(gdml_ctx* ctx);  // reads a pending phase timer (waits for its end event)
 void precon_release_f32(gdml_ctx* ctx);  // nystroem.hip
 void precon_release_aux(gdml_ctx* ctx);
+// |eigenvectors| of M symmetric N x N matrices on the device, columns by decreasing eigenvalue: d_v [a][k], d_vT [k][a] (sym_eig.hip)
+int sym_eig_absv_dev(gdml_ctx* ctx, const double* d_adj, double* d_v, double* d_vT, int64_t M, int N);
 int ktime_begin(gdml_ctx* ctx);  // returns slot or -1
 void ktime_end(gdml_ctx* ctx, int slot, const char* name, double work);
 int ktime_collect(gdml_ctx* ctx);

@@ -13,10 +13,9 @@
 //      shortest-path costs and the matching in LDS.  With distinct path costs the result does not depend on scan order; on an
 //      exact tie a column that is still free wins (scipy's rule), then the lower index;
 //   3. both Frobenius norms in ONE order of summation, so that an identity assignment reproduces `before` bit for bit.
-// The eigenvectors come from sym_eig_kernel below (batched Jacobi) unless the caller brings them; the spanning tree and the group
-// closure are host work (utils/perm.py).
+// The eigenvectors come from the batched Jacobi eigensolver (sym_eig_absv_dev, sym_eig.hip) unless the caller brings them; the
+// spanning tree and the group closure are host work (utils/perm.py).
 #include "common.h"
-#include "sym_eig.h"
 
 #include <cmath>
 #include <vector>
@@ -222,117 +221,10 @@ __global__ void __launch_bounds__(64) perm_match_kernel(PermMatchArgs A) {
 }
 
 
-// ------------------------------------------------------------------------------------------
-// Eigenvectors of the M symmetric N x N distance matrices (the reference: numpy.linalg.eig per geometry, perm.py:183-187; the
-// host form here: one batched LAPACK eigh -- 4.5 s for 1000 geometries of 100 atoms, more than the matching itself).  One
-// workgroup per matrix, cyclic two-sided Jacobi with the round-robin ordering: a step rotates N/2 disjoint index pairs at once
-// (angles from the current matrix, then all row updates, then all column updates -- disjoint rotations commute), N - 1 steps
-// visit every pair once.  The sweep loop, its storage routes and its stopping rule are sym_eig.h's (gdml_sym_eig in vib.hip
-// runs the same loop).  Output: |V| with columns by decreasing
-// eigenvalue, the form the matching consumes (only |V| enters, perm.py:66-70, so the sign convention is immaterial).
-// ------------------------------------------------------------------------------------------
-struct SymEigArgs {
-  const double* adj;  // (M, N, N)
-  double* absv;       // (M, N, N) out: [a][k]
-  double* absvT;      // (M, N, N) out: [k][a]
-  double* work;       // gridDim.x x 2 x N x NP doubles (only the parts that do not fit in LDS are used)
-  int64_t M;
-  int N, NP;          // NP: row pitch of the working matrices (N + 1 when N is even: column accesses spread over the banks)
-  int a_in_lds, v_in_lds;
-};
-
-__global__ void __launch_bounds__(256) sym_eig_kernel(SymEigArgs S) {
-  extern __shared__ __attribute__((aligned(8))) unsigned char eig_raw[];
-  const int N = S.N, NP = S.NP, tid = threadIdx.x;
-  const SymEigWork w = sym_eig_carve(eig_raw, N, NP, S.a_in_lds, S.v_in_lds, S.work + (int64_t)blockIdx.x * 2 * N * NP);
-  double* A = w.A;
-  double* V = w.V;
-
-  for (int64_t mat = blockIdx.x; mat < S.M; mat += gridDim.x) {
-    const double* G = S.adj + mat * N * N;
-    for (int e = tid; e < N * N; e += 256) {
-      const int r = e / N, c = e - r * N;
-      A[r * NP + c] = 0.5 * (G[e] + G[c * N + r]);
-      V[r * NP + c] = (r == c) ? 1.0 : 0.0;
-    }
-    __threadfence_block();
-    __syncthreads();
-    sym_eig_sweeps(w, N, NP, tid);  // (sym_eig.h)
-    // columns by decreasing eigenvalue (ties: lower index first), absolute values out
-    double* O = S.absv + mat * N * N;
-    double* OT = S.absvT + mat * N * N;
-    for (int i = tid; i < N; i += 256) {
-      const double li = A[i * NP + i];
-      int rank = 0;
-      for (int j = 0; j < N; ++j) {
-        const double lj = A[j * NP + j];
-        rank += (lj > li) || (lj == li && j < i);
-      }
-      for (int a = 0; a < N; ++a) {
-        const double av = fabs(V[a * NP + i]);
-        O[a * N + rank] = av;
-        OT[rank * N + a] = av;
-      }
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-}
-
 }  // namespace
 
-// |V| (columns by decreasing eigenvalue) of M symmetric N x N matrices already on the device; d_v [a][k], d_vT [k][a]
-static int launch_sym_eig(gdml_ctx* ctx, const double* d_adj, double* d_v, double* d_vT, int64_t M, int N) {
-  SymEigArgs e;
-  e.adj = d_adj; e.absv = d_v; e.absvT = d_vT; e.M = M; e.N = N;
-  const SymEigPlan pl = sym_eig_plan(ctx->num_cus, M, N);
-  e.NP = pl.NP; e.a_in_lds = pl.a_in_lds; e.v_in_lds = pl.v_in_lds;
-  const size_t eig_lds = pl.lds;
-  const int64_t eg = pl.grid;
-  double* d_w = nullptr;
-  GDML_TRY(ctx_alloc(ctx, (void**)&d_w, eg * 2 * (int64_t)N * e.NP * 8));
-  e.work = d_w;
-  hipError_t se = hipSuccess;
-  if (eig_lds > 48 * 1024)
-    se = hipFuncSetAttribute(reinterpret_cast<const void*>(sym_eig_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)eig_lds);
-  if (se == hipSuccess) {
-    const int es = ktime_begin(ctx);
-    hipLaunchKernelGGL(sym_eig_kernel, dim3((unsigned)eg), dim3(256), eig_lds, ctx->stream, e);
-    ktime_end(ctx, es, "sym_eig", (double)M);
-    ctx->launch_counter++;
-    se = hipGetLastError();
-    if (se == hipSuccess) se = hipStreamSynchronize(ctx->stream);  // (the work buffer is released below)
-  }
-  ctx_free(ctx, d_w);
-  if (se != hipSuccess) return gdml_fail(ctx, GDML_ERR_HIP, "eigenvector kernel of the symmetry search: %s", hipGetErrorString(se));
-  return GDML_OK;
-}
-
-// |eigenvectors| of M symmetric N x N matrices, columns by decreasing eigenvalue (what gdml_perm_match computes when it is not
-// handed any): for tests and for callers that want them on the host.
-extern "C" int gdml_sym_eig_absv(gdml_ctx* ctx, const double* adj, int64_t M, int N, double* absv_out) {
-  if (!ctx) return GDML_ERR_INVALID;
-  if (!adj || !absv_out || M < 0 || N < 1 || N > GDML_MAX_ATOMS)
-    return gdml_fail(ctx, GDML_ERR_INVALID, "gdml_sym_eig_absv: bad arguments (M=%lld N=%d)", (long long)M, N);
-  if (M == 0) return GDML_OK;
-  HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const int64_t bytes = M * (int64_t)N * N * 8;
-  double *d_a = nullptr, *d_v = nullptr, *d_t = nullptr;
-  int rc = ctx_alloc(ctx, (void**)&d_a, bytes);
-  if (rc == GDML_OK) rc = ctx_alloc(ctx, (void**)&d_v, bytes);
-  if (rc == GDML_OK) rc = ctx_alloc(ctx, (void**)&d_t, bytes);
-  if (rc == GDML_OK && hipMemcpyAsync(d_a, adj, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-    rc = gdml_fail(ctx, GDML_ERR_HIP, "gdml_sym_eig_absv: upload failed");
-  if (rc == GDML_OK) rc = launch_sym_eig(ctx, d_a, d_v, d_t, M, N);
-  if (rc == GDML_OK && (hipMemcpyAsync(absv_out, d_v, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                        hipStreamSynchronize(ctx->stream) != hipSuccess))
-    rc = gdml_fail(ctx, GDML_ERR_HIP, "gdml_sym_eig_absv: download failed");
-  ctx_free(ctx, d_a); ctx_free(ctx, d_v); ctx_free(ctx, d_t);
-  return rc;
-}
-
 // absv: (M,N,N) |eigenvectors| of the distance matrices, columns by decreasing eigenvalue, or NULL: computed on the device
-// (sym_eig_kernel); adj: (M,N,N) distance matrices;
+// (sym_eig_absv_dev); adj: (M,N,N) distance matrices;
 // species: (N).  cost_out (M,M): entries (i,j), i < j (the rest is zero); found_ij (capacity,2) / found_perm
 // (capacity,N): the kept assignments in no particular order, *n_found of them (if *n_found > capacity the call has to be repeated
 // with more room: the first `capacity` are valid).
@@ -401,7 +293,7 @@ extern "C" int gdml_perm_match(gdml_ctx* ctx, const double* absv, const double* 
     PM_HIP(hipMemcpyAsync(d_v, absv, (size_t)(M * NN * 8), hipMemcpyHostToDevice, st));
     PM_HIP(hipMemcpyAsync(d_vT, hT.data(), (size_t)(M * NN * 8), hipMemcpyHostToDevice, st));
   } else {
-    rc = launch_sym_eig(ctx, d_adj, d_v, d_vT, M, N);
+    rc = sym_eig_absv_dev(ctx, d_adj, d_v, d_vT, M, N);
     if (rc != GDML_OK) {
       release();
       return rc;

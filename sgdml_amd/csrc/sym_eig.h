@@ -1,35 +1,23 @@
-// The batched cyclic Jacobi eigensolver's shared parts: the launch plan (storage route, LDS bytes, grid), the carving of a
-// workgroup's LDS and the sweep loop itself.  Two kernels call them: sym_eig_kernel (perm_match.hip: |V| by decreasing
-// eigenvalue for the symmetry search) and sym_eig_full_kernel (vib.hip: eigenvalues ascending, signed eigenvectors as rows).
+// The batched cyclic Jacobi eigensolver's device parts: the carving of a workgroup's LDS, the off-diagonal mass and the sweep
+// loop itself, which the one kernel template of sym_eig.hip runs under either of its output policies; and what the other files
+// call of sym_eig.hip.  The launch plan (storage route, LDS bytes, grid, work matrices) is sym_eig_plan.h's.
 // One workgroup of 256 threads per matrix, round-robin ordering: a step rotates N/2 disjoint index pairs at once (angles from
 // the current matrix, then all row updates, then all column updates -- disjoint rotations commute), N - 1 steps visit every
 // pair once.  The working matrix A and the accumulated rotations V live in LDS when both fit (N <= 100), only A when it alone
 // fits (N <= 141), both in device memory above that.
 #pragma once
 #include "common.h"
+#include "sym_eig_plan.h"
 
 constexpr int SYM_EIG_MAX_SWEEPS = 30;
 
-struct SymEigPlan {
-  int NP;                  // row pitch of the working matrices (N + 1 when N is even: column accesses spread over the banks)
-  int a_in_lds, v_in_lds;
-  size_t lds;              // dynamic LDS bytes of a workgroup
-  int64_t grid;            // workgroups (at most M)
-};
-
-static inline SymEigPlan sym_eig_plan(int num_cus, int64_t M, int N) {
-  SymEigPlan p;
-  p.NP = (N % 2 == 0) ? N + 1 : N;
-  const int ne = (N + 1) & ~1, npairs = ne / 2;
-  const size_t fixed = (size_t)(2 * npairs) * 8 + (size_t)(2 * npairs + (npairs & 1) * 2) * 4 + 8 * 8;
-  const size_t mat_b = (size_t)N * p.NP * 8, lds_max = 160 * 1024;
-  p.a_in_lds = fixed + mat_b <= lds_max;
-  p.v_in_lds = p.a_in_lds && fixed + 2 * mat_b <= lds_max;
-  p.lds = fixed + (p.a_in_lds ? mat_b : 0) + (p.v_in_lds ? mat_b : 0);
-  p.grid = (int64_t)num_cus * (p.lds > 80 * 1024 ? 1 : p.lds > 40 * 1024 ? 2 : 4);
-  if (p.grid > M) p.grid = M;
-  return p;
-}
+// ---- sym_eig.hip, for vib.hip -------------------------------------------------------------------------------------------------
+// Queues the eigen-kernel (eigenvalues ascending, signed eigenvectors as rows, sweeps) for M matrices on the device, p.grid
+// workgroups; work: p.work_doubles doubles.  d_V may be d_A, or null.  Counts the launch; does not synchronise.
+hipError_t sym_eig_rows_launch(gdml_ctx* ctx, const SymEigPlan& p, const double* d_A, int64_t M, int N, double* d_w, double* d_V,
+                               int64_t* d_sweeps, double* work);
+// the first matrix (numbered from m0) the cap stopped above the threshold becomes the call's error
+int sym_eig_check_sweeps(gdml_ctx* ctx, const char* fn, const int64_t* sweeps, int64_t M, int64_t m0);
 
 // a workgroup's pieces: cs [npairs][2], pq [npairs][2], red [8] in LDS; A and V in LDS or in the workgroup's 2 x N x NP
 // doubles of device memory gw

@@ -1,5 +1,5 @@
 // What the on-device trajectory entries (gdml_md_run in md.hip, gdml_pimd_run in pimd.hip, gdml_relax_run in relax.hip,
-// gdml_neb_run in neb.hip, gdml_cell_relax_run in cellrelax.hip, gdml_ef_run in vib.hip) share:
+// gdml_neb_run in neb.hip, gdml_cell_relax_run in cellrelax.hip, gdml_ef_run in ef.hip) share:
 // the counter-based noise, the fixed reduction tree, the argument checks and prelude, the recorder of a chunk of frames and
 // the chunk loop of the two MD entries, and the chunk loop of the four entries whose replicas freeze on their own
 // (gdml_relax_run, gdml_neb_run, gdml_cell_relax_run, gdml_ef_run), whose host-only part is traj_host.h's.

@@ -793,7 +793,7 @@ class GDMLPredict(object):
         out['freq'] = np.sign(out['w2']) * np.sqrt(np.abs(out['w2']))
         return out
 
-    # ---- eigenvector following on the device (gdml_ef_run, csrc/vib.hip)
+    # ---- eigenvector following on the device (gdml_ef_run, csrc/ef.hip)
 
     def stationary_point(self, R0, fmax, order=1, follow=None, max_steps=100, trust_start=0.1, trust_max=0.3, trust_min=1e-4,
                          project=None, state=None, lattice=None, f_unit=1.0, record_every=0):

@@ -1,4 +1,4 @@
-"""NumPy restatement of the on-device eigenvector following (gdml_ef_run, csrc/vib.hip; GDMLPredict.stationary_point) around a
+"""NumPy restatement of the on-device eigenvector following (gdml_ef_run, csrc/ef.hip; GDMLPredict.stationary_point) around a
 Hessian callback, the margins of its decisions, and the toy runs of the tests.  Test helper only: the package never imports it.
 
 The step (the contract; include/gdml_hip.h states the same).  g = -f_unit * F, D = f_unit * H with E, F, H those of

@@ -1,5 +1,5 @@
 """NumPy restatement of the harmonic vibrational analysis (gdml_vib_run, csrc/vib.hip) and of the batched Jacobi eigensolver
-under it (gdml_sym_eig, csrc/sym_eig.h), with the conventions both state.  Test helper only: the package never imports it.
+under it (gdml_sym_eig, csrc/sym_eig.hip; the sweep loop: csrc/sym_eig.h), with the conventions both state.  Test helper only: the package never imports it.
 
 The eigensolver.  Cyclic two-sided Jacobi, round-robin ordering: with ne = n rounded up to even, m = ne - 1 and np = ne / 2, step
 s = 0 .. m - 1 of a sweep rotates the pairs (s mod m, m) and ((s + t) mod m, (s + m - t) mod m), t = 1 .. np - 1 (the smaller
@@ -179,7 +179,81 @@ def vibrations(H, R, masses, h_scale=1.0, project=2):
                 Lambda=lam)
 
 
-# ---- geometries and toys of the tests
+# ---- the launch plan of the eigensolver and the slice of a spectrum (csrc/sym_eig_plan.h), restated
+
+LDS_MAX = 160 * 1024
+VIB_CHUNK_BYTES = 256 << 20
+
+
+def sym_eig_plan(num_cus, M, N, cap_global):
+    """NP, a_in_lds, v_in_lds, lds, grid, work_doubles.  LDS of a workgroup: cs [npairs][2] doubles, pq [npairs][2] ints padded to
+    a multiple of 8 bytes, red [8] doubles, then A and V (N x NP doubles each) as far as they fit under 160 KiB; 4, 2 or 1
+    workgroups per compute unit by the LDS they take, at most M, and with cap_global at most one per compute unit once A is in
+    device memory; the device-memory work area is two matrices per workgroup unless V is in LDS."""
+    NP = N + 1 if N % 2 == 0 else N
+    npairs = (N + 1) // 2
+    fixed = 2 * npairs * 8 + (2 * npairs + (npairs % 2) * 2) * 4 + 64
+    mat = N * NP * 8
+    a = fixed + mat <= LDS_MAX
+    v = a and fixed + 2 * mat <= LDS_MAX
+    lds = fixed + (mat if a else 0) + (mat if v else 0)
+    grid = num_cus * (1 if lds > 80 * 1024 else 2 if lds > 40 * 1024 else 4)
+    if cap_global and not a:
+        grid = min(grid, num_cus)
+    grid = min(grid, M)
+    return dict(NP=NP, a_in_lds=int(a), v_in_lds=int(v), lds=lds, grid=grid, work_doubles=0 if v else grid * 2 * N * NP)
+
+
+SPECTRUM_FIELDS = ('work', 'H', 'R', 'F', 'w', 'info', 'E', 'mass', 'sweeps', 'n_rigid', 'n_neg')
+
+
+def spectrum_ws(len_, N, work_doubles, with_R):
+    """[(field, offset, length)] of a slice's workspace in 8-byte words, in SPECTRUM_FIELDS' order, and the total."""
+    n3 = 3 * N
+    sizes = dict(work=work_doubles, H=len_ * n3 * n3, R=len_ * n3 if with_R else 0, F=len_ * n3, w=len_ * n3, info=4 * len_,
+                 E=len_, mass=N, sweeps=len_, n_rigid=len_, n_neg=len_)
+    out, o = [], 0
+    for f in SPECTRUM_FIELDS:
+        out.append((f, o, sizes[f]))
+        o += sizes[f]
+    return out, o
+
+
+def spectrum_slice_len(num_cus, B, n3, option):
+    """Geometries per slice: VIB_CHUNK_BYTES over the bytes one geometry brings (its share of the workspace with R and the work
+    matrices of one workgroup), whole 64s above 64; a positive option instead; within 1 .. B."""
+    p1 = sym_eig_plan(num_cus, 1, n3, True)
+    per = (n3 * n3 + 3 * n3 + 8 + p1['work_doubles']) * 8
+    chunk = VIB_CHUNK_BYTES // per
+    if chunk > 64:
+        chunk = chunk // 64 * 64
+    if option > 0:
+        chunk = option
+    return min(max(chunk, 1), B)
+
+
+# ---- inputs, geometries and toys of the tests
+
+def eig_inputs(n, M=3, seed=0):
+    """M random symmetric matrices of order n."""
+    rs = np.random.RandomState(1000 * n + seed)
+    A = rs.standard_normal((M, n, n))
+    return A + A.transpose(0, 2, 1)
+
+
+def eig_special(n):
+    """diagonal, zero, c I + rank one (an (n - 1)-fold eigenvalue), random scaled by 2^30 and by 2^-30."""
+    rs = np.random.RandomState(7 * n + 1)
+    u = rs.standard_normal(n)
+    R = eig_inputs(n, 1, seed=3)[0]
+    return np.stack([np.diag(rs.standard_normal(n)), np.zeros((n, n)), 1.5 * np.eye(n) + np.outer(u, u), R * 2.0**30, R * 2.0**-30])
+
+
+def geoms(g):
+    """Seven geometries of a fixture: its first six test geometries and its first training geometry."""
+    Rt = g['R_test'].reshape(len(g['R_test']), -1)
+    return np.concatenate([Rt[:6], g['R_train'][:1].reshape(1, -1)])
+
 
 def collinear(bent=False):
     """Five atoms on a line of direction (1, 2, 3) with unequal spacings 1.0 .. 1.7 and masses 1, 12, 16, 1, 12 ((15,), (5,));

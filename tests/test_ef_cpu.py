@@ -1,4 +1,4 @@
-"""CPU-side checks of the eigenvector-following search (gdml_ef_run, csrc/vib.hip; GDMLPredict.stationary_point): the NumPy
+"""CPU-side checks of the eigenvector-following search (gdml_ef_run, csrc/ef.hip; GDMLPredict.stationary_point): the NumPy
 restatement (tests/_ef_ref.py) on the toy models of the band and relaxation tests, the margins of every decision of every run the
 GPU test compares, and the argument errors of the C entry and of stationary_point() that need no device."""
 import ctypes as C

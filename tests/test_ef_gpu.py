@@ -1,4 +1,4 @@
-"""Eigenvector following on the GPU (gdml_ef_run, csrc/vib.hip; GDMLPredict.stationary_point): step-by-step parity with the NumPy
+"""Eigenvector following on the GPU (gdml_ef_run, csrc/ef.hip; GDMLPredict.stationary_point): step-by-step parity with the NumPy
 restatement (tests/_ef_ref.py) on the fixtures, the toy runs to convergence, a band refined end to end, bit-identity and error
 paths.
 

@@ -430,7 +430,7 @@ def test_device_matching_is_the_host_matching(ctx):
     applies the reference's acceptance rule (perm.py:76-89).  Against the NumPy / SciPy form in sgdml_amd/utils/perm.py, which
     the CPU suite pins to the reference's output: the SAME pairs kept, the SAME assignments, pair costs to 1e-13 relative; and
     find_perms with the device matching returns the reference's groups (tests/golden/perm_c3.npz) element for element.  The
-    device side computes its own eigenvectors (sym_eig_kernel), the host side LAPACK's: same assignments."""
+    device side computes its own eigenvectors (csrc/sym_eig.hip), the host side LAPACK's: same assignments."""
     from sgdml_amd.utils import perm
 
     kept_nontrivial = 0

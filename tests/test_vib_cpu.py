@@ -1,4 +1,4 @@
-"""CPU-side checks of the harmonic vibrational analysis (gdml_vib_run, gdml_sym_eig, csrc/vib.hip; GDMLPredict.vibrations): the
+"""CPU-side checks of the harmonic vibrational analysis (gdml_vib_run, csrc/vib.hip; gdml_sym_eig, csrc/sym_eig.hip; GDMLPredict.vibrations): the
 NumPy restatement (tests/_vib_ref.py) against LAPACK and on the toy models of the relaxation and band tests, the margins of the
 rank rule, the two host helpers, and the argument errors of the C entries and of vibrations() that need no device."""
 import ctypes as C

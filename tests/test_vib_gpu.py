@@ -1,4 +1,4 @@
-"""Harmonic vibrational analysis on the GPU (csrc/vib.hip): the batched eigensolver against LAPACK, vibrations() against the
+"""Harmonic vibrational analysis on the GPU (csrc/vib.hip; the eigensolver: csrc/sym_eig.hip): the batched eigensolver against LAPACK, vibrations() against the
 NumPy restatement (tests/_vib_ref.py) applied to the device's own Hessians, the physics of the two toy models, invariances,
 bit-identity and error paths.
 
@@ -22,6 +22,7 @@ import _hessian_ref as hr  # noqa: E402
 import _neb_ref as nr  # noqa: E402
 import _relax_ref as rr  # noqa: E402
 import _vib_ref as vr  # noqa: E402
+from _vib_ref import eig_inputs, eig_special, geoms as _geoms  # noqa: E402
 from sgdml_amd import _lib  # noqa: E402
 from sgdml_amd._lib import VibParams  # noqa: E402,F401  (the binding of gdml_vib_run: this file tests nothing without it)
 from sgdml_amd.predict import GDMLPredict  # noqa: E402
@@ -39,29 +40,9 @@ def _load(name):
     return dict(np.load(os.path.join(GOLDEN, name + '.npz')))
 
 
-def _geoms(g):
-    Rt = g['R_test'].reshape(len(g['R_test']), -1)
-    return np.concatenate([Rt[:6], g['R_train'][:1].reshape(1, -1)])
-
-
 @functools.lru_cache(maxsize=None)
 def _ctx():
     return _lib.Context(0)
-
-
-def eig_inputs(n, M=3, seed=0):
-    """M random symmetric matrices of order n."""
-    rs = np.random.RandomState(1000 * n + seed)
-    A = rs.standard_normal((M, n, n))
-    return A + A.transpose(0, 2, 1)
-
-
-def eig_special(n):
-    """diagonal, zero, c I + rank one (an (n - 1)-fold eigenvalue), random scaled by 2^30 and by 2^-30."""
-    rs = np.random.RandomState(7 * n + 1)
-    u = rs.standard_normal(n)
-    R = eig_inputs(n, 1, seed=3)[0]
-    return np.stack([np.diag(rs.standard_normal(n)), np.zeros((n, n)), 1.5 * np.eye(n) + np.outer(u, u), R * 2.0**30, R * 2.0**-30])
 
 
 def eig_check(A, w, V, what=''):
